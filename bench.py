@@ -15,6 +15,13 @@ resident in HBM before the timed region.  Each step evaluates all N^2 pairs
 (diagonal included), so value = N^2 * K / time (whole job, all ranks);
 sim-steps/s = K / time.  Rows are partitioned, total work is fixed:
 scaling "strong".
+
+A plain run does what the headline value needs and no more: set-up, settle
+and warm-up steps, the K timed steps, the result line.  ``--dump-outputs DIR``
+also writes what the timed path computed in its last step (the state arrays
+and the last CD call's pairs) as ``DIR/<name>.npy``.  ``--full`` adds the
+secondary measurements: the CPU baseline, the cadence / reuse / geo-matrix /
+1M variants, the drop-in ``detect()`` and ``ASAS.update`` lines.
 """
 import argparse
 import json
@@ -55,6 +62,55 @@ TIMING_SAMPLE = 20           # detects per HIP-event-timed detect in the warm-up
                              # (bsa_set_timing_sample; each timed one costs ~24 us of event bubbles,
                              # profiles/r02 kernel trace); the headline batch times ONE detect, its first
                              # (the stage times the roofline uses; ~0.4 us per step at 60 steps)
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000   # --dump-outputs: all files together stay below this
+DUMP_SEED = 20240607                # ... by a fixed sample of the arrays that are too long
+
+
+def dump_sample(a, cap):
+    """``a`` as a flat float64 array (float32 stays float32; integer and bool
+    values are exact in float64), cut to ``cap`` elements when longer: the
+    elements at a fixed, seeded, ascending choice of indices that depends on
+    the length alone, so two builds' dumps of equal length line up."""
+    a = np.asarray(a).ravel()
+    a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+    if a.size > cap:
+        a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, cap, replace=False))]
+    return a
+
+
+def dump_outputs(dirname, arrays):
+    """Write ``arrays`` (name -> array) as ``dirname/<name>.npy``, every array
+    with the same element cap (8-byte elements at the most), so that all of
+    them hold at most DUMP_MAX_BYTES.  Returns name -> [elements written, elements]."""
+    os.makedirs(dirname, exist_ok=True)
+    cap = DUMP_MAX_BYTES // (8 * max(len(arrays), 1))
+    done = {}
+    for name in sorted(arrays):
+        a = dump_sample(arrays[name], cap)
+        np.save(os.path.join(dirname, name + '.npy'), a)
+        done[name] = [int(a.size), int(np.asarray(arrays[name]).size)]
+    return done
+
+
+def timed_path_outputs(ctx, sim, world):
+    """What a caller of the timed path holds after its last step: the state
+    (``ResidentSim.read``, aircraft-index order) and the last CD call's pairs,
+    per-row flags and tcpamax (``fetch_pairs``; with several ranks all ranks'
+    pairs gathered to rank 0).  Collective with several ranks; rank 0's
+    dict, None elsewhere."""
+    state = sim.read()
+    if world > 1:
+        pairs = sim.gather_pairs(root=0)
+    else:
+        st = sim.stats()
+        pairs = ctx.fetch_pairs(st['n_conf'], st['n_los'])
+    if pairs is None:
+        return None
+    out = {'state_' + k: v for k, v in state.items()}
+    out.update(('pairs_' + k, v) for k, v in pairs.items() if v is not None)
+    return out
 
 
 def pmc_figures(lib_sha, path=PMC_JSON):
@@ -371,18 +427,30 @@ def main():
     ap.add_argument('--n', type=int, default=100000)
     ap.add_argument('--workload', default='box100k', choices=['box10k', 'box100k', 'global1m'])
     ap.add_argument('--cd-every', type=int, default=1)
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline run also take the secondary measurements: the CPU baseline, the '
+                         'variants (reference CD cadence, candidate-list reuse, geo matrix, global1m), the '
+                         'drop-in detect() and ASAS.update lines; --no-cpu / --no-variants leave some out')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the timed path computed in its last step (state arrays, the last CD '
+                         'call\'s pairs) as DIR/<name>.npy, float64, at most %d MB in all (longer arrays: a '
+                         'fixed seeded sample)' % (DUMP_MAX_BYTES // 1000000))
     ap.add_argument('--cpu-rows', type=int, default=1024)
-    ap.add_argument('--no-cpu', action='store_true')
+    ap.add_argument('--no-cpu', action='store_true',
+                    help='with --full: skip the CPU baseline and the drop-in detect() line')
     ap.add_argument('--reuse', type=float, nargs=2, default=None, metavar=('SIGMA_H', 'SIGMA_V'),
                     help='candidate-list reuse budgets [m] (bsa_set_candidate_reuse); default off')
     ap.add_argument('--no-variants', action='store_true',
-                    help='skip the secondary lines (reference CD cadence, candidate-list reuse)')
+                    help='with --full: skip the secondary lines (reference CD cadence, candidate-list reuse, '
+                         'geo matrix, global1m, drop-in detect(), ASAS.update)')
     ap.add_argument('--parity-steps', type=int, default=2,
                     help='with several GPUs: steps of the sharded run checked bitwise against one GPU first '
                          '(0: skip)')
     ap.add_argument('--dry-run', action='store_true',
                     help='resolve the ranks (spawning them if needed), report them, touch no GPU (launcher test)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1 (the timed batch)')
 
     rw = resolve_world(args.gpus)
     if rw[0] == 'spawn':
@@ -567,20 +635,26 @@ def main():
         if rank == 0:
             out['pair_gather'] = dict(ms=gms, n_conf=len(gp['ci']), n_los=len(gp['li']),
                                       note='bsa_gather_pairs to rank 0 (counts, then rank-order blocks)')
-    if not args.no_variants and not args.reuse:
+    if args.dump_outputs:   # before anything else runs on this context: the timed sim's own last step
+        arrays = timed_path_outputs(ctx, sim, world)
+        if rank == 0:
+            out['dumped_outputs'] = dict(dir=args.dump_outputs, elements=dump_outputs(args.dump_outputs, arrays),
+                                         note='name: [elements written, elements of the array]')
+    out['full'] = args.full
+    if args.full and not args.no_variants and not args.reuse:
         out['variants'] = variants(ctx, t, rank, world, args.warmup)
         if rank == 0:
             out['variants']['geo_matrix'] = geo_matrix_line(ctx, t)
         if args.workload == 'box100k':
             out['variants']['global1m'] = global1m_line(ctx, rank, world)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         out['cpu_baseline'] = cpu_baseline(t, args.cpu_rows)
         out['speedup_vs_cpu'] = value / out['cpu_baseline']['value']
         if not args.no_variants:
             d = dropin_detect_line(ctx, t)
             d['speedup_vs_cpu_detect'] = out['cpu_baseline']['detect_s_extrapolated'] * 1e3 / d['ms']['total']
             out['dropin_detect'] = d
-    if rank == 0 and world == 1 and not args.no_variants and args.workload == 'box100k':
+    if args.full and rank == 0 and world == 1 and not args.no_variants and args.workload == 'box100k':
         out['asas_update'] = asas_update_line(ctx, t)
     if rank == 0:
         print(json.dumps(out), flush=True)

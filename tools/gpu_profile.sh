@@ -50,7 +50,7 @@ if [ "${K24PASS:-1}" = 1 ]; then
   python tools/pmc_roofline.py $OUT/pmc_k24off.json $OUT/k24off_p1 $OUT/k24off_p2
   cp $OUT/pmc_k24off.json profiles/pmc_k24off.json
 fi
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; echo "bench rc=$rc"; cat $OUT/bench.json; [ $rc -eq 0 ] || exit $rc
 if [ "${PROBE:-0}" = 1 ]; then  # the per-rank share of a sharded step
   timeout -k 10 400 python -u tools/rowslice_probe.py box100k global1m > $OUT/rowslice_probe.log 2>&1
