@@ -18,8 +18,12 @@
 //   K1b exact      one lane per candidate: the reference's fp64 expression
 //                  sequence op for op (-ffp-contract=off), outputs appended
 //                  with one atomic per wave.
-//   K2  sort       radix sort on (i << 32 | j) = the reference's row-major
-//                  np.where order, then a gather.
+//   K2  rank       the reference's row-major np.where order: K1b drops each
+//                  pair into its row's bucket, k_rowblk sums the row counts
+//                  and k_rank_rows ranks each row's pairs by column and
+//                  writes the outputs.  Bucket width 0 (a row overflowed the
+//                  widest bucket): scan of the row counts, scatter into row
+//                  segments, k_rank per segment.
 // Neither the spatial order nor the culling changes any result: every stage
 // before K1b only removes pairs that provably cannot be a conflict or a loss
 // of separation, and K1b evaluates the survivors exactly.
@@ -2477,10 +2481,53 @@ static int next_events(Ctx *c, hipEvent_t **ev) {
   return 0;
 }
 
+// The detect's A/B and diagnostic environment knobs, all
+// read once at the first use of any of them.  None is a product setting.
+struct DetectEnv {
+  int home_rec;        // BSA_HOME_REC=0/1: home mode stores fp64 column records (-1: home_records' rule)
+  bool stage1_t0;      // BSA_STAGE1_T0!=0: stage 1 at the t = 0 points, not the look-ahead midpoints
+  bool tp_super;       // BSA_TP_SUPER=1: K0d as k_tilepairs (super-tiles) at every size
+  bool k0z;            // BSA_K0Z=1: K0z always launched, never left to the last detect's K2
+  bool tp_halo_all;    // BSA_TP_HALO_ALL=1: halo mode's K0d sweeps all column tiles, not the present ones
+  bool tpr;            // BSA_TPR=0: no tile-pair list reuse
+  bool hk_trace;       // BSA_HK_TRACE=1: one stderr line per host-known rebuild decision (diagnostics)
+  double tpr_sh;       // BSA_TPR_SH>0: the kept list's horizontal budget [m]
+  int pf_pieces;       // BSA_PF_PIECES=1/2/4/8: units per prefilter item
+  int pf_heavy_t0;     // BSA_PF_HEAVY_T0=0..3: PfKnobs::t0
+  int pf_pieces_near;  // BSA_PF_PIECES_NEAR=1/2/4/8: units per near item
+  int fuse_exact;      // BSA_FUSE_EXACT=0/1: K1b fused into the prefilter (-1: detect_decide's rule)
+  int ov_grid_a;       // BSA_OV_GRID_A: workgroups per CU of the overlap's own-tile sweep (<= 0: the whole grid)
+  int k1b_grid;        // BSA_K1B_GRID>0: K1b's grid
+};
+static const DetectEnv &detect_env() {
+  static const DetectEnv env = [] {
+    const auto num = [](const char *name, int unset) {
+      const char *s = getenv(name);
+      return s ? atoi(s) : unset;
+    };
+    const char *sh = getenv("BSA_TPR_SH");
+    return DetectEnv{num("BSA_HOME_REC", -1),
+                     num("BSA_STAGE1_T0", 0) != 0,
+                     num("BSA_TP_SUPER", 0) == 1,
+                     num("BSA_K0Z", 0) == 1,
+                     num("BSA_TP_HALO_ALL", 0) == 1,
+                     num("BSA_TPR", 1) != 0,
+                     num("BSA_HK_TRACE", 0) == 1,
+                     sh ? atof(sh) : 0.0,
+                     num("BSA_PF_PIECES", 0),
+                     num("BSA_PF_HEAVY_T0", -1),
+                     num("BSA_PF_PIECES_NEAR", 0),
+                     num("BSA_FUSE_EXACT", -1),
+                     num("BSA_OV_GRID_A", 2),
+                     num("BSA_K1B_GRID", 0)};
+  }();
+  return env;
+}
+
 // stage 1 at the look-ahead midpoints unless KWIK, candidate
 // reuse, BSA_FLAG_STAGE1_T0 or the BSA_STAGE1_T0 environment variable
 // home mode: K1b reads stored fp64 column records (else builds them from the
-// state arrays); BSA_HOME_REC=0/1 overrides (see detect_enqueue)
+// state arrays); BSA_HOME_REC=0/1 overrides (see detect_decide)
 // One rank below 163 840 rows stores them (K1b then runs fused into the
 // prefilter, on stored records; 500k and 1M rows are slower with them).  A
 // rank of a row-sharded step (halo mode) does not: its two K0b launches (own
@@ -2492,18 +2539,50 @@ static int next_events(Ctx *c, hipEvent_t **ev) {
 // 0.1109 / 0.1082 (an older detect-only probe with per-stage events had
 // favoured the records by ~4 us).
 bool home_records(const Ctx *c, int64_t nrows) {
-  static const int home_rec_env = getenv("BSA_HOME_REC") ? atoi(getenv("BSA_HOME_REC")) : -1;
-  return home_rec_env >= 0 ? home_rec_env == 1 : c->halo_mode == 0 && nrows <= 163840;
+  const int env = detect_env().home_rec;
+  return env >= 0 ? env == 1 : c->halo_mode == 0 && nrows <= 163840;
 }
 
 int stage1_mid(int flags, bool reuse, int kwik) {
-  static const bool t0_env = getenv("BSA_STAGE1_T0") && atoi(getenv("BSA_STAGE1_T0")) != 0;
-  return (!reuse && !kwik && !(flags & BSA_FLAG_STAGE1_T0) && !t0_env) ? 1 : 0;
+  return (!reuse && !kwik && !(flags & BSA_FLAG_STAGE1_T0) && !detect_env().stage1_t0) ? 1 : 0;
 }
 
 static SoA6 soa(const DevBuf *a) {
   return SoA6{(const double *)a[0].p, (const double *)a[1].p, (const double *)a[2].p,
               (const double *)a[3].p, (const double *)a[4].p, (const double *)a[5].p};
+}
+
+// One K0b launch (k_prep_cols; the records go to Ctx::colrec / pfcol / pfvcol
+// / pfpcol).  The first block is the same at every launch of one detect
+// (DetectRun::prep_cols); a launch site states what differs from the neutral
+// values of the second.
+struct PrepColsLaunch {
+  int n = 0;
+  const unsigned *perm = nullptr;
+  int presorted = 1, rec = 0;
+  SoA6 own{}, intr{};
+  int distinct = 0, shared = 1;
+  double rpz = 0.0, hpz = 0.0, tla = 0.0;
+  int mid = 0;
+  ReuseParams rz{};
+  NfArgs nf{};
+
+  FusedBoxes fb{};  // no fused K0c
+  ZeroArgs zs{0, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, {}, {}};  // no fused K0z (only nrows set)
+  int tile_base = 0;               // workgroup b < nown prepares tile tile_base + b,
+  const int *tile_list = nullptr;  // the others slot b - nown of this list,
+  HaloUnpack hu{};                 // unpacked from the exchange first,
+  Counters *hcnt = nullptr;        // with a mismatch reported here
+  TprCheck tck{};                  // no budget checks
+  int nown = -1;                   // the whole grid
+};
+static int launch_prep_cols(Ctx *c, hipStream_t stream, unsigned grid, const PrepColsLaunch &a) {
+  hipLaunchKernelGGL(k_prep_cols, dim3(grid), dim3(kTile), 0, stream, a.n, a.perm, a.presorted, a.rec, a.own, a.intr,
+                     a.distinct, a.shared, a.rpz, a.hpz, a.tla, (ColRec *)c->colrec.p, (PFRec *)c->pfcol.p,
+                     (PFVel *)c->pfvcol.p, (float4 *)c->pfpcol.p, a.mid, a.rz, a.fb, a.zs, a.tile_base, a.tile_list,
+                     a.hu, a.hcnt, a.tck, a.nf, a.nown < 0 ? (int)grid : a.nown);
+  BSA_HIP(c, hipGetLastError());
+  return 0;
 }
 
 int prep_all_tiles(Ctx *c, double rpz, double hpz, double tla, unsigned long long nf_epoch) {
@@ -2518,20 +2597,20 @@ int prep_all_tiles(Ctx *c, double rpz, double hpz, double tla, unsigned long lon
       !ensure(c, c->gbox_c, ((n + kGroup - 1) / kGroup) * sizeof(TileBox), "column group boxes") ||
       !ensure(c, c->sbox_c, ((n + kSub - 1) / kSub) * sizeof(TileBox), "column sub-group boxes"))
     return -1;
-  const SoA6 own = soa(c->own);
-  const FusedBoxes fb{(TileBox *)c->sbox_c.p, (TileBox *)c->gbox_c.p, (TileBox *)c->tbox_c.p, nullptr, 0};
-  const ZeroArgs zs{0, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, {}, {}};
-  hipLaunchKernelGGL(k_prep_cols, dim3((unsigned)nct), dim3(kTile), 0, c->stream, (int)n,
-                     (const unsigned *)c->h2id.p, 1, 0, own, own, 0, 1, rpz, hpz, tla, (ColRec *)c->colrec.p,
-                     (PFRec *)c->pfcol.p, (PFVel *)c->pfvcol.p, (float4 *)c->pfpcol.p, stage1_mid(0, false, 0),
-                     ReuseParams{}, fb, zs, 0, (const int *)nullptr, HaloUnpack{}, (Counters *)nullptr, TprCheck{},
-                     NfArgs{nf_epoch ? (unsigned long long *)c->nonfin.p : nullptr, nf_epoch, nullptr}, nct);
-  BSA_HIP(c, hipGetLastError());
-  return 0;
+  // home order, no stored fp64 records, every tile with its fused boxes
+  PrepColsLaunch a;
+  a.n = (int)n;
+  a.perm = (const unsigned *)c->h2id.p;
+  a.own = a.intr = soa(c->own);
+  a.rpz = rpz;
+  a.hpz = hpz;
+  a.tla = tla;
+  a.mid = stage1_mid(0, false, 0);
+  a.nf = NfArgs{nf_epoch ? (unsigned long long *)c->nonfin.p : nullptr, nf_epoch, nullptr};
+  a.fb = FusedBoxes{(TileBox *)c->sbox_c.p, (TileBox *)c->gbox_c.p, (TileBox *)c->tbox_c.p, nullptr, 0};
+  return launch_prep_cols(c, c->stream, (unsigned)nct, a);
 }
 
-// Enqueue one complete detect on the stream (K0-K2), no host synchronisation.
-// gate (device, nullable): receives {overflow, P} for the resident sim step.
 // k_rank_rows' arguments (kept for a fused launch, k24_launch)
 struct RankLaunch {
   unsigned grid;
@@ -2609,9 +2688,287 @@ static int ov_init(Ctx *c) {
   return 0;
 }
 
-int detect_enqueue(Ctx *c, double rpz, double hpz, double tla, int flags, int64_t rb, int64_t re,
-                   unsigned long long *gate) {
-  c->fuse_done = false;  // set again only if K2 below evaluates MVP's per-pair vectors
+// ---- one detect: DetectPlan (every decision, taken by detect_decide before
+// the first stream operation), DetectRun (the device pointers the stages
+// share), one function per stage, detect_enqueue runs them in order
+struct DetectPlan {
+  double rpz, hpz, tla;
+  int flags;
+  // -- detect shape
+  int64_t n, rb, re, nrows;
+  bool empty;  // n == 0 || nrows == 0: nothing below `timed` is decided
+  bool distinct;
+  // home mode (the resident sim, bsa_sim.hip): own[] is already in spatial
+  // (home) order, h2id names the aircraft; the rows are the 512-aligned home
+  // slice [rb, re) of the columns (no re-sort, no gather)
+  bool home;
+  // halo mode (home mode of the row-sharded step, or its one-GPU probe): K0
+  // prepares the rank's own column tiles [a0, a1) (na of them), halo_mid plans
+  // / exchanges the tiles its rows can reach, K0 prepares those from the list
+  bool halo;
+  int a0, a1, na;
+  // home mode: K1b builds its fp64 records from the state arrays instead of
+  // reading 128-B records K0b wrote for EVERY column: cheaper when K0b's
+  // record writes dominate -- at 1M (0.165 -> 0.084 ms of K0) or for one rank's
+  // slice of several; with one rank below 2^18 aircraft the stored records
+  // win (each aircraft is in ~5 candidates there: K1b 27 -> 18 us at 100k).
+  // BSA_HOME_REC=0/1 overrides.
+  bool recs;
+  // KWIK: stage 1 is exact-safe only with the pair's own mean latitude in
+  // cavelat (own == intruder; DESIGN.md 3.2), and the CPA refine's geometry
+  // is the great circle's: a distinct intruder set disables the prefilter,
+  // and the refine keeps every stage-1 survivor.
+  int kwik, noprune;
+  // rows share the column order and records when own == intruder and the
+  // whole range is detected; only then can the candidate list be reused
+  bool shared;
+  int64_t roff;  // the rows' offset in the shared records
+  // -- reuse and rebuild decisions
+  bool reuse;  // candidate-list reuse
+  // stage 1 at the look-ahead midpoints (DESIGN.md 3.2b): its bound is derived
+  // for the great-circle geometry and fixed reaches, so not with KWIK nor with
+  // the reuse budgets (whose drift checks assume t = 0 points); the
+  // BSA_STAGE1_T0 environment variable selects t = 0 for A/B measurements
+  int mid;
+  // the resident step's K4' already wrote this detect's column records and
+  // boxes from the state it computed (Ctx::sim_prepped; any detect consumes or
+  // invalidates them: it rewrites the same buffers)
+  bool prepped;
+  // tile-pair list reuse: the resident step's detects of a
+  // rank's rows -- one rank: records prepared (and checked) by K4'; several
+  // ranks or the probe: the halo plan is kept with the list.  Any other detect
+  // of this context invalidates the kept list.  Halo mode: K0d sweeps the
+  // present column tiles only (tp_list: own + received, the flat halo list;
+  // BSA_TP_HALO_ALL=1 sweeps all tiles for A/B).  tvalid: the kept list is
+  // this shape's.
+  bool tp_list, tpr, tvalid;
+  // Who decides a rebuild.  HK (the resident step, Ctx::hk_*): the host, before
+  // enqueuing -- a kept list (hkeep) then launches no K0d and, several ranks,
+  // no box all-gather, no halo plan and one K0b for own + halo tiles.  Every
+  // rank takes the same decision from the same inputs (the host-side
+  // invalidations are collective events, the prediction is all-reduced with
+  // the gate).  Otherwise the device: the records' preparers raise a flag, K0d
+  // / the plan read it (round-5 behaviour).  hm: the HK detect's number.
+  bool hk, hkeep;
+  int64_t hm;
+  // K0z skipped: the last detect's K2 (k_rank_rows) zeroed this detect's
+  // counter block (double-buffered), dequeue words and per-row counts, and
+  // writes inconf / tcpamax of every row itself; the prepped tile boxes are
+  // derived from the group boxes by K0d (direct form only).  (HK keep, halo
+  // mode: K2 zeroed this detect's counters too, or K0z runs as its own launch
+  // -- not inside the merged K0b, whose halo workgroups write Counters)
+  bool nozero;
+  // stage events of this detect: only one detect in ev_every is timed (each
+  // record costs a ~5 us bubble before the next kernel, bsa_set_timing_sample)
+  bool timed;
+  hipEvent_t *ev;
+  unsigned long long nf_epoch;  // non-finite tcpa inputs: this detect's epoch (the prepped records carry K4''s)
+  double kf;                    // k_keys midpoint factor
+  // K0a spatial order.  Any permutation gives identical results (the output is
+  // re-sorted canonically), so the order is reused for up to kResortEvery
+  // calls on the same shape: aircraft move ~km between calls, tiles span ~100
+  // km (with a reusable list: 64 calls, and every re-sort rebuilds the list).
+  bool resort;
+  // -- launch shape
+  unsigned long long cap;  // candidate capacity
+  // candidate-list reuse: the list of the last build stays valid for this
+  // perm / parameters / buffers unless an aircraft overran its budget
+  // (decided on the device by K0b; ctl[0] = build this detect)
+  bool rvalid;
+  // halo overlap (Ctx::ov_mode): a kept plan of several ranks (mode 2: also the
+  // probe) sweeps the own column tiles on the stream while the exchange, the
+  // received tiles' K0b and their sweep run on xstream
+  bool ovl;
+  // K1b fused into the prefilter (ExactFuse): stored records, row buckets, no
+  // KWIK / candidate reuse, not one rank's share of a sharded step (there the
+  // sweep is short and the workgroups' end-of-sweep evaluation lengthened it
+  // more than K1b's launch cost: global1m rank 2 of 8, prefilter 46 + K1b 11
+  // -> 63 us; box100k one rank: 0.1387-0.1396 -> 0.1336-0.1367 ms per step).
+  // BSA_FUSE_EXACT=0/1 overrides (A/B).
+  bool fuse;
+  int B;  // K2 row buckets (B pairs per row per list; a fuller row retries wider, then without)
+  int nrt, nct;
+  long long ntp;
+  int ngr, ngc, nsc;
+  unsigned long long icap;  // items: 8 slices per tile pair
+  // K1a prefilter: persistent grid, PF_BLOCKS_PER_CU workgroups per CU
+  // (LDS-limited residency), at least one workgroup per dequeue shard
+  unsigned pf_grid;
+  PfKnobs kn;  // (ph, ca0, ca1: per launch)
+  int diag;    // rows sharing the column records: row i is column roff + i (its diagonal), else -1
+};
+
+struct DetectRun {
+  Ctx *c;
+  const DetectPlan &p;
+  unsigned long long *gate;  // (device, nullable): receives {overflow, P} for the resident sim step
+  SoA6 own, intr;
+  Counters *dcnt;
+  NfArgs nfa;
+  ReuseParams rz{};
+  const unsigned *build = nullptr;  // candidate reuse: its control words
+  const unsigned *perm_c = nullptr, *perm_r = nullptr;
+  const RowRec *rowrec = nullptr;
+  const PFRec *pfrow = nullptr;
+  const PFVel *pfvrow = nullptr;
+  const float4 *pfprow = nullptr;
+  const TileBox *gbox_r = nullptr, *tbox_r = nullptr;
+  HaloTpr ht{};  // tile-pair list reuse: the halo plan's share (halo_mid may raise ht.force),
+  TprArgs tp{};  // K0d's and the prefilter's
+  // HK: the prediction word of this detect's records (raised by their
+  // preparer -- K4' one step ago, or the own tiles' K0b here)
+  unsigned long long *hk_word = nullptr;
+  HeavyNext hn{};
+
+  int mark(int e) const {
+    if (p.timed) BSA_HIP(c, hipEventRecord(p.ev[e], c->stream));
+    return 0;
+  }
+  // K0z: zero the per-detect state (launched once the reuse decision is known)
+  int zero(bool keep, unsigned *rctl, int rforce, bool tiles = false) const {
+    const int64_t m = std::max<int64_t>(2 * (p.nrows + 1), 256);
+    hipLaunchKernelGGL(k_zero, dim3((unsigned)std::min<int64_t>(blocks_for(m, 256 * 4), 256)), dim3(256), 0,
+                       c->stream, (int)p.nrows, 1, keep ? 1 : 0, rctl, rforce, dcnt,
+                       (unsigned long long *)c->workq.p, (unsigned char *)c->inconf.p,
+                       (unsigned long long *)c->tcpamax.p, (unsigned *)c->rowcnt.p, (int)p.n,
+                       (const TileBox *)c->gbox_c.p, tiles ? (TileBox *)c->tbox_c.p : (TileBox *)nullptr);
+    BSA_HIP(c, hipGetLastError());
+    return 0;
+  }
+  // K0b's arguments that every launch of this detect shares
+  PrepColsLaunch prep_cols() const {
+    PrepColsLaunch a;
+    a.n = (int)p.n;
+    a.perm = perm_c;
+    a.presorted = p.home ? 1 : 0;
+    a.rec = p.recs ? 1 : 0;
+    a.own = own;
+    a.intr = intr;
+    a.distinct = p.distinct ? 1 : 0;
+    a.shared = p.shared ? 1 : 0;
+    a.rpz = p.rpz;
+    a.hpz = p.hpz;
+    a.tla = p.tla;
+    a.mid = p.mid;
+    a.rz = rz;
+    a.nf = nfa;
+    a.zs.nrows = (int)p.nrows;
+    return a;
+  }
+};
+
+// HK (see DetectPlan::hk): the host's rebuild decision for this detect
+static int decide_hk(Ctx *c, DetectPlan &p) {
+  if (p.tpr && c->hk_req && c->hk_on && !c->simp.resume_nav && c->hk_hdev) {
+    if (c->hk_cool > 0) {  // after a stale abort: device-decided for a while
+      c->hk_cool--;
+      c->hk_ok = false;
+    } else {
+      p.hk = true;
+      p.hm = c->hk_m++;
+      const int64_t hm = p.hm;
+      const int nf = (c->simp.winddim == 0 && c->sim_gs_derivable) ? 6 : 8;  // (halo_mid's field count)
+      bool build = !p.tvalid || !c->hk_ok || (c->halo_mode == 1 && nf != c->halo_fields);
+      // a build one or two detects ago: its snapshot is fresh enough (the
+      // prediction covers two steps of drift); else the prediction made from
+      // the records of detect hm - 2, published by that step's K4'
+      if (!build && !c->hk_built[(hm + 3) & 3] && !c->hk_built[(hm + 2) & 3]) {
+        unsigned long long v = 0;
+        if (hk_wait(c, hm - 2, &v)) return -1;
+        build = (v & 3ull) != 0;  // predicted, or that step aborted (its retry rebuilds anyway)
+      }
+      c->hk_built[hm & 3] = build;
+      c->hk_ok = true;
+      p.hkeep = !build;
+      (build ? c->hk_builds : c->hk_keeps)++;
+      if (detect_env().hk_trace)
+        fprintf(stderr, "[bsa hk] rank %d detect %lld: %s (tvalid %d, step %lld)\n", c->rank, (long long)hm,
+                build ? "build" : "keep", p.tvalid ? 1 : 0, (long long)c->sim_steps);
+    }
+  } else if (p.tpr) {
+    c->hk_ok = false;  // a device-decided detect: the build history is no longer the host's
+  }
+  c->hk_cur = p.hk;
+  c->hk_keep = p.hkeep;
+  c->hk_last = p.hm;
+  return 0;
+}
+
+// the launch shape of a detect with rows (and the candidate list's reuse state)
+static int decide_launch(Ctx *c, DetectPlan &p) {
+  const DetectEnv &env = detect_env();
+  const int64_t n = p.n, nrows = p.nrows;
+  p.kf = p.mid ? 0.5 * (p.tla > 0.0 ? p.tla : 0.0) / 6371000.0 : 0.0;
+  p.resort = !p.home && (!c->perm_valid || c->perm_n != n || c->perm_rb != p.rb || c->perm_re != p.re ||
+                         c->perm_shared != p.shared || c->perm_distinct != p.distinct || c->perm_f != p.kf ||
+                         (p.flags & BSA_FLAG_RESORT) || c->perm_age >= (p.reuse ? kResortEveryReuse : kResortEvery));
+  if (c->cand_cap == 0)
+    // 8 x max(128 k, 4 rows) candidates in all (at 100k rows ~12x the demand), whole shards
+    c->cand_cap = (unsigned long long)kCandShards *
+                  (((unsigned long long)8 * std::max<int64_t>(1 << 17, 4 * nrows) + kCandShards - 1) / kCandShards);
+  p.cap = c->cand_cap;
+  if (!ensure(c, c->cand, p.cap * sizeof(uint2), "candidate pairs")) return -1;
+  if (p.reuse) {
+    if (!ensure(c, c->snap_build, (size_t)n * sizeof(Snap), "reuse snapshot") ||
+        !ensure(c, c->snap_cur, (size_t)n * sizeof(Snap), "reuse state") ||
+        !ensure(c, c->reuse_use, (size_t)((n + 63) / 64) * 8, "reuse budget use") ||
+        !ensure(c, c->reuse_ctl, 16, "reuse control"))
+      return -1;
+    const double key[4] = {p.rpz, p.hpz, p.tla, (double)p.flags};
+    p.rvalid = c->reuse_valid && !p.resort && c->reuse_n == n && c->reuse_cap == p.cap &&
+               c->reuse_candp == c->cand.p && memcmp(key, c->reuse_key, sizeof key) == 0;
+    c->reuse_valid = true;  // optimistic: an overflow invalidates it (detect_finish / sim retry)
+    memcpy(c->reuse_key, key, sizeof key);
+    c->reuse_n = n;
+    c->reuse_cap = p.cap;
+    c->reuse_candp = c->cand.p;
+  }
+  p.na = p.halo ? p.a1 - p.a0 : 0;
+  p.ovl = p.halo && p.hkeep && !p.noprune && p.na > 0 && (c->ov_mode == 2 || (c->ov_mode == 1 && c->halo_mode == 1));
+  p.nrt = (int)((nrows + kTile - 1) / kTile);
+  p.nct = (int)((n + kTile - 1) / kTile);
+  p.ntp = (long long)p.nrt * p.nct;
+  p.ngr = (int)((nrows + kGroup - 1) / kGroup);
+  p.ngc = (int)((n + kGroup - 1) / kGroup);
+  p.nsc = (int)((n + kSub - 1) / kSub);
+  p.icap = (unsigned long long)p.ntp * kSlicesPerTile;
+  // pieces: ~8 items per row tile, a few hundred row tiles fill the waves;
+  // fewer rows split the items (BSA_PF_PIECES overrides)
+  p.kn = PfKnobs{1, 1, 1, 0, 0, 0};
+  if (env.pf_heavy_t0 >= 0 && env.pf_heavy_t0 <= 3) p.kn.t0 = env.pf_heavy_t0;
+  // (measured, tools/gpu_pieces.sh: 2 pieces at the 100k box, 102 -> 97 us; 4 for
+  // one rank of 8 there, 36 -> 29 us; 2 at 125k rows of 1M, 65 -> 53 us; 1
+  // from 250k rows up, where 2 cost +15 us.  Round 5, with the longest-items
+  // listing and the fused K1b: 1 piece from 64k rows up -- the 100k box
+  // 0.1204 / 0.1212 -> 0.1185 / 0.1181 ms per step, one rank of 8 at 1M
+  // 0.1130 / 0.1117 -> 0.1118 / 0.1112; tools/gpu_ab.sh, BSA_PF_PIECES=1),
+  // 2 from 16k rows: one rank of 4 at the 100k box (25k rows) 0.0942 / 0.0938
+  // -> 0.0925 / 0.0912 (tools/probe_step.py), of 8 (12.8k rows) stays at 4
+  p.kn.pieces = nrows >= (1 << 16) ? 1 : (nrows >= (1 << 14) ? 2 : 4);
+  const auto pieces_ok = [](int v) { return v == 1 || v == 2 || v == 4 || v == 8; };
+  if (pieces_ok(env.pf_pieces)) p.kn.pieces = env.pf_pieces;
+  p.kn.pnear = p.kn.pieces;
+  if (pieces_ok(env.pf_pieces_near)) p.kn.pnear = env.pf_pieces_near;
+  p.B = c->k2_bucket;
+  p.fuse = env.fuse_exact != 0 && (env.fuse_exact == 1 || !p.halo) && c->fuse_on && !c->fuse_skip && p.B > 0 &&
+           p.recs && !p.kwik && !p.reuse && !p.ovl;
+  c->fuse_skip = false;  // (one retry unfused; the next detect fuses again)
+  c->last_fused = p.fuse;
+  if (p.fuse) c->fuse_count++;
+  p.diag = p.shared ? (int)p.roff : -1;
+  p.pf_grid = (unsigned)std::max<long long>(
+      kWorkShards, std::min<long long>(p.ntp * PF_ITEMS_PER_TILE / PF_WAVES + 1, 256 * PF_BLOCKS_PER_CU));
+  return 0;
+}
+
+// Every decision of one detect and the host bookkeeping that goes with them,
+// before anything of it is enqueued (the field comments of DetectPlan say why)
+static int detect_decide(Ctx *c, double rpz, double hpz, double tla, int flags, int64_t rb, int64_t re,
+                         DetectPlan *plan) {
+  const DetectEnv &env = detect_env();
+  DetectPlan &p = *plan;
+  p = DetectPlan{};
+  c->fuse_done = false;  // set again only if K2 evaluates MVP's per-pair vectors
   const int64_t n = c->n;
   if (re <= 0) re = n;
   if (rb < 0 || rb > re || re > n)
@@ -2633,251 +2990,142 @@ int detect_enqueue(Ctx *c, double rpz, double hpz, double tla, int flags, int64_
       !ensure(c, c->rowcnt, (size_t)rowcnt_words((int)nrows) * 4, "row counts") ||
       !ensure(c, c->rowoff, (size_t)(2 * (nrows + 1)) * 4, "row offsets"))
     return -1;
-  const bool distinct = c->has_intruder;
-  // home mode (the resident sim, bsa_sim.hip): own[] is already in spatial
-  // (home) order, h2id names the aircraft; the rows are the 512-aligned home
-  // slice [rb, re) of the columns (no re-sort, no gather)
-  const bool home = c->det_home;
-  c->last_home = home;
-  // halo mode (home mode of the row-sharded step, or its one-GPU probe): K0
-  // prepares the rank's own column tiles [a0, a1), halo_mid plans / exchanges
-  // the tiles its rows can reach, K0 prepares those from the list
-  const bool halo = home && c->halo_mode != 0;
-  const int a0 = (int)(rb / kTile), a1 = (int)((re + kTile - 1) / kTile);
-  // home mode: K1b builds its fp64 records from the state arrays instead of
-  // reading 128-B records K0b wrote for EVERY column: cheaper when K0b's
-  // record writes dominate -- at 1M (0.165 -> 0.084 ms of K0) or for one rank's
-  // slice of several; with one rank below 2^18 aircraft the stored records
-  // win (each aircraft is in ~5 candidates there: K1b 27 -> 18 us at 100k).
-  // BSA_HOME_REC=0/1 overrides.
-  const bool recs = !home || home_records(c, nrows);
-  if (home && (distinct || (rb % kTile != 0 && re > rb) || (flags & BSA_FLAG_KWIK)))  // (a rank without rows: rb = n)
+  p.rpz = rpz;
+  p.hpz = hpz;
+  p.tla = tla;
+  p.flags = flags;
+  p.n = n;
+  p.rb = rb;
+  p.re = re;
+  p.nrows = nrows;
+  p.distinct = c->has_intruder;
+  p.home = c->det_home;
+  c->last_home = p.home;
+  p.halo = p.home && c->halo_mode != 0;
+  p.a0 = (int)(rb / kTile);
+  p.a1 = (int)((re + kTile - 1) / kTile);
+  p.recs = !p.home || home_records(c, nrows);
+  if (p.home && (p.distinct || (rb % kTile != 0 && re > rb) || (flags & BSA_FLAG_KWIK)))  // (a rank without rows: rb = n)
     return fail(c, "home-order detect needs own == intruder, a %d-aligned row slice, no KWIK", kTile);
-  const int kwik = (flags & BSA_FLAG_KWIK) ? 1 : 0;
-  // KWIK: stage 1 is exact-safe only with the pair's own mean latitude in
-  // cavelat (own == intruder; DESIGN.md 3.2), and the CPA refine's geometry
-  // is the great circle's: a distinct intruder set disables the prefilter,
-  // and the refine keeps every stage-1 survivor.
-  const int noprune = ((flags & BSA_FLAG_NOPRUNE) || (kwik && distinct)) ? 1 : 0;
-  // rows share the column order and records when own == intruder and the
-  // whole range is detected; only then can the candidate list be reused
-  const bool shared = home || (!distinct && rb == 0 && re == n);
-  const int64_t roff = home ? rb : 0;  // the rows' offset in the shared records
-  const bool reuse = c->reuse_on && shared && rb == 0 && re == n && !noprune && !kwik && n > 0 && !halo;
-  if (!reuse) c->reuse_valid = false;
-  // stage 1 at the look-ahead midpoints (DESIGN.md 3.2b): its bound is derived
-  // for the great-circle geometry and fixed reaches, so not with KWIK nor with
-  // the reuse budgets (whose drift checks assume t = 0 points); the
-  // BSA_STAGE1_T0 environment variable selects t = 0 for A/B measurements
-  const int mid = stage1_mid(flags, reuse, kwik);
-  // the resident step's K4' already wrote this detect's column records and
-  // boxes from the state it computed (Ctx::sim_prepped; any detect consumes or
-  // invalidates them: it rewrites the same buffers)
-  const bool prepped = c->sim_prepped && home && !halo && !reuse && rb == 0 && re == n && flags == 0 &&
-                       c->sim_prep_key[0] == rpz && c->sim_prep_key[1] == hpz && c->sim_prep_key[2] == tla &&
-                       c->sim_prep_key[3] == (double)mid && c->sim_prep_n == n;
+  p.kwik = (flags & BSA_FLAG_KWIK) ? 1 : 0;
+  p.noprune = ((flags & BSA_FLAG_NOPRUNE) || (p.kwik && p.distinct)) ? 1 : 0;
+  p.shared = p.home || (!p.distinct && rb == 0 && re == n);
+  p.roff = p.home ? rb : 0;
+  p.reuse = c->reuse_on && p.shared && rb == 0 && re == n && !p.noprune && !p.kwik && n > 0 && !p.halo;
+  if (!p.reuse) c->reuse_valid = false;
+  p.mid = stage1_mid(flags, p.reuse, p.kwik);
+  p.prepped = c->sim_prepped && p.home && !p.halo && !p.reuse && rb == 0 && re == n && flags == 0 &&
+              c->sim_prep_key[0] == rpz && c->sim_prep_key[1] == hpz && c->sim_prep_key[2] == tla &&
+              c->sim_prep_key[3] == (double)p.mid && c->sim_prep_n == n;
   c->sim_prepped = false;
-  // non-finite tcpa inputs: this detect's epoch (the prepped records carry K4''s)
   if (!nonfin_word(c)) return -1;
-  NfArgs nfa{(unsigned long long *)c->nonfin.p,
-             prepped ? c->nf_prep_epoch : (c->nf_force_epoch ? c->nf_force_epoch : ++c->nf_counter), nullptr};
-  // K0z skipped: the last detect's K2 (k_rank_rows) zeroed this detect's
-  // counter block (double-buffered), dequeue words and per-row counts, and
-  // writes inconf / tcpamax of every row itself; the prepped tile boxes are
-  // derived from the group boxes by K0d (direct form only)
-  static const bool tp_super = getenv("BSA_TP_SUPER") && atoi(getenv("BSA_TP_SUPER")) == 1;  // (A/B)
-  static const bool zero_env = getenv("BSA_K0Z") && atoi(getenv("BSA_K0Z")) == 1;           // (A/B)
-  // ---- tile-pair list reuse: the resident step's detects of
-  // a rank's rows -- one rank: records prepared (and checked) by K4'; several
-  // ranks or the probe: the halo plan is kept with the list.  Any other detect
-  // of this context invalidates the kept list.  Halo mode: K0d sweeps the
-  // present column tiles only (own + received, the flat halo list;
-  // BSA_TP_HALO_ALL=1 sweeps all tiles for A/B).
-  static const bool tp_all = getenv("BSA_TP_HALO_ALL") && atoi(getenv("BSA_TP_HALO_ALL")) == 1;
-  const bool tp_list = halo && !tp_all && !tp_super;
-  static const bool tpr_env = !(getenv("BSA_TPR") && atoi(getenv("BSA_TPR")) == 0);
-  const bool tpr = tpr_env && c->tpr_on && home && !reuse && flags == 0 && !tp_super &&
-                   ((!halo && prepped && (n + kTile - 1) / kTile <= kTPDirectMax) || tp_list);
-  const double tkey[6] = {rpz, hpz, tla, (double)mid, (double)rb, (double)re};
-  const bool tvalid = tpr && c->tpr_valid && c->tpr_n == n && memcmp(tkey, c->tpr_key, sizeof tkey) == 0;
-  // Who decides a rebuild.  HK (the resident step, Ctx::hk_*): the host, before
-  // enqueuing -- a kept list then launches no K0d and, several ranks, no box
-  // all-gather, no halo plan and one K0b for own + halo tiles.  Every rank
-  // takes the same decision from the same inputs (the host-side invalidations
-  // are collective events, the prediction is all-reduced with the gate).
-  // Otherwise the device: the records' preparers raise a flag, K0d / the plan
-  // read it (round-5 behaviour).
-  bool hk = false, hkeep = false;
-  int64_t hm = 0;
-  if (tpr && c->hk_req && c->hk_on && !c->simp.resume_nav && c->hk_hdev) {
-    if (c->hk_cool > 0) {  // after a stale abort: device-decided for a while
-      c->hk_cool--;
-      c->hk_ok = false;
-    } else {
-      hk = true;
-      hm = c->hk_m++;
-      const int nf = (c->simp.winddim == 0 && c->sim_gs_derivable) ? 6 : 8;  // (halo_mid's field count)
-      bool build = !tvalid || !c->hk_ok || (c->halo_mode == 1 && nf != c->halo_fields);
-      // a build one or two detects ago: its snapshot is fresh enough (the
-      // prediction covers two steps of drift); else the prediction made from
-      // the records of detect hm - 2, published by that step's K4'
-      if (!build && !c->hk_built[(hm + 3) & 3] && !c->hk_built[(hm + 2) & 3]) {
-        unsigned long long v = 0;
-        if (hk_wait(c, hm - 2, &v)) return -1;
-        build = (v & 3ull) != 0;  // predicted, or that step aborted (its retry rebuilds anyway)
-      }
-      c->hk_built[hm & 3] = build;
-      c->hk_ok = true;
-      hkeep = !build;
-      (build ? c->hk_builds : c->hk_keeps)++;
-      static const bool trace = getenv("BSA_HK_TRACE") && atoi(getenv("BSA_HK_TRACE")) == 1;  // (diagnostics)
-      if (trace)
-        fprintf(stderr, "[bsa hk] rank %d detect %lld: %s (tvalid %d, step %lld)\n", c->rank, (long long)hm,
-                build ? "build" : "keep", tvalid ? 1 : 0, (long long)c->sim_steps);
-    }
-  } else if (tpr) {
-    c->hk_ok = false;  // a device-decided detect: the build history is no longer the host's
-  }
-  c->hk_cur = hk;
-  c->hk_keep = hkeep;
-  c->hk_last = hm;
-  if (tpr) {  // (every rank, also one without rows: the kept state stays collective)
+  p.nf_epoch = p.prepped ? c->nf_prep_epoch : (c->nf_force_epoch ? c->nf_force_epoch : ++c->nf_counter);
+  p.tp_list = p.halo && !env.tp_halo_all && !env.tp_super;
+  p.tpr = env.tpr && c->tpr_on && p.home && !p.reuse && flags == 0 && !env.tp_super &&
+          ((!p.halo && p.prepped && (n + kTile - 1) / kTile <= kTPDirectMax) || p.tp_list);
+  const double tkey[6] = {rpz, hpz, tla, (double)p.mid, (double)rb, (double)re};
+  p.tvalid = p.tpr && c->tpr_valid && c->tpr_n == n && memcmp(tkey, c->tpr_key, sizeof tkey) == 0;
+  if (decide_hk(c, p)) return -1;
+  if (p.tpr) {  // (every rank, also one without rows: the kept state stays collective)
     c->tpr_valid = true;  // (an aborted step or any state change clears it)
     memcpy(c->tpr_key, tkey, sizeof tkey);
     c->tpr_n = n;
   } else {
     c->tpr_valid = false;
   }
-  // (HK keep, halo mode: K2 zeroed this detect's counters too, or K0z runs as
-  // its own launch -- not inside the merged K0b, whose halo workgroups write Counters)
-  const bool nozero = ((prepped && (n + kTile - 1) / kTile <= kTPDirectMax) || (hkeep && halo)) && !zero_env &&
-                      !tp_super && c->k2_bucket > 0 && c->zeroed_rows == nrows;
+  p.nozero = ((p.prepped && (n + kTile - 1) / kTile <= kTPDirectMax) || (p.hkeep && p.halo)) && !env.k0z &&
+             !env.tp_super && c->k2_bucket > 0 && c->zeroed_rows == nrows;
   c->zeroed_rows = -1;
-  if (nozero) {
+  if (p.nozero) {
     std::swap(c->counters, c->counters2);
     std::swap(c->workq, c->workq2);
   }
-  // stage events of this detect: only one detect in ev_every is timed (each
-  // record costs a ~5 us bubble before the next kernel, bsa_set_timing_sample)
-  hipEvent_t *ev = nullptr;
-  const bool timed = c->ev_every > 0 && (c->ev_count++ % c->ev_every) == 0;
-  if (timed && next_events(c, &ev)) return -1;
-  auto mark = [&](int e) -> int {
-    if (timed) BSA_HIP(c, hipEventRecord(ev[e], c->stream));
-    return 0;
-  };
-  if (mark(0)) return -1;
-  Counters *dcnt = (Counters *)c->counters.p;
-  // K0z: zero the per-detect state (launched once the reuse decision is known)
-  auto zero = [&](bool keep, unsigned *rctl, int rforce, bool tiles = false) -> int {
-    const int64_t m = std::max<int64_t>(2 * (nrows + 1), 256);
-    hipLaunchKernelGGL(k_zero, dim3((unsigned)std::min<int64_t>(blocks_for(m, 256 * 4), 256)), dim3(256), 0,
-                       c->stream, (int)nrows, 1, keep ? 1 : 0, rctl, rforce, dcnt,
-                       (unsigned long long *)c->workq.p, (unsigned char *)c->inconf.p,
-                       (unsigned long long *)c->tcpamax.p, (unsigned *)c->rowcnt.p, (int)n,
-                       (const TileBox *)c->gbox_c.p, tiles ? (TileBox *)c->tbox_c.p : (TileBox *)nullptr);
-    BSA_HIP(c, hipGetLastError());
-    return 0;
-  };
-  if (n == 0 || nrows == 0) {
-    if (zero(false, nullptr, 0)) return -1;
-    if (halo) {  // a rank without rows still takes part in the exchange (HK keep: no box all-gather)
-      HaloPre hp;
-      HaloUnpack hu;
-      if (halo_pre(c, rb, re, &hp)) return -1;
-      if (!hkeep) {
-        for (int r = 0; r < 3; ++r)
-          if (hp.zn[r]) BSA_HIP(c, hipMemsetAsync(hp.z[r], 0, (size_t)hp.zn[r] * 4, c->stream));
-        // (its plan-reuse flag stays clear: it holds no records that could drift)
-        if (unsigned *f = halo_flag_word(c)) BSA_HIP(c, hipMemsetAsync(f, 0, 4, c->stream));
-      }
-      if (halo_mid(c, rb, re, &hu, nullptr, hkeep)) return -1;
-    }
-    if (gate) BSA_HIP(c, hipMemsetAsync(gate, 0, kGateWords * 8, c->stream));
-    for (int e = 1; e < 5; ++e)
-      if (mark(e)) return -1;
-    c->ev_valid = c->ev_valid || timed;
-    c->empty_detect = true;
-    return 0;
-  }
+  p.timed = c->ev_every > 0 && (c->ev_count++ % c->ev_every) == 0;
+  if (p.timed && next_events(c, &p.ev)) return -1;
+  p.empty = n == 0 || nrows == 0;
+  if (p.empty) return 0;
   c->empty_detect = false;
-  DevBuf *I = distinct ? c->intr : c->own;
-  SoA6 own{(const double *)c->own[0].p, (const double *)c->own[1].p, (const double *)c->own[2].p,
-           (const double *)c->own[3].p, (const double *)c->own[4].p, (const double *)c->own[5].p};
-  SoA6 intr{(const double *)I[0].p, (const double *)I[1].p, (const double *)I[2].p,
-            (const double *)I[3].p, (const double *)I[4].p, (const double *)I[5].p};
+  return decide_launch(c, p);
+}
 
-  // ---- K0a spatial order.  Any permutation gives identical results (the
-  // output is re-sorted canonically), so the order is reused for up to
-  // kResortEvery calls on the same shape: aircraft move ~km between calls,
-  // tiles span ~100 km (with a reusable list: 64 calls, and every re-sort
-  // rebuilds the list).
-  const double kf = mid ? 0.5 * (tla > 0.0 ? tla : 0.0) / 6371000.0 : 0.0;  // k_keys midpoint factor
-  const bool resort = !home && (!c->perm_valid || c->perm_n != n || c->perm_rb != rb || c->perm_re != re ||
-                      c->perm_shared != shared || c->perm_distinct != distinct || c->perm_f != kf ||
-                      (flags & BSA_FLAG_RESORT) || c->perm_age >= (reuse ? kResortEveryReuse : kResortEvery));
-  // ---- candidate-list reuse: the list of the last build stays valid for
-  // this perm / parameters / buffers unless an aircraft overran its budget
-  // (decided on the device by K0b; ctl[0] = build this detect)
-  if (c->cand_cap == 0)
-    // 8 x max(128 k, 4 rows) candidates in all (at 100k rows ~12x the demand), whole shards
-    c->cand_cap = (unsigned long long)kCandShards *
-                  (((unsigned long long)8 * std::max<int64_t>(1 << 17, 4 * nrows) + kCandShards - 1) / kCandShards);
-  const unsigned long long cap = c->cand_cap;
-  if (!ensure(c, c->cand, cap * sizeof(uint2), "candidate pairs")) return -1;
-  ReuseParams rz{};
-  bool rvalid = false;
-  if (reuse) {
-    if (!ensure(c, c->snap_build, (size_t)n * sizeof(Snap), "reuse snapshot") ||
-        !ensure(c, c->snap_cur, (size_t)n * sizeof(Snap), "reuse state") ||
-        !ensure(c, c->reuse_use, (size_t)((n + 63) / 64) * 8, "reuse budget use") ||
-        !ensure(c, c->reuse_ctl, 16, "reuse control"))
-      return -1;
-    const double key[4] = {rpz, hpz, tla, (double)flags};
-    rvalid = c->reuse_valid && !resort && c->reuse_n == n && c->reuse_cap == cap &&
-             c->reuse_candp == c->cand.p && memcmp(key, c->reuse_key, sizeof key) == 0;
-    rz.build = (const Snap *)c->snap_build.p;
-    rz.cur = (Snap *)c->snap_cur.p;
-    rz.ctl = (unsigned *)c->reuse_ctl.p;
-    rz.use = (float *)c->reuse_use.p;
-    rz.sh = c->reuse_sh;
-    rz.sh_chord = (float)(c->reuse_sh / 6.3e6) * 1.000001f;
-    rz.sv_default = c->reuse_sv;
-    rz.sv_min = 1.0;
-    rz.sv_max = 4.0 * c->reuse_sv;
-    rz.ktarget = 16.0;
-    rz.valid = rvalid ? 1 : 0;
-    c->reuse_valid = true;  // optimistic: an overflow invalidates it (detect_finish / sim retry)
-    memcpy(c->reuse_key, key, sizeof key);
-    c->reuse_n = n;
-    c->reuse_cap = cap;
-    c->reuse_candp = c->cand.p;
+// a detect without aircraft or rows: zeroed outputs; a rank without rows still
+// takes part in the exchange (HK keep: no box all-gather)
+static int detect_empty(const DetectRun &R) {
+  Ctx *c = R.c;
+  const DetectPlan &p = R.p;
+  if (R.zero(false, nullptr, 0)) return -1;
+  if (p.halo) {
+    HaloPre hp;
+    HaloUnpack hu;
+    if (halo_pre(c, p.rb, p.re, &hp)) return -1;
+    if (!p.hkeep) {
+      for (int r = 0; r < 3; ++r)
+        if (hp.zn[r]) BSA_HIP(c, hipMemsetAsync(hp.z[r], 0, (size_t)hp.zn[r] * 4, c->stream));
+      // (its plan-reuse flag stays clear: it holds no records that could drift)
+      if (unsigned *f = halo_flag_word(c)) BSA_HIP(c, hipMemsetAsync(f, 0, 4, c->stream));
+    }
+    if (halo_mid(c, p.rb, p.re, &hu, nullptr, p.hkeep)) return -1;
   }
-  const unsigned *build = reuse ? (const unsigned *)c->reuse_ctl.p : nullptr;
-  // K0z runs inside K0b (k_prep_cols) unless the list is reused (its build flag is set here)
-  if (reuse && zero(true, (unsigned *)c->reuse_ctl.p, rvalid ? 0 : 1)) return -1;
-  if (resort) {
+  if (R.gate) BSA_HIP(c, hipMemsetAsync(R.gate, 0, kGateWords * 8, c->stream));
+  for (int e = 1; e < 5; ++e)
+    if (R.mark(e)) return -1;
+  c->ev_valid = c->ev_valid || p.timed;
+  c->empty_detect = true;
+  return 0;
+}
+
+// ---- K0a spatial order (DetectPlan::resort), after the reusable candidate
+// list's K0z
+static int detect_order(DetectRun &R) {
+  Ctx *c = R.c;
+  const DetectPlan &p = R.p;
+  if (p.reuse) {
+    R.rz.build = (const Snap *)c->snap_build.p;
+    R.rz.cur = (Snap *)c->snap_cur.p;
+    R.rz.ctl = (unsigned *)c->reuse_ctl.p;
+    R.rz.use = (float *)c->reuse_use.p;
+    R.rz.sh = c->reuse_sh;
+    R.rz.sh_chord = (float)(c->reuse_sh / 6.3e6) * 1.000001f;
+    R.rz.sv_default = c->reuse_sv;
+    R.rz.sv_min = 1.0;
+    R.rz.sv_max = 4.0 * c->reuse_sv;
+    R.rz.ktarget = 16.0;
+    R.rz.valid = p.rvalid ? 1 : 0;
+    R.build = (const unsigned *)c->reuse_ctl.p;
+    // K0z runs inside K0b (k_prep_cols) unless the list is reused (its build flag is set here)
+    if (R.zero(true, (unsigned *)c->reuse_ctl.p, p.rvalid ? 0 : 1)) return -1;
+  }
+  if (p.resort) {
     // columns: intruder position, own velocity; rows: own position, intruder velocity
-    if (spatial_order(c, (int)n, 0, intr.lat, intr.lon, own.trk, own.gs, kf, c->key_c, c->idx_c, c->key_c2,
-                      c->perm_c))
+    if (spatial_order(c, (int)p.n, 0, R.intr.lat, R.intr.lon, R.own.trk, R.own.gs, p.kf, c->key_c, c->idx_c,
+                      c->key_c2, c->perm_c))
       return -1;
-    if (!shared && spatial_order(c, (int)nrows, (int)rb, own.lat, own.lon, intr.trk, intr.gs, kf, c->key_r,
-                                 c->idx_r, c->key_r2, c->perm_r))
+    if (!p.shared && spatial_order(c, (int)p.nrows, (int)p.rb, R.own.lat, R.own.lon, R.intr.trk, R.intr.gs, p.kf,
+                                   c->key_r, c->idx_r, c->key_r2, c->perm_r))
       return -1;
-    c->perm_f = kf;
+    c->perm_f = p.kf;
     c->perm_valid = true;
-    c->perm_n = n;
-    c->perm_rb = rb;
-    c->perm_re = re;
-    c->perm_shared = shared;
-    c->perm_distinct = distinct;
+    c->perm_n = p.n;
+    c->perm_rb = p.rb;
+    c->perm_re = p.re;
+    c->perm_shared = p.shared;
+    c->perm_distinct = p.distinct;
     c->perm_age = 0;
   }
-  if (!home) c->perm_age++;
-  const unsigned *perm_c = (const unsigned *)(home ? c->h2id.p : c->perm_c.p);
-  const unsigned *perm_r = home ? nullptr : (const unsigned *)(shared ? c->perm_c.p : c->perm_r.p);
+  if (!p.home) c->perm_age++;
+  R.perm_c = (const unsigned *)(p.home ? c->h2id.p : c->perm_c.p);
+  R.perm_r = p.home ? nullptr : (const unsigned *)(p.shared ? c->perm_c.p : c->perm_r.p);
+  return 0;
+}
 
-  // ---- buffers sized by the candidate capacity (every pair list <= candidates)
+// the buffers of K0b / K0c and those sized by the candidate capacity (every
+// pair list <= candidates); shared: the column records serve as row records
+// too (RowRec and ColRec agree field for field up to `vs`)
+static int detect_buffers(DetectRun &R) {
+  Ctx *c = R.c;
+  const DetectPlan &p = R.p;
+  const unsigned long long cap = p.cap;
+  const int64_t n = p.n, nrows = p.nrows, roff = p.roff;
   if (!ensure(c, c->cflag, cap, "candidate flags") ||
       !ensure(c, c->cpay, cap * kPayStride * 8, "candidate records") ||
       !ensure(c, c->ckey2, cap * 8, "conflict keys") || !ensure(c, c->cval2, cap * 4, "conflict slots") ||
@@ -2885,212 +3133,254 @@ int detect_enqueue(Ctx *c, double rpz, double hpz, double tla, int flags, int64_
       !ensure(c, c->out_cj, cap * 4, "cj") || !ensure(c, c->out_pay, cap * 5 * 8, "conflict outputs") ||
       !ensure(c, c->out_li, cap * 4, "li") || !ensure(c, c->out_lj, cap * 4, "lj"))
     return -1;
-  // ---- K0b records in sorted order (shared: the column records serve as
-  // row records too; RowRec and ColRec agree field for field up to `vs`)
   if (!ensure(c, c->colrec, n * sizeof(ColRec), "column records") ||
       !ensure(c, c->pfcol, n * sizeof(PFRec), "prefilter columns") ||
       !ensure(c, c->pfvcol, n * sizeof(PFVel), "prefilter column velocities") ||
       !ensure(c, c->pfpcol, n * sizeof(float4), "prefilter column positions"))
     return -1;
-  if (!shared && (!ensure(c, c->rowrec, nrows * sizeof(RowRec), "row records") ||
-                  !ensure(c, c->pfrow, nrows * sizeof(PFRec), "prefilter rows") ||
-                  !ensure(c, c->pfvrow, nrows * sizeof(PFVel), "prefilter row velocities") ||
-                  !ensure(c, c->pfprow, nrows * sizeof(float4), "prefilter row positions")))
+  if (!p.shared && (!ensure(c, c->rowrec, nrows * sizeof(RowRec), "row records") ||
+                    !ensure(c, c->pfrow, nrows * sizeof(PFRec), "prefilter rows") ||
+                    !ensure(c, c->pfvrow, nrows * sizeof(PFVel), "prefilter row velocities") ||
+                    !ensure(c, c->pfprow, nrows * sizeof(float4), "prefilter row positions") ||
+                    !ensure(c, c->rownf, (size_t)nrows, "row non-finite flags")))
     return -1;
-  const RowRec *rowrec = shared ? (const RowRec *)c->colrec.p + roff : (const RowRec *)c->rowrec.p;
-  const PFRec *pfrow = shared ? (const PFRec *)c->pfcol.p + roff : (const PFRec *)c->pfrow.p;
-  const PFVel *pfvrow = shared ? (const PFVel *)c->pfvcol.p + roff : (const PFVel *)c->pfvrow.p;
-  const float4 *pfprow = shared ? (const float4 *)c->pfpcol.p + roff : (const float4 *)c->pfprow.p;
-  if (!shared) {  // (rows that are columns: the column word covers them)
-    if (!ensure(c, c->rownf, (size_t)nrows, "row non-finite flags")) return -1;
-    nfa.rowbad = (const uint8_t *)c->rownf.p;
-    hipLaunchKernelGGL(k_prep_rows, dim3(blocks_for(nrows, 256)), dim3(256), 0, c->stream, (int)nrows,
-                       perm_r, own, intr, rpz, hpz, tla, (RowRec *)c->rowrec.p, (PFRec *)c->pfrow.p,
-                       (PFVel *)c->pfvrow.p, (float4 *)c->pfprow.p, mid, (uint8_t *)c->rownf.p, (int)rb);
+  R.rowrec = p.shared ? (const RowRec *)c->colrec.p + roff : (const RowRec *)c->rowrec.p;
+  R.pfrow = p.shared ? (const PFRec *)c->pfcol.p + roff : (const PFRec *)c->pfrow.p;
+  R.pfvrow = p.shared ? (const PFVel *)c->pfvcol.p + roff : (const PFVel *)c->pfvrow.p;
+  R.pfprow = p.shared ? (const float4 *)c->pfpcol.p + roff : (const float4 *)c->pfprow.p;
+  if (!ensure(c, c->tbox_c, p.nct * sizeof(TileBox), "column tile boxes") ||
+      !ensure(c, c->gbox_c, p.ngc * sizeof(TileBox), "column group boxes") ||
+      !ensure(c, c->sbox_c, p.nsc * sizeof(TileBox), "column sub-group boxes") ||
+      !ensure(c, c->tilepairs, (size_t)p.ntp * kSlicesPerTile * sizeof(uint2), "prefilter items"))
+    return -1;
+  return 0;
+}
+
+// halo mode, after K0b of the own tiles (or none: HK keep): the plan / the
+// exchange (halo_mid), then K0b of the received tiles
+static int detect_halo_records(DetectRun &R, const PrepColsLaunch &own_tiles) {
+  Ctx *c = R.c;
+  const DetectPlan &p = R.p;
+  HaloUnpack hu{};
+  // (halo overlap: K0z before the pack -- xstream's K0b writes Counters)
+  if (p.ovl && !p.nozero && R.zero(false, nullptr, 0)) return -1;
+  if (halo_mid(c, p.rb, p.re, &hu, p.tpr ? &R.ht : nullptr, p.hkeep, p.ovl && c->halo_mode == 1 ? c->xstream : nullptr))
+    return -1;
+  hu.count = halo_list_count(c);
+  // the received tiles: unpacked (exchange), records and boxes (no zeroing,
+  // no budget checks, no boxes into the sent block)
+  PrepColsLaunch recv = own_tiles;
+  recv.tile_base = 0;
+  recv.tile_list = (const int *)c->h_hl.p;
+  recv.hu = hu;
+  recv.hcnt = R.dcnt;
+  recv.tck = TprCheck{};
+  recv.nown = 0;
+  if (p.ovl) {
+    // the own tiles (budget checks included) on the stream; the received
+    // ones on xstream once the exchange is in (the probe: no exchange, after
+    // K0z), which then waits for the own tiles (its sweep's rows)
+    if (c->halo_mode != 1) {
+      BSA_HIP(c, hipEventRecord(c->ov_ev[0], c->stream));
+      BSA_HIP(c, hipStreamWaitEvent(c->xstream, c->ov_ev[0], 0));
+    }
+    if (launch_prep_cols(c, c->stream, (unsigned)p.na, own_tiles)) return -1;
+    BSA_HIP(c, hipEventRecord(c->ov_ev[1], c->stream));
+    if (c->halo_hl > 0 && launch_prep_cols(c, c->xstream, (unsigned)c->halo_hl, recv)) return -1;
+    BSA_HIP(c, hipStreamWaitEvent(c->xstream, c->ov_ev[1], 0));
+  } else if (p.hkeep) {
+    // HK keep: no plan, so the own tiles wait for nothing before the
+    // exchange -- ONE K0b for them and the received tiles (workgroups [0, na)
+    // the own tiles with their budget checks, the rest the halo list's
+    // slots); K0z is K2's (double-buffered counters) or its own launch,
+    // never inside it (its halo workgroups write Counters)
+    if (!p.nozero && R.zero(false, nullptr, 0)) return -1;
+    PrepColsLaunch both = recv;
+    both.tile_base = p.a0;
+    both.tck = own_tiles.tck;
+    both.nown = p.na;
+    if (launch_prep_cols(c, c->stream, (unsigned)(p.na + c->halo_hl), both)) return -1;
+  } else if (c->halo_hl > 0) {
+    if (launch_prep_cols(c, c->stream, (unsigned)c->halo_hl, recv)) return -1;
+  }
+  return 0;
+}
+
+// ---- K0b records in sorted order, K0c for the columns fused into it unless
+// the candidate list is reused (then the boxes wait for the build decision
+// every K0b lane contributes to); halo mode: the exchange between the own and
+// the received tiles' K0b
+static int detect_records(DetectRun &R) {
+  Ctx *c = R.c;
+  const DetectPlan &p = R.p;
+  if (detect_buffers(R)) return -1;
+  if (!p.shared) {  // (rows that are columns: the column word covers them)
+    R.nfa.rowbad = (const uint8_t *)c->rownf.p;
+    hipLaunchKernelGGL(k_prep_rows, dim3(blocks_for(p.nrows, 256)), dim3(256), 0, c->stream, (int)p.nrows, R.perm_r,
+                       R.own, R.intr, p.rpz, p.hpz, p.tla, (RowRec *)c->rowrec.p, (PFRec *)c->pfrow.p,
+                       (PFVel *)c->pfvrow.p, (float4 *)c->pfprow.p, p.mid, (uint8_t *)c->rownf.p, (int)p.rb);
     BSA_HIP(c, hipGetLastError());
   }
-  // K0c for the columns is fused into K0b unless the candidate list is reused
-  // (then the boxes wait for the build decision every K0b lane contributes to)
-  const int nrt = (int)((nrows + kTile - 1) / kTile), nct = (int)((n + kTile - 1) / kTile);
-  const long long ntp = (long long)nrt * nct;
-  const int ngr = (int)((nrows + kGroup - 1) / kGroup), ngc = (int)((n + kGroup - 1) / kGroup);
-  const int nsc = (int)((n + kSub - 1) / kSub);
-  if (!ensure(c, c->tbox_c, nct * sizeof(TileBox), "column tile boxes") ||
-      !ensure(c, c->gbox_c, ngc * sizeof(TileBox), "column group boxes") ||
-      !ensure(c, c->sbox_c, nsc * sizeof(TileBox), "column sub-group boxes") ||
-      !ensure(c, c->tilepairs, (size_t)ntp * kSlicesPerTile * sizeof(uint2), "prefilter items"))
-    return -1;
-  // tile-pair list reuse (decided above): the list's buffers and budgets
-  TprArgs tp{};
-  HaloTpr ht{};
-  if (tpr) {
-    if (!ensure(c, c->tpr_snap, (size_t)n * sizeof(PFRec), "tile-pair list snapshot")) return -1;
+  // tile-pair list reuse (DetectPlan::tpr): the list's buffers and budgets
+  if (p.tpr) {
+    if (!ensure(c, c->tpr_snap, (size_t)p.n * sizeof(PFRec), "tile-pair list snapshot")) return -1;
     const bool fresh = !c->tpr_ctl.p;
     if (!ensure(c, c->tpr_ctl, 64, "tile-pair list control")) return -1;
     if (fresh) BSA_HIP(c, hipMemsetAsync(c->tpr_ctl.p, 0, 64, c->stream));
-    static const double sh_env = getenv("BSA_TPR_SH") ? atof(getenv("BSA_TPR_SH")) : 0.0;  // (A/B) [m]
+    const double sh_env = detect_env().tpr_sh;
     if (sh_env > 0.0) {
       c->tpr_dx = (float)(sh_env / 6.3e6);
       c->tpr_ds = (float)(sh_env / 6.3e6 / 20);
     }
-    const bool force = hk ? !hkeep : !tvalid;  // (HK: the host's decision; a kept list launches no plan)
-    ht = HaloTpr{halo ? 1 : 0, force ? 1 : 0, c->tpr_dx, c->tpr_ds, c->tpr_dv, (unsigned long long *)c->tpr_ctl.p,
-                 nullptr};
+    const bool force = p.hk ? !p.hkeep : !p.tvalid;  // (HK: the host's decision; a kept list launches no plan)
+    R.ht = HaloTpr{p.halo ? 1 : 0, force ? 1 : 0, c->tpr_dx, c->tpr_ds, c->tpr_dv,
+                   (unsigned long long *)c->tpr_ctl.p, nullptr};
   }
-  // HK: the prediction word of this detect's records (raised by their
-  // preparer -- K4' one step ago, or the own tiles' K0b here)
-  unsigned long long *hk_word = hk ? (unsigned long long *)c->tpr_ctl.p + 6 + (hm & 1) : nullptr;
-  FusedBoxes fb{nullptr, nullptr, nullptr, nullptr, 0};
-  ZeroArgs zs{(int)nrows, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, {}, {}};
+  R.hk_word = p.hk ? (unsigned long long *)c->tpr_ctl.p + 6 + (p.hm & 1) : nullptr;
   // halo mode: the plan's buffers are zeroed and the own tile boxes written
   // into the exchanged block by this K0b (no memset / copy launches)
   HaloPre hp{};
-  if (halo && halo_pre(c, rb, re, &hp, tpr ? &ht : nullptr)) return -1;
+  if (p.halo && halo_pre(c, p.rb, p.re, &hp, p.tpr ? &R.ht : nullptr)) return -1;
+  PrepColsLaunch a = R.prep_cols();
+  const ZeroArgs no_zero = a.zs;
   // plan reuse: the own K0b checks its records against the last build's and
   // raises this rank's flag (not at a forced rebuild: it rebuilds anyway)
-  TprCheck tck{};
-  if (tpr && halo) {
-    ht.myflag = halo_flag_word(c);
-    if (!ht.force)
-      tck = TprCheck{(const PFRec *)c->tpr_snap.p, ht.myflag, c->tpr_dx, c->tpr_ds, c->tpr_dv, hk_word, c->hk_f};
+  if (p.tpr && p.halo) {
+    R.ht.myflag = halo_flag_word(c);
+    if (!R.ht.force)
+      a.tck = TprCheck{(const PFRec *)c->tpr_snap.p, R.ht.myflag, c->tpr_dx, c->tpr_ds, c->tpr_dv, R.hk_word, c->hk_f};
   }
-  if (!reuse) {
-    fb = FusedBoxes{(TileBox *)c->sbox_c.p, (TileBox *)c->gbox_c.p, (TileBox *)c->tbox_c.p, hp.blk, hp.blk_base};
-    zs = ZeroArgs{(int)nrows, 1, 0, dcnt, (unsigned long long *)c->workq.p, (unsigned char *)c->inconf.p,
-                  (unsigned long long *)c->tcpamax.p, (unsigned *)c->rowcnt.p, {hp.z[0], hp.z[1], hp.z[2]},
-                  {hp.zn[0], hp.zn[1], hp.zn[2]}};
+  if (!p.reuse) {  // fused K0c and K0z
+    a.fb = FusedBoxes{(TileBox *)c->sbox_c.p, (TileBox *)c->gbox_c.p, (TileBox *)c->tbox_c.p, hp.blk, hp.blk_base};
+    a.zs = ZeroArgs{(int)p.nrows, 1, 0, R.dcnt, (unsigned long long *)c->workq.p, (unsigned char *)c->inconf.p,
+                    (unsigned long long *)c->tcpamax.p, (unsigned *)c->rowcnt.p, {hp.z[0], hp.z[1], hp.z[2]},
+                    {hp.zn[0], hp.zn[1], hp.zn[2]}};
   }
-  const int na = halo ? a1 - a0 : 0;
-  // halo overlap (Ctx::ov_mode): a kept plan of several ranks (mode 2: also the
-  // probe) sweeps the own column tiles on the stream while the exchange, the
-  // received tiles' K0b and their sweep run on xstream
-  const bool ovl = halo && hkeep && !noprune && na > 0 && (c->ov_mode == 2 || (c->ov_mode == 1 && c->halo_mode == 1));
-  if (ovl && ov_init(c)) return -1;
-  if (prepped) {  // K0b + K0c ran in the previous step's K4': K0z + the tile boxes here
-    if (!nozero && zero(false, nullptr, 0, true)) return -1;
-  } else if (!(halo && hkeep)) {  // (HK keep, several ranks: the own tiles go with the halo tiles below)
-    const unsigned g = halo ? (unsigned)na : blocks_for(n, kTile);
-    hipLaunchKernelGGL(k_prep_cols, dim3(g), dim3(kTile), 0, c->stream, (int)n, perm_c, home ? 1 : 0,
-                       recs ? 1 : 0, own, intr, distinct ? 1 : 0, shared ? 1 : 0, rpz, hpz, tla,
-                       (ColRec *)c->colrec.p, (PFRec *)c->pfcol.p, (PFVel *)c->pfvcol.p, (float4 *)c->pfpcol.p, mid,
-                       rz, fb, zs, halo ? a0 : 0, (const int *)nullptr, HaloUnpack{}, (Counters *)nullptr, tck, nfa,
-                       (int)g);
+  a.tile_base = p.halo ? p.a0 : 0;  // (halo mode: the own tiles only)
+  if (p.ovl && ov_init(c)) return -1;
+  if (p.prepped) {  // K0b + K0c ran in the previous step's K4': K0z + the tile boxes here
+    if (!p.nozero && R.zero(false, nullptr, 0, true)) return -1;
+  } else if (!(p.halo && p.hkeep)) {  // (HK keep, several ranks: the own tiles go with the halo tiles below)
+    if (launch_prep_cols(c, c->stream, p.halo ? (unsigned)p.na : blocks_for(p.n, kTile), a)) return -1;
   }
-  BSA_HIP(c, hipGetLastError());
-  if (halo) {
-    HaloUnpack hu{};
-    // (halo overlap: K0z before the pack -- xstream's K0b writes Counters)
-    if (ovl && !nozero && zero(false, nullptr, 0)) return -1;
-    if (halo_mid(c, rb, re, &hu, tpr ? &ht : nullptr, hkeep, ovl && c->halo_mode == 1 ? c->xstream : nullptr))
-      return -1;
-    const ZeroArgs zs2{(int)nrows, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, {}, {}};
-    FusedBoxes fb2 = fb;
-    fb2.blk = nullptr;
-    hu.count = halo_list_count(c);
-    if (ovl) {
-      // the own tiles (budget checks included) on the stream; the received
-      // ones on xstream once the exchange is in (the probe: no exchange, after
-      // K0z), which then waits for the own tiles (its sweep's rows)
-      if (c->halo_mode != 1) {
-        BSA_HIP(c, hipEventRecord(c->ov_ev[0], c->stream));
-        BSA_HIP(c, hipStreamWaitEvent(c->xstream, c->ov_ev[0], 0));
-      }
-      hipLaunchKernelGGL(k_prep_cols, dim3((unsigned)na), dim3(kTile), 0, c->stream, (int)n, perm_c, 1, recs ? 1 : 0,
-                         own, intr, 0, 1, rpz, hpz, tla, (ColRec *)c->colrec.p, (PFRec *)c->pfcol.p,
-                         (PFVel *)c->pfvcol.p, (float4 *)c->pfpcol.p, mid, rz, fb2, zs2, a0, (const int *)nullptr,
-                         HaloUnpack{}, (Counters *)nullptr, tck, nfa, na);
-      BSA_HIP(c, hipGetLastError());
-      BSA_HIP(c, hipEventRecord(c->ov_ev[1], c->stream));
-      if (c->halo_hl > 0) {
-        hipLaunchKernelGGL(k_prep_cols, dim3((unsigned)c->halo_hl), dim3(kTile), 0, c->xstream, (int)n, perm_c, 1,
-                           recs ? 1 : 0, own, intr, 0, 1, rpz, hpz, tla, (ColRec *)c->colrec.p,
-                           (PFRec *)c->pfcol.p, (PFVel *)c->pfvcol.p, (float4 *)c->pfpcol.p, mid, rz, fb2, zs2, 0,
-                           (const int *)c->h_hl.p, hu, dcnt, TprCheck{}, nfa, 0);
-        BSA_HIP(c, hipGetLastError());
-      }
-      BSA_HIP(c, hipStreamWaitEvent(c->xstream, c->ov_ev[1], 0));
-    } else if (hkeep) {
-      // HK keep: no plan, so the own tiles wait for nothing before the
-      // exchange -- ONE K0b for them and the received tiles (workgroups [0, na)
-      // the own tiles with their budget checks, the rest the halo list's
-      // slots); K0z is K2's (double-buffered counters) or its own launch,
-      // never inside it (its halo workgroups write Counters)
-      if (!nozero && zero(false, nullptr, 0)) return -1;
-      hipLaunchKernelGGL(k_prep_cols, dim3((unsigned)(na + c->halo_hl)), dim3(kTile), 0, c->stream, (int)n, perm_c,
-                         1, recs ? 1 : 0, own, intr, 0, 1, rpz, hpz, tla, (ColRec *)c->colrec.p,
-                         (PFRec *)c->pfcol.p, (PFVel *)c->pfvcol.p, (float4 *)c->pfpcol.p, mid, rz, fb2, zs2, a0,
-                         (const int *)c->h_hl.p, hu, dcnt, tck, nfa, na);
-      BSA_HIP(c, hipGetLastError());
-    } else if (c->halo_hl > 0) {  // the received tiles: unpacked (exchange), records and boxes (no zeroing here)
-      hipLaunchKernelGGL(k_prep_cols, dim3((unsigned)c->halo_hl), dim3(kTile), 0, c->stream, (int)n, perm_c, 1,
-                         recs ? 1 : 0, own, intr, 0, 1, rpz, hpz, tla, (ColRec *)c->colrec.p,
-                         (PFRec *)c->pfcol.p, (PFVel *)c->pfvcol.p, (float4 *)c->pfpcol.p, mid, rz, fb2, zs2, 0,
-                         (const int *)c->h_hl.p, hu, dcnt, TprCheck{}, nfa, 0);
-      BSA_HIP(c, hipGetLastError());
-    }
-  }
+  if (!p.halo) return 0;
+  // the later launches of the own tiles: K0z and the sent block are done
+  a.zs = no_zero;
+  a.fb.blk = nullptr;
+  return detect_halo_records(R, a);
+}
 
-  // ---- K0c/K0d group / tile boxes (rows; columns when reused) and the tile-pair work list
-  if (!shared && (!ensure(c, c->tbox_r, nrt * sizeof(TileBox), "row tile boxes") ||
-                  !ensure(c, c->gbox_r, ngr * sizeof(TileBox), "row group boxes")))
+// ---- K0c/K0d group / tile boxes (rows; columns when reused) and the tile-pair work list
+static int detect_tilepairs(DetectRun &R) {
+  Ctx *c = R.c;
+  const DetectPlan &p = R.p;
+  const int64_t roff = p.roff;
+  const bool tp_super = detect_env().tp_super;
+  if (!p.shared && (!ensure(c, c->tbox_r, p.nrt * sizeof(TileBox), "row tile boxes") ||
+                    !ensure(c, c->gbox_r, p.ngr * sizeof(TileBox), "row group boxes")))
     return -1;
-  const TileBox *gbox_r = shared ? (const TileBox *)c->gbox_c.p + roff / kGroup : (const TileBox *)c->gbox_r.p;
-  const TileBox *tbox_r = shared ? (const TileBox *)c->tbox_c.p + roff / kTile : (const TileBox *)c->tbox_r.p;
-  if (!shared)
-    hipLaunchKernelGGL(k_boxes, dim3(nrt), dim3(kTile), 0, c->stream, (int)nrows, pfrow, (TileBox *)nullptr,
-                       (TileBox *)c->gbox_r.p, (TileBox *)c->tbox_r.p, build, (Counters *)nullptr);
-  if (reuse)
-    hipLaunchKernelGGL(k_boxes, dim3(nct), dim3(kTile), 0, c->stream, (int)n, (const PFRec *)c->pfcol.p,
-                       (TileBox *)c->sbox_c.p, (TileBox *)c->gbox_c.p, (TileBox *)c->tbox_c.p, build, dcnt);
-  // ~1024 workgroups' worth of candidates per thread-chunk (one at 100k, several at 1M)
-  const unsigned long long icap = (unsigned long long)ntp * kSlicesPerTile;  // items: 8 slices per tile pair
-  if (tpr)  // (after halo_mid, which may have forced the rebuild)
-    tp = TprArgs{(unsigned long long *)c->tpr_ctl.p, ht.force, c->tpr_dx, c->tpr_ds, c->tpr_dv,
-                 (const PFRec *)c->pfcol.p + roff, (PFRec *)c->tpr_snap.p + roff, halo ? ht.myflag : nullptr,
-                 hkeep ? 1 : 0, hkeep ? (halo ? ht.myflag : (const unsigned *)c->tpr_ctl.p) : nullptr,
-                 hkeep && c->sim_ctl.p ? (unsigned long long *)((char *)c->sim_ctl.p + kSimCtlStale) : nullptr};
-  if (hkeep) {
+  R.gbox_r = p.shared ? (const TileBox *)c->gbox_c.p + roff / kGroup : (const TileBox *)c->gbox_r.p;
+  R.tbox_r = p.shared ? (const TileBox *)c->tbox_c.p + roff / kTile : (const TileBox *)c->tbox_r.p;
+  if (!p.shared)
+    hipLaunchKernelGGL(k_boxes, dim3(p.nrt), dim3(kTile), 0, c->stream, (int)p.nrows, R.pfrow, (TileBox *)nullptr,
+                       (TileBox *)c->gbox_r.p, (TileBox *)c->tbox_r.p, R.build, (Counters *)nullptr);
+  if (p.reuse)
+    hipLaunchKernelGGL(k_boxes, dim3(p.nct), dim3(kTile), 0, c->stream, (int)p.n, (const PFRec *)c->pfcol.p,
+                       (TileBox *)c->sbox_c.p, (TileBox *)c->gbox_c.p, (TileBox *)c->tbox_c.p, R.build, R.dcnt);
+  if (p.tpr)  // (after halo_mid, which may have forced the rebuild)
+    R.tp = TprArgs{(unsigned long long *)c->tpr_ctl.p, R.ht.force, c->tpr_dx, c->tpr_ds, c->tpr_dv,
+                   (const PFRec *)c->pfcol.p + roff, (PFRec *)c->tpr_snap.p + roff, p.halo ? R.ht.myflag : nullptr,
+                   p.hkeep ? 1 : 0, p.hkeep ? (p.halo ? R.ht.myflag : (const unsigned *)c->tpr_ctl.p) : nullptr,
+                   p.hkeep && c->sim_ctl.p ? (unsigned long long *)((char *)c->sim_ctl.p + kSimCtlStale) : nullptr};
+  if (p.hkeep) {
     // HK keep: no K0d -- the prefilter takes the kept list's counts from the control words
-  } else if ((nct <= kTPDirectMax || tp_list) && !tp_super)
-    hipLaunchKernelGGL(k_tilepairs_direct, dim3((unsigned)nrt), dim3(kTPDirectThreads), 0, c->stream, nrt, nct,
-                       (int)nrows, tbox_r, gbox_r, (const TileBox *)c->tbox_c.p, noprune, (uint2 *)c->tilepairs.p,
-                       icap, dcnt, (unsigned long long *)c->workq.p, build, halo ? halo_present(c) : nullptr, a0,
-                       a1, nozero ? (const TileBox *)c->gbox_c.p : (const TileBox *)nullptr,
-                       tp_list ? (const int *)c->h_hl.p : (const int *)nullptr, (int)c->halo_hl,
-                       tp_list ? halo_list_count(c) : (const unsigned *)nullptr, tp);
+  } else if ((p.nct <= kTPDirectMax || p.tp_list) && !tp_super)
+    hipLaunchKernelGGL(k_tilepairs_direct, dim3((unsigned)p.nrt), dim3(kTPDirectThreads), 0, c->stream, p.nrt, p.nct,
+                       (int)p.nrows, R.tbox_r, R.gbox_r, (const TileBox *)c->tbox_c.p, p.noprune,
+                       (uint2 *)c->tilepairs.p, p.icap, R.dcnt, (unsigned long long *)c->workq.p, R.build,
+                       p.halo ? halo_present(c) : nullptr, p.a0, p.a1,
+                       p.nozero ? (const TileBox *)c->gbox_c.p : (const TileBox *)nullptr,
+                       p.tp_list ? (const int *)c->h_hl.p : (const int *)nullptr, (int)c->halo_hl,
+                       p.tp_list ? halo_list_count(c) : (const unsigned *)nullptr, R.tp);
   else
-    hipLaunchKernelGGL(k_tilepairs, dim3((unsigned)((nrt + kSuper - 1) / kSuper)), dim3(kTPThreads), 0, c->stream,
-                       nrt, nct, (int)nrows, tbox_r, gbox_r, (const TileBox *)c->tbox_c.p, noprune,
-                       (uint2 *)c->tilepairs.p, icap, dcnt, (unsigned long long *)c->workq.p, build,
-                       halo ? halo_present(c) : nullptr, a0, a1);
+    hipLaunchKernelGGL(k_tilepairs, dim3((unsigned)((p.nrt + kSuper - 1) / kSuper)), dim3(kTPThreads), 0, c->stream,
+                       p.nrt, p.nct, (int)p.nrows, R.tbox_r, R.gbox_r, (const TileBox *)c->tbox_c.p, p.noprune,
+                       (uint2 *)c->tilepairs.p, p.icap, R.dcnt, (unsigned long long *)c->workq.p, R.build,
+                       p.halo ? halo_present(c) : nullptr, p.a0, p.a1);
   BSA_HIP(c, hipGetLastError());
-  if (mark(1)) return -1;
+  return 0;
+}
 
-  const float T = (float)(tla > 0.0 ? tla : 0.0);
-  const float lim = (float)((rpz + kEABS + (reuse ? 2.0 * c->reuse_sh : 0.0)) / (1.0 - kE1));
+// longest items first (HeavyArgs): detects of a kept tile-pair list only
+// (Ctx::hv_us: the listing threshold, < 0 off); leaves the next detect's
+// listing (R.hn) to K1b / K2
+static int heavy_setup(DetectRun &R, HeavyArgs *hv) {
+  Ctx *c = R.c;
+  const DetectPlan &p = R.p;
+  const unsigned long long icap = p.icap;
+  if (!(p.tpr && c->hv_us >= 0.0)) return 0;
+  const bool fresh = c->hv_icap != icap || !c->hv_cnt.p;
+  if (!ensure(c, c->hv_cost, icap * 4, "item costs") || !ensure(c, c->hv_flag, icap * 4, "listed item flags") ||
+      !ensure(c, c->hv_list[0], icap * 4, "listed items") || !ensure(c, c->hv_list[1], icap * 4, "listed items") ||
+      !ensure(c, c->hv_list[2], icap * 4, "listed items") || !ensure(c, c->hv_list[3], icap * 4, "listed items") ||
+      !ensure(c, c->hv_cnt, 64, "listed item counts"))
+    return -1;
+  if (fresh) {
+    BSA_HIP(c, hipMemsetAsync(c->hv_cost.p, 0, icap * 4, c->stream));
+    BSA_HIP(c, hipMemsetAsync(c->hv_flag.p, 0, icap * 4, c->stream));
+    BSA_HIP(c, hipMemsetAsync(c->hv_cnt.p, 0, 64, c->stream));
+    c->hv_icap = icap;
+  }
+  const unsigned E = ++c->hv_epoch;  // (flags hold epochs >= 1; 0 = never)
+  unsigned *cn = (unsigned *)c->hv_cnt.p;
+  const unsigned a = E & 1, b = (E + 1) & 1;  // this detect's / the next one's lists and counts
+  const double x = c->hv_x > 0.0 ? c->hv_x : 1e30;  // (tier 0 off: no slot reaches it)
+  // a rank's share (halo mode) sweeps in ~40 us, not ~70: half the threshold
+  // (one rank of 8 at global1m, probe A/B x 3: 0.1010-0.1029 -> 0.1007-0.1009
+  // ms per step at 8 us, 0.0995-0.1010 at 5; box100k unchanged at 16)
+  const double us = p.halo && !c->hv_us_env ? 0.5 * c->hv_us : c->hv_us;
+  *hv = HeavyArgs{{(const unsigned *)c->hv_list[2 * a].p, (const unsigned *)c->hv_list[2 * a + 1].p}, cn + 2 * a,
+                  cn + 2 * b, (const unsigned *)c->hv_flag.p, (unsigned *)c->hv_cost.p, E};
+  R.hn = HeavyNext{(unsigned *)c->hv_cost.p, {(unsigned *)c->hv_list[2 * b].p, (unsigned *)c->hv_list[2 * b + 1].p},
+                   cn + 2 * b, (unsigned *)c->hv_flag.p, E + 1,
+                   {(unsigned)std::min(us * x * 100.0, 4e9), (unsigned)std::min(us * 100.0, 4e9)},
+                   // the list's item counts: ctl[1], ctl[2] (the prefilter publishes a built list's there;
+                   // an HK-kept detect fills no dequeue words)
+                   (const unsigned long long *)c->tpr_ctl.p, icap};
+  return 0;
+}
+
+// One K1a launch (k_prefilter): rp and xf are the same at every launch of one
+// detect; a launch site states the knobs and what differs from no list reuse
+// and no listing
+struct PrefilterLaunch {
+  RefineParams rp;
+  ExactFuse xf;
+  PfKnobs kn;
+  TprArgs tp{};
+  HeavyArgs hv{};
+};
+static int launch_prefilter(const DetectRun &R, hipStream_t stream, unsigned grid, const PrefilterLaunch &a) {
+  Ctx *c = R.c;
+  const DetectPlan &p = R.p;
+  const auto K = p.noprune ? k_prefilter<true> : k_prefilter<false>;
+  hipLaunchKernelGGL(K, dim3(grid), dim3(PF_BLOCK), 0, stream, R.pfrow, R.pfvrow, R.pfprow, (int)p.nrows,
+                     (const PFRec *)c->pfcol.p, (const PFVel *)c->pfvcol.p, (const float4 *)c->pfpcol.p, (int)p.n,
+                     R.gbox_r, (const TileBox *)c->sbox_c.p, p.noprune, (const uint2 *)c->tilepairs.p, p.icap, R.dcnt,
+                     (unsigned long long *)c->workq.p, a.rp, (uint2 *)c->cand.p, p.cap, R.build, a.kn, p.diag, a.tp,
+                     a.hv, a.xf);
+  BSA_HIP(c, hipGetLastError());
+  return 0;
+}
+
+// ---- K1a prefilter (with K1b when fused), the overlap's two sweeps and their join
+static int detect_prefilter(DetectRun &R) {
+  Ctx *c = R.c;
+  const DetectPlan &p = R.p;
+  const float T = (float)(p.tla > 0.0 ? p.tla : 0.0);
+  const float lim = (float)((p.rpz + kEABS + (p.reuse ? 2.0 * c->reuse_sh : 0.0)) / (1.0 - kE1));
   const float liml = lim / kRS;  // unit-sphere units (pf_refine)
-  const RefineParams rp{(float)rpz, (float)hpz, T, kwik ? INFINITY : liml * liml, 0.f};
-  // ---- K1a prefilter: persistent grid, PF_BLOCKS_PER_CU workgroups per CU
-  // (LDS-limited residency), at least one workgroup per dequeue shard
-  // pieces: ~8 items per row tile, a few hundred row tiles fill the waves;
-  // fewer rows split the items (BSA_PF_PIECES overrides)
-  static const int pieces_env = getenv("BSA_PF_PIECES") ? atoi(getenv("BSA_PF_PIECES")) : 0;
-  PfKnobs kn{1, 1, 1, 0, 0, 0};
-  static const int t0_env = getenv("BSA_PF_HEAVY_T0") ? atoi(getenv("BSA_PF_HEAVY_T0")) : -1;
-  if (t0_env >= 0 && t0_env <= 3) kn.t0 = t0_env;
-  // (measured, tools/gpu_pieces.sh: 2 pieces at the 100k box, 102 -> 97 us; 4 for
-  // one rank of 8 there, 36 -> 29 us; 2 at 125k rows of 1M, 65 -> 53 us; 1
-  // from 250k rows up, where 2 cost +15 us.  Round 5, with the longest-items
-  // listing and the fused K1b: 1 piece from 64k rows up -- the 100k box
-  // 0.1204 / 0.1212 -> 0.1185 / 0.1181 ms per step, one rank of 8 at 1M
-  // 0.1130 / 0.1117 -> 0.1118 / 0.1112; tools/gpu_ab.sh, BSA_PF_PIECES=1),
-  // 2 from 16k rows: one rank of 4 at the 100k box (25k rows) 0.0942 / 0.0938
-  // -> 0.0925 / 0.0912 (tools/probe_step.py), of 8 (12.8k rows) stays at 4
-  kn.pieces = nrows >= (1 << 16) ? 1 : (nrows >= (1 << 14) ? 2 : 4);
-  if (pieces_env == 1 || pieces_env == 2 || pieces_env == 4 || pieces_env == 8) kn.pieces = pieces_env;
-  static const int pnear_env = getenv("BSA_PF_PIECES_NEAR") ? atoi(getenv("BSA_PF_PIECES_NEAR")) : 0;
-  kn.pnear = kn.pieces;
-  if (pnear_env == 1 || pnear_env == 2 || pnear_env == 4 || pnear_env == 8) kn.pnear = pnear_env;
+  PrefilterLaunch a{RefineParams{(float)p.rpz, (float)p.hpz, T, p.kwik ? INFINITY : liml * liml, 0.f}, ExactFuse{}, p.kn};
 #ifdef BSA_PF_TRACE
   {
     static DevBuf tb;
@@ -3103,123 +3393,74 @@ int detect_enqueue(Ctx *c, double rpz, double hpz, double tla, int flags, int64_
     c->trace_bytes = need;
   }
 #endif
-  // longest items first (HeavyArgs): detects of a kept tile-pair list only
-  // (Ctx::hv_us: the listing threshold, < 0 off)
   HeavyArgs hv{};
-  HeavyNext hn{};
-  if (tpr && c->hv_us >= 0.0) {
-    const bool fresh = c->hv_icap != icap || !c->hv_cnt.p;
-    if (!ensure(c, c->hv_cost, icap * 4, "item costs") || !ensure(c, c->hv_flag, icap * 4, "listed item flags") ||
-        !ensure(c, c->hv_list[0], icap * 4, "listed items") || !ensure(c, c->hv_list[1], icap * 4, "listed items") ||
-        !ensure(c, c->hv_list[2], icap * 4, "listed items") || !ensure(c, c->hv_list[3], icap * 4, "listed items") ||
-        !ensure(c, c->hv_cnt, 64, "listed item counts"))
-      return -1;
-    if (fresh) {
-      BSA_HIP(c, hipMemsetAsync(c->hv_cost.p, 0, icap * 4, c->stream));
-      BSA_HIP(c, hipMemsetAsync(c->hv_flag.p, 0, icap * 4, c->stream));
-      BSA_HIP(c, hipMemsetAsync(c->hv_cnt.p, 0, 64, c->stream));
-      c->hv_icap = icap;
-    }
-    const unsigned E = ++c->hv_epoch;  // (flags hold epochs >= 1; 0 = never)
-    unsigned *cn = (unsigned *)c->hv_cnt.p;
-    const unsigned a = E & 1, b = (E + 1) & 1;  // this detect's / the next one's lists and counts
-    const double x = c->hv_x > 0.0 ? c->hv_x : 1e30;  // (tier 0 off: no slot reaches it)
-    // a rank's share (halo mode) sweeps in ~40 us, not ~70: half the threshold
-    // (one rank of 8 at global1m, probe A/B x 3: 0.1010-0.1029 -> 0.1007-0.1009
-    // ms per step at 8 us, 0.0995-0.1010 at 5; box100k unchanged at 16)
-    const double us = halo && !c->hv_us_env ? 0.5 * c->hv_us : c->hv_us;
-    hv = HeavyArgs{{(const unsigned *)c->hv_list[2 * a].p, (const unsigned *)c->hv_list[2 * a + 1].p}, cn + 2 * a,
-                   cn + 2 * b, (const unsigned *)c->hv_flag.p, (unsigned *)c->hv_cost.p, E};
-    hn = HeavyNext{(unsigned *)c->hv_cost.p, {(unsigned *)c->hv_list[2 * b].p, (unsigned *)c->hv_list[2 * b + 1].p},
-                   cn + 2 * b, (unsigned *)c->hv_flag.p, E + 1,
-                   {(unsigned)std::min(us * x * 100.0, 4e9), (unsigned)std::min(us * 100.0, 4e9)},
-                   // the list's item counts: ctl[1], ctl[2] (the prefilter publishes a built list's there;
-                   // an HK-kept detect fills no dequeue words)
-                   (const unsigned long long *)c->tpr_ctl.p, icap};
-  }
-  // K2 row buckets (B pairs per row per list; a fuller row retries wider, then without)
-  const int B = c->k2_bucket;
-  if (B && !ensure(c, c->kbuck, (size_t)2 * nrows * B * sizeof(uint2), "K2 row buckets")) return -1;
-  // K1b fused into the prefilter (ExactFuse): stored records, row buckets, no
-  // KWIK / candidate reuse, not one rank's share of a sharded step (there the
-  // sweep is short and the workgroups' end-of-sweep evaluation lengthened it
-  // more than K1b's launch cost: global1m rank 2 of 8, prefilter 46 + K1b 11
-  // -> 63 us; box100k one rank: 0.1387-0.1396 -> 0.1336-0.1367 ms per step).
-  // BSA_FUSE_EXACT=0/1 overrides (A/B).
-  static const int fuse_env = getenv("BSA_FUSE_EXACT") ? atoi(getenv("BSA_FUSE_EXACT")) : -1;
-  const bool fuse = fuse_env != 0 && (fuse_env == 1 || !halo) && c->fuse_on && !c->fuse_skip && B > 0 && recs &&
-                    !kwik && !reuse && !ovl;
-  c->fuse_skip = false;  // (one retry unfused; the next detect fuses again)
-  ExactFuse xf{};
-  if (fuse)
-    xf = ExactFuse{rowrec, (const ColRec *)c->colrec.p, perm_r, perm_c, rpz, hpz, tla, (int)rb, (int)nrows, B,
-                   (double *)c->cpay.p, (unsigned *)c->rowcnt.p, (uint2 *)c->kbuck.p, (unsigned)c->fuse_recs};
-  c->last_fused = fuse;
-  if (fuse) c->fuse_count++;
-  // rows sharing the column records: row i is column roff + i (its diagonal)
-  const int diag = shared ? (int)roff : -1;
-  const unsigned pf_grid = (unsigned)std::max<long long>(
-      kWorkShards, std::min<long long>(ntp * PF_ITEMS_PER_TILE / PF_WAVES + 1, 256 * PF_BLOCKS_PER_CU));
-  if (noprune)
-    hipLaunchKernelGGL(k_prefilter<true>, dim3(pf_grid), dim3(PF_BLOCK), 0, c->stream, pfrow, pfvrow, pfprow,
-                       (int)nrows, (const PFRec *)c->pfcol.p, (const PFVel *)c->pfvcol.p,
-                       (const float4 *)c->pfpcol.p, (int)n, gbox_r, (const TileBox *)c->sbox_c.p, noprune,
-                       (const uint2 *)c->tilepairs.p, icap, dcnt,
-                       (unsigned long long *)c->workq.p, rp, (uint2 *)c->cand.p, cap, build, kn, diag, TprArgs{},
-                       HeavyArgs{}, xf);
-  else
-    for (int ph = ovl ? 1 : 0; ph <= (ovl ? 2 : 0); ++ph) {  // (halo overlap: own tiles here, the others on xstream)
-      PfKnobs kp = kn;
-      kp.ph = ph;
-      kp.ca0 = a0;
-      kp.ca1 = a1;
+  if (heavy_setup(R, &hv)) return -1;
+  if (p.B && !ensure(c, c->kbuck, (size_t)2 * p.nrows * p.B * sizeof(uint2), "K2 row buckets")) return -1;
+  if (p.fuse)
+    a.xf = ExactFuse{R.rowrec, (const ColRec *)c->colrec.p, R.perm_r, R.perm_c, p.rpz, p.hpz, p.tla, (int)p.rb,
+                     (int)p.nrows, p.B, (double *)c->cpay.p, (unsigned *)c->rowcnt.p, (uint2 *)c->kbuck.p,
+                     (unsigned)c->fuse_recs};
+  if (p.noprune) {  // every tile pair, every pair: no list reuse, no listing
+    if (launch_prefilter(R, c->stream, p.pf_grid, a)) return -1;
+  } else {
+    a.tp = R.tp;
+    a.hv = hv;
+    for (int ph = p.ovl ? 1 : 0; ph <= (p.ovl ? 2 : 0); ++ph) {  // (halo overlap: own tiles here, the others on xstream)
+      a.kn.ph = ph;
+      a.kn.ca0 = p.a0;
+      a.kn.ca1 = p.a1;
       // (the own tiles' sweep leaves half the workgroup slots to the received
       // tiles' K0b and sweep: 2 of 4 per CU, BSA_OV_GRID_A; probe with the
       // overlap 0.134 ms per step at 4, 0.121 at 2, 0.104 without it)
-      static const int ga = getenv("BSA_OV_GRID_A") ? atoi(getenv("BSA_OV_GRID_A")) : 2;
-      const unsigned g = ph == 1 && ga > 0 ? std::min<unsigned>(pf_grid, std::max(256u * (unsigned)ga, (unsigned)kWorkShards)) : pf_grid;
-      hipLaunchKernelGGL(k_prefilter<false>, dim3(g), dim3(PF_BLOCK), 0, ph == 2 ? c->xstream : c->stream,
-                         pfrow, pfvrow, pfprow, (int)nrows, (const PFRec *)c->pfcol.p, (const PFVel *)c->pfvcol.p,
-                         (const float4 *)c->pfpcol.p, (int)n, gbox_r, (const TileBox *)c->sbox_c.p, noprune,
-                         (const uint2 *)c->tilepairs.p, icap, dcnt,
-                         (unsigned long long *)c->workq.p, rp, (uint2 *)c->cand.p, cap, build, kp, diag, tp, hv, xf);
-      BSA_HIP(c, hipGetLastError());
+      const int ga = detect_env().ov_grid_a;
+      const unsigned g = ph == 1 && ga > 0
+                             ? std::min<unsigned>(p.pf_grid, std::max(256u * (unsigned)ga, (unsigned)kWorkShards))
+                             : p.pf_grid;
+      if (launch_prefilter(R, ph == 2 ? c->xstream : c->stream, g, a)) return -1;
     }
-  if (ovl) {  // join: K1b on waits for the halo tiles' sweep
+  }
+  if (p.ovl) {  // join: K1b on waits for the halo tiles' sweep
     BSA_HIP(c, hipEventRecord(c->ov_ev[2], c->xstream));
     BSA_HIP(c, hipStreamWaitEvent(c->stream, c->ov_ev[2], 0));
     c->ov_count++;
   }
+  return 0;
+}
+
+// ---- K1b exact evaluation (unless fused into K1a): grid-stride over the
+// device-side count of the dense candidate list; 2048 workgroups (524 k lanes:
+// the 100k box's ~153 k candidates in one stride, the workgroups past the
+// count exit at once; BSA_K1B_GRID overrides for A/B)
+static int detect_exact(DetectRun &R) {
+  Ctx *c = R.c;
+  const DetectPlan &p = R.p;
+  if (p.fuse) return 0;
+  const auto KEX = !p.recs ? k_exact<kExactHome> : (p.kwik ? k_exact<kExactKwik> : k_exact<kExactRec>);
+  const int k1b_grid = detect_env().k1b_grid;
+  hipLaunchKernelGGL(KEX, dim3(k1b_grid > 0 ? (unsigned)k1b_grid : 256u * 8u), dim3(256), 0, c->stream, R.rowrec,
+                     (const ColRec *)c->colrec.p, R.perm_r, R.perm_c, (const uint2 *)c->cand.p, R.dcnt, R.own, p.cap,
+                     p.rpz, p.hpz, p.tla, (int)p.rb, (int)p.nrows, (unsigned char *)c->cflag.p, (double *)c->cpay.p,
+                     (unsigned char *)c->inconf.p, (unsigned long long *)c->tcpamax.p, (unsigned *)c->rowcnt.p,
+                     (uint2 *)c->kbuck.p, p.B, p.reuse ? (unsigned *)c->reuse_ctl.p : nullptr,
+                     (const Snap *)c->snap_cur.p, (Snap *)c->snap_build.p, (int)p.n, R.hn);
   BSA_HIP(c, hipGetLastError());
-  if (mark(2)) return -1;
-  // ---- K1b exact evaluation: grid-stride over the device-side count of the
-  // dense candidate list; 2048 workgroups (524 k lanes: the 100k box's ~153 k
-  // candidates in one stride, the workgroups past the count exit at once;
-  // BSA_K1B_GRID overrides for A/B)
-  if (!fuse) {
-    const auto KEX = !recs ? k_exact<kExactHome> : (kwik ? k_exact<kExactKwik> : k_exact<kExactRec>);
-    static const int k1b_grid = getenv("BSA_K1B_GRID") ? atoi(getenv("BSA_K1B_GRID")) : 0;
-    hipLaunchKernelGGL(KEX, dim3(k1b_grid > 0 ? (unsigned)k1b_grid : 256u * 8u), dim3(256), 0, c->stream, rowrec, (const ColRec *)c->colrec.p,
-                       perm_r, perm_c, (const uint2 *)c->cand.p, dcnt, own, cap, rpz, hpz, tla, (int)rb,
-                       (int)nrows,
-                       (unsigned char *)c->cflag.p, (double *)c->cpay.p,
-                       (unsigned char *)c->inconf.p, (unsigned long long *)c->tcpamax.p,
-                       (unsigned *)c->rowcnt.p, (uint2 *)c->kbuck.p, B,
-                       reuse ? (unsigned *)c->reuse_ctl.p : nullptr,
-                       (const Snap *)c->snap_cur.p, (Snap *)c->snap_build.p, (int)n, hn);
-  }
-  BSA_HIP(c, hipGetLastError());
-  if (mark(3)) return -1;
-  // ---- K2: row offsets and the pairs in row-major order: from K1b's row
-  // buckets (k_rank_rows, one launch), or scan + scatter into row segments +
-  // per-segment rank (bucket width 0)
+  return 0;
+}
+
+// ---- K2: row offsets and the pairs in row-major order: from K1b's row
+// buckets (k_rank_rows, one launch), or scan + scatter into row segments +
+// per-segment rank (bucket width 0); MVP's per-pair vectors when asked for
+static int detect_rank(DetectRun &R) {
+  Ctx *c = R.c;
+  const DetectPlan &p = R.p;
+  const unsigned long long cap = p.cap;
+  const int nrows = (int)p.nrows, rb = (int)p.rb, B = p.B;
   if (!B) {
-    const int nscan = (int)(2 * (nrows + 1));
+    const int nscan = 2 * (nrows + 1);
     if (scan_excl(c, (const unsigned *)c->rowcnt.p, (unsigned *)c->rowoff.p, nscan)) return -1;
-    hipLaunchKernelGGL(k_scatter, dim3(256 * 4), dim3(256), 0, c->stream, (const Counters *)dcnt, cap, (int)rb,
-                       (int)nrows, (const unsigned char *)c->cflag.p, (const double *)c->cpay.p,
-                       (const unsigned *)c->rowoff.p, (unsigned *)c->rowcnt.p,
-                       (unsigned long long *)c->ckey2.p, (unsigned *)c->cval2.p,
+    hipLaunchKernelGGL(k_scatter, dim3(256 * 4), dim3(256), 0, c->stream, (const Counters *)R.dcnt, cap, rb, nrows,
+                       (const unsigned char *)c->cflag.p, (const double *)c->cpay.p, (const unsigned *)c->rowoff.p,
+                       (unsigned *)c->rowcnt.p, (unsigned long long *)c->ckey2.p, (unsigned *)c->cval2.p,
                        (unsigned long long *)c->lkey2.p);
     BSA_HIP(c, hipGetLastError());
   }
@@ -3237,43 +3478,62 @@ int detect_enqueue(Ctx *c, double rpz, double hpz, double tla, int flags, int64_
     mf.pfl = (uint8_t *)c->mvp_pfl.p;
     c->fuse_done = true;
     if (B) {  // K2 also folds each row's vectors (MvpIn::rowdv)
-      if (!ensure(c, c->mvp_rowdv, (size_t)std::max<int64_t>(nrows, 1) * sizeof(double4), "mvp row dv")) return -1;
+      if (!ensure(c, c->mvp_rowdv, (size_t)std::max(nrows, 1) * sizeof(double4), "mvp row dv")) return -1;
       mf.rowdv = (double4 *)c->mvp_rowdv.p;
       c->fuse_rowdv = true;
     }
   }
   if (B) {
-    const bool hl = fuse && hn.cost;  // the heavy-item listing moves here from K1b
-    hipLaunchKernelGGL(k_rowblk, dim3((unsigned)((rank_blocks((int)nrows) + kRowblkWaves - 1) / kRowblkWaves) +
+    const bool hl = p.fuse && R.hn.cost;  // the heavy-item listing moves here from K1b
+    hipLaunchKernelGGL(k_rowblk, dim3((unsigned)((rank_blocks(nrows) + kRowblkWaves - 1) / kRowblkWaves) +
                                           (hl ? kHeavyBlocks : 0u)),
-                       dim3(64 * kRowblkWaves), 0,
-                       c->stream, (int)nrows, (unsigned *)c->rowcnt.p, hl ? hn : HeavyNext{});
-    const RankLaunch rl{(unsigned)rank_blocks((int)nrows), (int)nrows, dcnt, cap, (unsigned *)c->rowoff.p,
-                        (unsigned *)c->rowcnt.p, (const uint2 *)c->kbuck.p, B, (const double *)c->cpay.p, (int)rb,
+                       dim3(64 * kRowblkWaves), 0, c->stream, nrows, (unsigned *)c->rowcnt.p, hl ? R.hn : HeavyNext{});
+    const RankLaunch rl{(unsigned)rank_blocks(nrows), nrows, R.dcnt, cap, (unsigned *)c->rowoff.p,
+                        (unsigned *)c->rowcnt.p, (const uint2 *)c->kbuck.p, B, (const double *)c->cpay.p, rb,
                         (int *)c->out_ci.p, (int *)c->out_cj.p, (double *)c->out_pay.p, (int *)c->out_li.p,
-                        (int *)c->out_lj.p, (unsigned long long *)c->stats.p, gate, build, mf,
+                        (int *)c->out_lj.p, (unsigned long long *)c->stats.p, R.gate, R.build, mf,
                         (unsigned char *)c->inconf.p, (unsigned long long *)c->tcpamax.p,
-                        (Counters *)c->counters2.p, (unsigned long long *)c->workq2.p, nfa, hk_word};
+                        (Counters *)c->counters2.p, (unsigned long long *)c->workq2.p, R.nfa, R.hk_word};
     if (c->k24_want) {  // bsa_sim_step launches it fused with K4' (k24_launch)
       c->k24_blob.resize(sizeof rl);
       memcpy(c->k24_blob.data(), &rl, sizeof rl);
       c->k24_pending = true;
-      c->k24_ev = timed ? ev[4] : nullptr;
+      c->k24_ev = p.timed ? p.ev[4] : nullptr;
     } else {
       rank_launch(c, rl, false, K24Args{});
     }
-    c->zeroed_rows = nrows;
+    c->zeroed_rows = p.nrows;
   } else {
-    hipLaunchKernelGGL(k_rank, dim3(256 * 4), dim3(256), 0, c->stream, (int)nrows, dcnt, cap,
+    hipLaunchKernelGGL(k_rank, dim3(256 * 4), dim3(256), 0, c->stream, nrows, R.dcnt, cap,
                        (const unsigned *)c->rowoff.p, (const unsigned long long *)c->ckey2.p,
                        (const unsigned *)c->cval2.p, (const double *)c->cpay.p,
-                       (const unsigned long long *)c->lkey2.p, (int)rb, (int *)c->out_ci.p, (int *)c->out_cj.p,
+                       (const unsigned long long *)c->lkey2.p, rb, (int *)c->out_ci.p, (int *)c->out_cj.p,
                        (double *)c->out_pay.p, (int *)c->out_li.p, (int *)c->out_lj.p,
-                       (unsigned long long *)c->stats.p, gate, build, mf, nfa, (unsigned long long *)c->tcpamax.p);
+                       (unsigned long long *)c->stats.p, R.gate, R.build, mf, R.nfa, (unsigned long long *)c->tcpamax.p);
   }
   BSA_HIP(c, hipGetLastError());
-  if (!c->k24_pending && mark(4)) return -1;
-  c->ev_valid = c->ev_valid || timed;
+  return 0;
+}
+
+// Enqueue one complete detect on the stream (K0-K2), no host synchronisation.
+// gate (device, nullable): receives {overflow, P} for the resident sim step.
+int detect_enqueue(Ctx *c, double rpz, double hpz, double tla, int flags, int64_t rb, int64_t re,
+                   unsigned long long *gate) {
+  DetectPlan p;
+  if (detect_decide(c, rpz, hpz, tla, flags, rb, re, &p)) return -1;
+  DetectRun R{c, p, gate, soa(c->own), soa(p.distinct ? c->intr : c->own), (Counters *)c->counters.p,
+              NfArgs{(unsigned long long *)c->nonfin.p, p.nf_epoch, nullptr}};
+  if (R.mark(0)) {
+    c->reuse_valid = false;  // (detect_decide's optimistic mark: nothing of this detect is enqueued)
+    return -1;
+  }
+  if (p.empty) return detect_empty(R);
+  if (detect_order(R) || detect_records(R) || detect_tilepairs(R) || R.mark(1)) return -1;
+  if (detect_prefilter(R) || R.mark(2)) return -1;
+  if (detect_exact(R) || R.mark(3)) return -1;
+  if (detect_rank(R)) return -1;
+  if (!c->k24_pending && R.mark(4)) return -1;
+  c->ev_valid = c->ev_valid || p.timed;
   return 0;
 }
 
