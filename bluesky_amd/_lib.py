@@ -201,7 +201,13 @@ SIGNATURES.update({
     'bsa_sim_comm_stats': (ctypes.c_int, [_vp, _c_i64p]),
     'bsa_sim_set_atmos': (ctypes.c_int, [_vp, ctypes.c_int]),
     'bsa_sim_read_atmos': (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp]),
+    'bsa_openap_forces': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _c_dp, _c_dp, _c_i32p, _c_u8p] +
+                          [_c_dp] * 10),
+    'bsa_sim_set_forces': (ctypes.c_int, [_vp, ctypes.c_int64, _c_dp, _c_dp]),
+    'bsa_sim_read_forces': (ctypes.c_int, [_vp] + [_c_dp] * 7),
 })
+
+FORCE_OUTPUTS = ('cd0', 'drag', 'thrustratio', 'thrust', 'fuelflow', 'bank')
 
 UNIQUE_ID_BYTES = 128
 
@@ -647,6 +653,55 @@ class Context:
         ax = np.zeros(self.n)
         self.check(self.lib.bsa_sim_read_perf(self.h, ptr(ph, _c_u8p), ptr(ax)), 'bsa_sim_read_perf')
         return ph, ax
+
+    @staticmethod
+    def _force_table(ftable):
+        ft = np.ascontiguousarray(ftable, dtype=np.float64)
+        if ft.ndim != 2 or ft.shape[1] != 16:
+            raise ValueError('force table must be ntypes x 16')
+        return ft
+
+    def openap_forces(self, table, ftable, type_idx, mass, tas, vs, alt, phase=None, bank=None):
+        """bsa_openap_forces: dict of FORCE_OUTPUTS (float64 [n]) for host arrays."""
+        tab = np.ascontiguousarray(table, dtype=np.float64)
+        ft = self._force_table(ftable)
+        if tab.ndim != 2 or tab.shape[1] != 24 or tab.shape[0] != ft.shape[0]:
+            raise ValueError('type table must be ntypes x 24 with the force table\'s row count')
+        idx = np.ascontiguousarray(type_idx, dtype=np.int32).ravel()
+        n = len(idx)
+        arrs = [f64(a).ravel() for a in (mass, tas, vs, alt)]
+        ph = None if phase is None else np.ascontiguousarray(phase, dtype=np.uint8).ravel()
+        for a in arrs + ([ph] if ph is not None else []):
+            if len(a) != n:
+                raise ValueError('forces input has length %d != %d' % (len(a), n))
+        out = {k: np.zeros(n) for k in FORCE_OUTPUTS}
+        if bank is not None:
+            out['bank'] = np.array(bank, dtype=np.float64).ravel()
+            if len(out['bank']) != n:
+                raise ValueError('bank has length %d != %d' % (len(out['bank']), n))
+        self.check(self.lib.bsa_openap_forces(self.h, n, tab.shape[0], ptr(tab), ptr(ft), ptr(idx, _c_i32p),
+                                              ptr(ph, _c_u8p), *[ptr(a) for a in arrs],
+                                              *[ptr(out[k]) for k in FORCE_OUTPUTS]), 'bsa_openap_forces')
+        return out
+
+    def sim_set_forces(self, ftable=None, mass=None):
+        """bsa_sim_set_forces: OpenAP drag / thrust / fuel flow + fuel burnt in every
+        step (``ftable`` / ``mass`` from bluesky_amd.perf.force_table); None = off."""
+        if ftable is None:
+            self.check(self.lib.bsa_sim_set_forces(self.h, 0, None, None), 'bsa_sim_set_forces')
+            return
+        ft = self._force_table(ftable)
+        m = f64(mass).ravel()
+        if len(m) != self.n:
+            raise ValueError('mass has length %d != %d' % (len(m), self.n))
+        self.check(self.lib.bsa_sim_set_forces(self.h, ft.shape[0], ptr(ft), ptr(m)), 'bsa_sim_set_forces')
+
+    def sim_read_forces(self):
+        """dict of FORCE_OUTPUTS + fuel_used of this rank's rows (full-n arrays, other rows 0)."""
+        out = {k: np.zeros(self.n) for k in FORCE_OUTPUTS + ('fuel_used',)}
+        self.check(self.lib.bsa_sim_read_forces(self.h, *[ptr(out[k]) for k in FORCE_OUTPUTS + ('fuel_used',)]),
+                   'bsa_sim_read_forces')
+        return out
 
     def sim_update(self, **arrays):
         """bsa_sim_update: overwrite the given full-n state arrays (SIM_STATE_FIELDS

@@ -456,6 +456,14 @@ struct Ctx {
   // type index (int32) and the phase of the last step (u8)
   DevBuf s_ptab, s_ptype, s_phase;
   bool sim_perf = false;
+  // OpenAP drag / thrust / fuel flow (bsa_sim_set_forces, bsa_perf.hip): the
+  // force table (16 doubles per type of s_ptab), per-aircraft mass, the six
+  // outputs of the last step (6 x n: cd0 drag thrustratio thrust fuelflow
+  // bank), the fuel burnt by the committed steps and the last step's share
+  // (fuelflow x simdt, committed by the next step's launch)
+  DevBuf s_ftab, s_fmass, s_fout, s_fused, s_fpend;
+  DevBuf f_const;  // perf::ForceConst, computed once per context
+  bool sim_forces = false;
   // NORESO / RESOOFF membership (bsa_sim_set_reso_lists, u8 in home order) and
   // the rows whose ResumeNav dropped a pair in the last CD call (u8, home order)
   DevBuf s_noreso, s_resooff, s_dropped;
@@ -497,6 +505,13 @@ struct KinDev {
 int kin_device(Ctx *c, int64_t n, double simdt, int winddim, double vn, double ve, const KinDev &d);
 struct WindField;
 WindField wind_field(const Ctx *c);  // device view of the context's 2-D field (bsa_kin.hip)
+
+// OpenAP drag / thrust / fuel flow (bsa_perf.hip).  forces_consts: Ctx::f_const
+// filled (once).  forces_sim_launch: k_sim_forces of the step about to be
+// enqueued, on this rank's rows; commit = the pending fuel of the step before
+// is added to fuel_used first (false for the first step of a re-run attempt).
+int forces_consts(Ctx *c);
+int forces_sim_launch(Ctx *c, bool commit);
 
 // ASAS bookkeeping of one CD call (bsa_asas.hip): bk_count before the gate
 // all-reduce and MVP (may raise the gate's bit 1 on resopairs overflow),

@@ -99,6 +99,16 @@ __device__ __forceinline__ double vcas2tas(double cas, double h) {
   return cas < 0 ? -1 * tas : tas;
 }
 
+// aero.py:100-104 vtas2mach, aero.py:150-154 vmach2cas (vmach2tas, then vtas2cas)
+__device__ __forceinline__ double vtas2mach(double tas, double h) {
+  const double T = npmax(288.15 - 0.0065 * h, kTstrat);
+  return tas / sqrt(kGamma * kRgas * T);
+}
+__device__ __forceinline__ double vmach2cas(double M, double h) {
+  const double T = npmax(288.15 - 0.0065 * h, kTstrat);
+  return vtas2cas(M * sqrt(kGamma * kRgas * T), h);
+}
+
 // per-aircraft OpenAP flight envelope (perfoap.py:185-209; vmin / vmax are CAS)
 struct Envelope {
   double hmax, vmin, vmax, vsmin, vsmax, axmax;

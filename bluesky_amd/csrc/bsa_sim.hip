@@ -23,6 +23,7 @@
 
 #include "bsa_kin_math.h"
 #include "bsa_mvp_row.h"
+#include "bsa_perf_math.h"
 #include "bsa_prep.h"
 #include "bsa_sim_row.h"
 
@@ -229,7 +230,8 @@ void sim_release(Ctx *c) {
                    &c->s_apalt, &c->s_apvs, &c->s_selalt, &c->s_bank, &c->s_eps, &c->s_accel,
                    &c->s_atrk, &c->s_atas, &c->s_avs, &c->s_aalt, &c->s_ase, &c->s_asn,
                    &c->s_active, &c->g_send, &c->g_recv, &c->pg_send, &c->pg_recv, &c->sim_ctl, &c->s_altprev, &c->s_ax, &c->s_env,
-                   &c->s_ptab, &c->s_ptype, &c->s_phase, &c->s_noreso, &c->s_resooff, &c->s_dropped, &c->s_atm,
+                   &c->s_ptab, &c->s_ptype, &c->s_phase, &c->s_ftab, &c->s_fmass, &c->s_fout, &c->s_fused, &c->s_fpend,
+                   &c->f_const, &c->s_noreso, &c->s_resooff, &c->s_dropped, &c->s_atm,
                    &c->xfer_stage, &c->lbyidx, &c->fetch_stage, &c->tpr_snap, &c->tpr_ctl, &c->nx_alt, &c->nx_vs, &c->nx_gse, &c->nx_gsn};
   for (auto *b : all) release(*b);
   bk_release(c);
@@ -601,6 +603,7 @@ int bsa_sim_init(bsa_ctx *cc, int64_t n, const bsa_sim_state *s, const bsa_sim_p
   BSA_HIP(c, hipMemsetAsync(c->s_ax.p, 0, N8, c->stream));   // traf.ax: 0 at create
   c->sim_limits = false;
   c->sim_perf = false;
+  c->sim_forces = false;
   if (bsa::put_home(c, c->s_atrk.p, s->trk, 8, tmp) || bsa::put_home(c, c->s_atas.p, s->tas, 8, tmp)) return -1;
   BSA_HIP(c, hipMemsetAsync(c->s_avs.p, 0, N8, c->stream));
   BSA_HIP(c, hipMemsetAsync(c->s_ase.p, 0, (size_t)n * 4, c->stream));
@@ -659,6 +662,10 @@ int bsa_sim_step(bsa_ctx *cc, int nsteps) {
     BSA_HIP(c, hipMemsetAsync((char *)c->sim_ctl.p + bsa::kSimCtlSticky, 0, 40, c->stream));  // sticky, steps_done, demands, stale
     while (c->sim_steps < target) {
       bool cd_step = false;
+      // OpenAP drag / thrust / fuel flow of the pre-step state, first on the step's
+      // stream (bsa_perf.hip).  The first step of a re-run attempt does not commit
+      // the pending fuel: it is the aborted step's own
+      if (c->sim_forces && bsa::forces_sim_launch(c, !(attempt > 0 && c->sim_steps == base))) return -1;
       if (c->sim_steps % c->simp.cd_every == 0) {
         // one rank: K2 and this step's K4' as one launch (k24_launch below;
         // BSA_K24=0 off) -- K4' then starts on each workgroup's rows as soon as
@@ -838,6 +845,7 @@ int bsa_sim_set_perf(bsa_ctx *cc, int64_t ntypes, const double *table, const int
   if (!c) return -1;
   if (!c->sim_ready) return bsa::fail(c, "bsa_sim_set_perf before bsa_sim_init");
   BSA_HIP(c, hipSetDevice(c->device));
+  c->sim_forces = false;  // the force table goes with the type table: bsa_sim_set_forces again
   if (!table) {
     c->sim_perf = false;
     return 0;
@@ -877,6 +885,78 @@ int bsa_sim_read_perf(bsa_ctx *cc, uint8_t *phase, double *ax) {
     if (bsa::get_home(c, phase, c->s_phase.p, 1, c->sim_rb, c->sim_re, tmp)) return -1;
   }
   if (ax && bsa::get_home(c, ax, c->s_ax.p, 8, c->sim_rb, c->sim_re, tmp)) return -1;
+  return 0;
+}
+
+int bsa_sim_set_forces(bsa_ctx *cc, int64_t ntypes, const double *ftable, const double *mass) {
+  Ctx *c = (Ctx *)cc;
+  if (!c) return -1;
+  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_set_forces before bsa_sim_init");
+  BSA_HIP(c, hipSetDevice(c->device));
+  if (!ftable) {
+    c->sim_forces = false;
+    return 0;
+  }
+  if (!c->sim_perf) return bsa::fail(c, "bsa_sim_set_forces needs the type table and index of bsa_sim_set_perf");
+  if (!mass) return bsa::fail(c, "bsa_sim_set_forces: NULL mass");
+  if (ntypes != c->sim_ntypes)
+    return bsa::fail(c, "bsa_sim_set_forces: %lld force-table rows for the %lld types of bsa_sim_set_perf",
+                     (long long)ntypes, (long long)c->sim_ntypes);
+  if (ntypes > bsa::perf::kForceTypesMax)
+    return bsa::fail(c, "bsa_sim_set_forces: %lld types, at most %d", (long long)ntypes, bsa::perf::kForceTypesMax);
+  // thr0 = engnum x engthrust divides the thrust ratio of every fixed wing
+  std::vector<double> tab24((size_t)ntypes * bsa::kin::kPerfCols);
+  BSA_HIP(c, hipMemcpyAsync(tab24.data(), c->s_ptab.p, tab24.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  BSA_HIP(c, hipStreamSynchronize(c->stream));
+  for (int64_t t = 0; t < ntypes; ++t) {
+    const double thr0 = ftable[t * bsa::perf::kForceCols + 1] * ftable[t * bsa::perf::kForceCols + 2];
+    if (tab24[(size_t)t * bsa::kin::kPerfCols + 22] == 1.0 && !std::isfinite(thr0))
+      return bsa::fail(c, "type %lld: engnum x engthrust is not finite", (long long)t);
+  }
+  const int64_t n = c->n;
+  const size_t N8 = (size_t)n * 8;
+  if (!bsa::ensure(c, c->s_ftab, (size_t)ntypes * bsa::perf::kForceCols * 8, "OpenAP force table") ||
+      !bsa::ensure(c, c->s_fmass, N8, "mass") || !bsa::ensure(c, c->s_fout, 6 * N8, "OpenAP forces") ||
+      !bsa::ensure(c, c->s_fused, N8, "fuel used") || !bsa::ensure(c, c->s_fpend, N8, "pending fuel"))
+    return -1;
+  if (bsa::forces_consts(c)) return -1;
+  BSA_HIP(c, hipMemcpyAsync(c->s_ftab.p, ftable, (size_t)ntypes * bsa::perf::kForceCols * 8, hipMemcpyHostToDevice,
+                            c->stream));
+  std::vector<char> tmp;
+  if (bsa::put_home(c, c->s_fmass.p, mass, 8, tmp)) return -1;
+  // switching on: outputs (perf.bank among them) and the fuel accumulators start at 0
+  BSA_HIP(c, hipMemsetAsync(c->s_fout.p, 0, 6 * N8, c->stream));
+  BSA_HIP(c, hipMemsetAsync(c->s_fused.p, 0, N8, c->stream));
+  BSA_HIP(c, hipMemsetAsync(c->s_fpend.p, 0, N8, c->stream));
+  BSA_HIP(c, hipStreamSynchronize(c->stream));
+  c->sim_forces = true;
+  return 0;
+}
+
+int bsa_sim_read_forces(bsa_ctx *cc, double *cd0, double *drag, double *thrustratio, double *thrust,
+                        double *fuelflow, double *bank, double *fuel_used) {
+  Ctx *c = (Ctx *)cc;
+  if (!c) return -1;
+  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_read_forces before bsa_sim_init");
+  if (!c->sim_forces) return bsa::fail(c, "no forces: bsa_sim_set_forces is off");
+  BSA_HIP(c, hipSetDevice(c->device));
+  const int64_t n = c->n, rb = c->sim_rb, re = c->sim_re;
+  std::vector<char> tmp;
+  double *dst[6] = {cd0, drag, thrustratio, thrust, fuelflow, bank};
+  for (int k = 0; k < 6; ++k)
+    if (dst[k] && bsa::get_home(c, dst[k], (const double *)c->s_fout.p + (size_t)k * n, 8, rb, re, tmp)) return -1;
+  if (fuel_used && re > rb) {
+    // the committed steps + the last completed step's share, added here as the
+    // next step's launch will add it (one fp64 add: the same bits)
+    std::vector<double> pend((size_t)n, 0.0);
+    if (bsa::get_home(c, fuel_used, c->s_fused.p, 8, rb, re, tmp) ||
+        bsa::get_home(c, pend.data(), c->s_fpend.p, 8, rb, re, tmp))
+      return -1;
+    for (int64_t h = rb; h < re; ++h) {
+      const unsigned i = c->h2id_h[(size_t)h];
+      fuel_used[i] = fuel_used[i] + pend[i];
+    }
+  }
   return 0;
 }
 

@@ -83,6 +83,12 @@ static std::vector<PerAc> per_aircraft(Ctx *c) {
     v.push_back({&c->s_ptype, 4, 1});
     v.push_back({&c->s_phase, 1, 1});
   }
+  if (c->sim_forces) {  // mass, the six outputs, fuel burnt and the last step's pending share
+    v.push_back({&c->s_fmass, 8, 1});
+    v.push_back({&c->s_fout, 8, 6});
+    v.push_back({&c->s_fused, 8, 1});
+    v.push_back({&c->s_fpend, 8, 1});
+  }
   return v;
 }
 

@@ -117,6 +117,17 @@ class ResidentSim:
         """(flight phase of the last step, traf.ax) of this rank's rows."""
         return self.ctx.sim_read_perf()
 
+    def set_forces(self, ftable=None, mass=None):
+        """The drag / thrust / fuel-flow half of OpenAP.update in every step, and
+        the fuel burnt per aircraft (bsa_sim_set_forces; needs ``set_perf``;
+        bluesky_amd.perf.force_table builds ``ftable`` / ``mass``); None switches it off."""
+        self.ctx.sim_set_forces(ftable, mass)
+
+    def read_forces(self):
+        """dict of cd0, drag, thrustratio, thrust, fuelflow, bank of the last step
+        and fuel_used [kg] so far, of this rank's rows."""
+        return self.ctx.sim_read_forces()
+
     def create(self, state):
         """Append aircraft (Traffic.create; ``state`` as ``initial_state`` returns,
         m long each): indices n..n+m-1 (bsa_sim_create; collective with several ranks)."""

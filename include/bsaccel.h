@@ -449,6 +449,41 @@ int bsa_sim_set_perf(bsa_ctx *ctx, int64_t ntypes, const double *table, const in
  * (0..8, phase.py:4-12; needs bsa_sim_set_perf) and of traf.ax, written into
  * full-n host arrays; either pointer may be NULL. */
 int bsa_sim_read_perf(bsa_ctx *ctx, uint8_t *phase, double *ax);
+/* The second half of OpenAP.update (perfoap.py:133-173): zero-lift drag
+ * coefficient by flight phase, drag (fixed wing: rhovs (cd0 + k cl^2); tas == 0
+ * gives NaN as numpy does), thrust ratio (thrust.py:5-129: take-off, in-flight
+ * by altitude segment, 15 % of it in descent, else 0), thrust, fuel flow
+ * engnum (a tr^2 + b tr + c) [kg/s] and the model's own bank limit (15 deg in
+ * TO / LD, 35 in IC / CR / AP, else unchanged; it does not feed traf.bank).
+ * Rotors and lift type 0 keep the reference's zeros (cd0 = cd0_clean).
+ * table: the ntypes x 24 type table of bsa_sim_set_perf; ftable: ntypes rows
+ * of 16 doubles -- Sref, engnum, engthrust, engbpr, ff_a, ff_b, ff_c,
+ * cd0_clean, cd0_gd, cd0_to, cd0_ic, cd0_ap, cd0_ld, k, default mass, 0
+ * (bluesky_amd/perf.py force_table builds it; ntypes <= 384); type_idx: row
+ * per aircraft; phase: 0..8 per aircraft (phase.py:4-12), or NULL to derive
+ * it from vs / alt as the step does; mass [kg], tas, vs, alt: length n.
+ * Outputs: length n; bank holds the previous perf.bank on entry. */
+int bsa_openap_forces(bsa_ctx *ctx, int64_t n, int64_t ntypes, const double *table, const double *ftable,
+                      const int32_t *type_idx, const uint8_t *phase, const double *mass, const double *tas,
+                      const double *vs, const double *alt, double *cd0, double *drag, double *thrustratio,
+                      double *thrust, double *fuelflow, double *bank);
+/* The same inside the resident step, on the pre-step state (OpenAP.update runs
+ * before the pilot and the kinematics, traffic.py:397-404), in a launch of its
+ * own at the start of every step; nothing in the step reads its outputs.
+ * Needs bsa_sim_set_perf (its type index and lift types; ntypes must be its
+ * row count, engnum x engthrust finite for fixed wings); mass: full-n host
+ * array [kg], constant as in the reference.  Switching on zeroes the outputs,
+ * perf.bank and the fuel burnt.  ftable == NULL switches it off (the default),
+ * and so does every bsa_sim_set_perf call.  bsa_sim_delete carries the arrays
+ * along; bsa_sim_create stays refused while bsa_sim_set_perf is on.
+ * Fuel burnt (an extension, not in the reference): per aircraft, the sum over
+ * the completed steps, in step order, of that step's fuelflow x simdt [kg] --
+ * exact through aborted and re-run steps (each step counted once). */
+int bsa_sim_set_forces(bsa_ctx *ctx, int64_t ntypes, const double *ftable, const double *mass);
+/* This rank's rows of the last step's outputs and of the fuel burnt, into
+ * full-n host arrays (rows as bsa_sim_row_ids); any pointer may be NULL. */
+int bsa_sim_read_forces(bsa_ctx *ctx, double *cd0, double *drag, double *thrustratio, double *thrust,
+                        double *fuelflow, double *bank, double *fuel_used);
 /* Traffic.update's atmosphere, traf.p / rho / Temp = vatmos(traf.alt) on the
  * pre-step altitude (traffic.py:389, aero.py:62-74), computed inside the step
  * when on (off after bsa_sim_init: nothing in the step reads them; a host

@@ -482,6 +482,148 @@ def run_perf(name, n, seed):
     print('perf_%-16s N=%5d phases %s' % (name, n, np.unique(ph)))
 
 
+ENGINE_FIELDS = ('thr', 'bpr', 'ff_idl', 'ff_app', 'ff_co', 'ff_to')
+POLAR_FIELDS = ('cd0_clean', 'cd0_gd', 'cd0_to', 'cd0_ic', 'cd0_ap', 'cd0_ld', 'k')
+
+
+def run_forces(name, n, seed):
+    """The drag / thrust / fuel-flow half of OpenAP.update (perfoap.py:133-173):
+    the reference's own lines, taken from the source of ``OpenAP.update`` at run
+    time and executed on an OpenAP instance made without __init__, with
+    thrust.compute_thrust_ratio / compute_eng_ff_coeff and the reference's
+    Coefficient tables.  All nine phases are given explicitly (phase.get never
+    produces TO / LD).  tests/openap_forces_np.py is asserted bitwise equal."""
+    import inspect
+    import textwrap
+    import bluesky as bs
+    from bluesky.tools import aero
+    from bluesky.traffic.performance.openap import coeff as refcoeff
+    from bluesky.traffic.performance.openap import phase as refphase
+    from bluesky.traffic.performance.openap import thrust as refthrust
+    from bluesky.traffic.performance.openap.perfoap import OpenAP
+    from bluesky_amd import perf as bperf
+    from tests import openap_forces_np as fnp
+    cwd = os.getcwd()
+    os.chdir(REF)
+    try:
+        C = refcoeff.Coefficient()
+    finally:
+        os.chdir(cwd)
+    # every type of limits_fixwing that OpenAP.create keeps: one without an engine in the
+    # engine table becomes an A320 there (perfoap.py:70-72) and never reaches perf.actypes
+    wing = sorted(m for m in C.limits_fixwing if C.acs_fixwing[m]['engines'])
+    print('forces: %d of %d fixed-wing types (no engine: %s)' % (
+        len(wing), len(C.limits_fixwing), sorted(set(C.limits_fixwing) - set(wing))))
+    rot = sorted(k for k in C.limits_rotor if k in C.acs_rotor)[:3]
+    rng = np.random.default_rng(seed)
+    names = np.array(wing + rot)
+    actypes = names[rng.integers(0, len(names), n)]
+    actypes[:len(names)] = names                      # every type at least once
+    lifttype = np.where(np.isin(actypes, rot), refcoeff.LIFT_ROTOR, refcoeff.LIFT_FIXWING)
+    alt = rng.uniform(-30., 12500., n)
+    vs = rng.uniform(-25., 25., n)
+    tas = rng.uniform(0., 280., n)
+    phase = rng.integers(0, 9, n).astype(np.float64)  # explicit: TO and LD too
+    k = n // 3
+    q = np.arange(k, 2 * k)
+    tas[q] = rng.choice([0.0, 5.0, 10.0, 10.5, 60.0, 150.0, 240.0], k)
+    alt[q] = rng.choice(np.array([0.0, 10000., 35000., 9999., 34999., 36000., 39000.]) * ft, k)
+    up = rng.random(k) < 0.4
+    alt[q] = np.where(up, np.nextafter(alt[q], np.inf), alt[q])    # ... and just above the segment edges
+    vs[q] = rng.choice(np.array([-2500., -1500., 0., 1499., 1500., 2500., 2600.]), k) * fpm
+    fwm =lifttype == refcoeff.LIFT_FIXWING
+    assert (alt == 10000 * ft).any() and (alt == 35000 * ft).any() and (alt == np.nextafter(35000 * ft, np.inf)).any()
+    assert set(np.unique(phase[fwm])) == set(range(9))
+    for v in (0.0, 5.0, 10.0):
+        assert (tas[fwm] == v).any()
+    # per-aircraft parameters by OpenAP.create's lookups (perfoap.py:56-109), restated on the
+    # reference's tables with its own fuel-flow fit; per-type copies go into the file
+    par = {c: np.zeros(n) for c in fnp.COLS}
+    par['engnum'] = np.zeros(n, dtype=int)
+    raw = {'ac_' + f: [] for f in ('wa', 'oew', 'mtow', 'n_engines')}
+    raw.update({'eng_' + f: [] for f in ENGINE_FIELDS})
+    raw.update({'dp_' + f: [] for f in POLAR_FIELDS})
+    raw['dp_known'] = []
+    tpar = {c: [] for c in fnp.COLS}
+    for mdl in wing:
+        ac = C.acs_fixwing[mdl]
+        es = ac['engines']
+        e = es[list(es.keys())[0]]
+        a, b, c = refthrust.compute_eng_ff_coeff(e['ff_idl'], e['ff_app'], e['ff_co'], e['ff_to'])
+        known = mdl in C.dragpolar_fixwing.keys()
+        dp = C.dragpolar_fixwing[mdl] if known else C.dragpolar_fixwing['NA']
+        vals = dict(Sref=ac['wa'], engnum=int(ac['n_engines']), engthrust=e['thr'], engbpr=e['bpr'], ff_a=a,
+                    ff_b=b, ff_c=c, mass=0.5 * (ac['oew'] + ac['mtow']), **{f: dp[f] for f in POLAR_FIELDS})
+        m = actypes == mdl
+        for cname, v in vals.items():
+            par[cname][m] = v
+            tpar[cname].append(v)
+        for f in ('wa', 'oew', 'mtow', 'n_engines'):
+            raw['ac_' + f].append(ac[f])
+        for f in ENGINE_FIELDS:
+            raw['eng_' + f].append(e[f])
+        for f in POLAR_FIELDS:
+            raw['dp_' + f].append(dp[f])
+        raw['dp_known'].append(known)
+    for mdl in rot:
+        ac = C.acs_rotor[mdl]
+        m = actypes == mdl
+        par['mass'][m] = 0.5 * (ac['oew'] + ac['mtow'])
+        par['engnum'][m] = int(ac['n_engines'])
+    mass = par['mass'] * rng.choice([1.0, 0.8, 1.15], n)       # a per-aircraft mass, not the default only
+    bank0 = rng.choice([0.0, 15.0, 25.0, 35.0], n)
+    perf = OpenAP.__new__(OpenAP)
+    for cname in fnp.COLS[:-1]:
+        attr = {'ff_a': 'ff_coeff_a', 'ff_b': 'ff_coeff_b', 'ff_c': 'ff_coeff_c'}.get(cname, cname)
+        object.__setattr__(perf, attr, par[cname].copy())
+    for attr, v in (('lifttype', lifttype), ('phase', phase), ('mass', mass.copy()), ('cd0', np.zeros(n)),
+                    ('drag', np.zeros(n)), ('thrust', np.zeros(n)), ('thrustratio', np.zeros(n)),
+                    ('fuelflow', np.zeros(n)), ('bank', bank0.copy())):
+        object.__setattr__(perf, attr, v)
+    # the reference's own lines, from `idx_fixwing = ...` to the second bank line of OpenAP.update
+    lines = inspect.getsource(OpenAP.update).splitlines()
+    first = next(i for i, s in enumerate(lines) if 'idx_fixwing = np.where' in s)
+    last = max(i for i, s in enumerate(lines) if s.strip().startswith('self.bank = np.where'))
+    body = textwrap.dedent('\n'.join(lines[first:last + 1]))
+    assert 'self.fuelflow' in body and 'self.drag[idx_fixwing]' in body and 'compute_thrust_ratio' in body
+    saved = getattr(bs, 'traf', None)
+    bs.traf = types.SimpleNamespace(ntraf=n, tas=tas.copy(), vs=vs.copy(), alt=alt.copy())
+    try:
+        with np.errstate(all='ignore'):
+            exec(compile(body, 'OpenAP.update[drag..bank]', 'exec'),
+                 dict(np=np, bs=bs, aero=aero, coeff=refcoeff, thrust=refthrust, ph=refphase, self=perf))
+    finally:
+        bs.traf = saved
+    ref = {o: np.asarray(getattr(perf, o), dtype=np.float64) for o in fnp.OUTPUTS}
+    mine = fnp.forces({c: par[c] for c in fnp.COLS[:-1]}, lifttype, phase, mass, tas, vs, alt, bank0)
+    for o in fnp.OUTPUTS:
+        assert np.array_equal(mine[o], ref[o], equal_nan=True), 'helper != reference forces %s' % o
+    assert np.isnan(ref['drag'][fwm & (tas == 0.0)]).all()      # the tas == 0 quirk is in the file
+    # breakpoints of dfunc / mfunc: no row may sit within 1e-9 of one (the mask is stored anyway)
+    near = fnp.near_breakpoint(tas, alt) & fwm
+    assert not near.any(), '%d rows within 1e-9 of a dfunc / mfunc breakpoint' % near.sum()
+    # the product's table builder on the reference's Coefficient object, and through it the helper
+    ftable, dmass = bperf.force_table(C, actypes, lifttype)
+    table24, tidx = bperf.type_table(C.limits_fixwing, C.limits_rotor, actypes, lifttype)
+    assert np.array_equal(dmass, par['mass'])
+    viat = fnp.forces_table(ftable, table24, tidx, phase, mass, tas, vs, alt, bank0)
+    for o in fnp.OUTPUTS:
+        ok = np.isclose(viat[o], ref[o], rtol=1e-12, atol=0, equal_nan=True)
+        assert ok.all(), 'force_table route != reference %s' % o
+    out = dict(actypes=actypes, lifttype=lifttype, phase=phase, mass=mass, tas=tas, vs=vs, alt=alt, bank0=bank0,
+               near_break=near, fw_types=np.array(wing), rot_types=np.array(rot),
+               rot_mass=np.array([0.5 * (C.acs_rotor[m]['oew'] + C.acs_rotor[m]['mtow']) for m in rot]),
+               rot_engnum=np.array([int(C.acs_rotor[m]['n_engines']) for m in rot]))
+    out.update({kk: np.array(v) for kk, v in raw.items()})
+    out.update({'par_' + c: np.array(v, dtype=np.float64) for c, v in tpar.items()})
+    out.update({'out_' + o: ref[o] for o in fnp.OUTPUTS})
+    path = os.path.join(OUT, 'perf_%s.npz' % name)
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) < 1000000
+    print('perf_%-16s N=%5d fixed wing %d, NaN drag rows %d, %d bytes'
+          % (name, n, fwm.sum(), np.isnan(ref['drag']).sum(), os.path.getsize(path)))
+
+
 def run_asas(name, traf, ncalls=4, dt=20.0):
     """Reference ASAS.update (asas.py:473-504) incl. ResumeNav on a stand-in
     bs.traf; state advanced along straight tracks between CD calls."""
@@ -621,6 +763,9 @@ def main():
     if '--perf-only' in sys.argv:
         run_perf('openap3000', 3000, 73)
         return
+    if '--forces-only' in sys.argv:
+        run_forces('forces3000', 3000, 75)
+        return
     if '--windfield-only' in sys.argv:
         run_kin('windfield1500', 1500, 34, 0.05, wind=WIND_FIELD)
         return
@@ -649,6 +794,7 @@ def main():
     run_kin('windfield1500', 1500, 34, 0.05, wind=WIND_FIELD)
     run_limits('openap2000', 2000, 71)
     run_perf('openap3000', 3000, 73)
+    run_forces('forces3000', 3000, 75)
     for case in geo_cases():
         run_geo(*case)
 

@@ -6,8 +6,9 @@ steps (one host synchronisation at its end, no stage events) after SETTLE
 untimed ones (the device at steady clocks, as bench.py's --settle).  Collectives
 (box all-gather, halo send / recv, gate all-reduce) are excluded: they need
 the 8-GPU node.  Prints every rank's ms per step and the slowest.
-Usage: python tools/probe_step.py [WORKLOAD [R [STEPS [RANK [SETTLE]]]]]  (RANK: that rank of R
-only, -1 all; SETTLE default 200)"""
+Usage: python tools/probe_step.py [WORKLOAD [R [STEPS [RANK [SETTLE]]]]] [--perf | --forces]  (RANK:
+that rank of R only, -1 all; SETTLE default 200; --perf: OpenAP phase / envelope in the step,
+--forces: also its drag / thrust / fuel-flow launch)"""
 import json
 import os
 import sys
@@ -17,7 +18,27 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bluesky_amd import _lib, resident, synth  # noqa: E402
 
 
+def openap_tables(n, seed=5):
+    """Type table, type index, force table and mass for n aircraft of random
+    OpenAP types, from the reference's coefficients as the goldens hold them."""
+    import numpy as np
+    from bluesky_amd import perf
+    from tests.test_perf_forces_cpu import load as load_forces
+    from tests.test_perf_oracle import load as load_perf
+    g, coeff = load_forces()
+    _, fw, rot = load_perf()
+    types = np.array([str(m) for m in g['fw_types']] + sorted(rot))
+    actypes = types[np.random.default_rng(seed).integers(0, len(types), n)]
+    lifttype = np.where(np.isin(actypes, sorted(rot)), perf.LIFT_ROTOR, perf.LIFT_FIXWING)
+    return perf.type_table(fw, rot, actypes, lifttype) + perf.force_table(coeff, actypes, lifttype)
+
+
 def main():
+    # --perf: OpenAP phase / envelope in the step (bsa_sim_set_perf); --forces: also its drag /
+    # thrust / fuel flow launch (bsa_sim_set_forces) -- its cost is --forces against --perf
+    forces = '--forces' in sys.argv
+    with_perf = forces or '--perf' in sys.argv
+    sys.argv = [a for a in sys.argv if a not in ('--forces', '--perf')]
     name = sys.argv[1] if len(sys.argv) > 1 else 'global1m'
     R = int(sys.argv[2]) if len(sys.argv) > 2 else 8
     steps = int(sys.argv[3]) if len(sys.argv) > 3 else 40
@@ -27,7 +48,12 @@ def main():
     ctx = _lib.Context(0)
     ctx.set_timing_sample(0)
     sim = resident.ResidentSim(resident.initial_state(t), resident.params(cd_every=1), ctx=ctx)
-    out = {}
+    if with_perf:
+        table, tidx, ftable, mass = openap_tables(t.ntraf)
+        sim.set_perf(table, tidx)
+        if forces:
+            sim.set_forces(ftable, mass)
+    out = dict(perf=with_perf, forces=forces)
     for ranks in sorted({1, R}) if only is None else [R]:
         per = []
         for r in range(ranks) if only is None else [only]:
