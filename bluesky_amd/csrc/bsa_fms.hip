@@ -1,0 +1,251 @@
+// Autopilot LNAV / VNAV guidance and waypoint switching (Autopilot.update,
+// autopilot.py:59-203) on the device: the standalone kernel over host arrays
+// (bsa_fms_update) and the resident step's own launch (k_sim_fms,
+// bsa_sim_set_fms), one lane per aircraft, one-wave workgroups like K4'.  The
+// per-aircraft arrays are SoA; the route table (8 doubles = 64 B per
+// waypoint) stays in HBM and only a lane that switches waypoint reads its row.
+#include "bsa_fms_math.h"
+
+#pragma clang fp contract(off)
+
+namespace bsa {
+
+struct FmsArrays {
+  const double *tr[8];     // lat lon alt tas gs trk ax bank (read only)
+  double *st[kFmsReals];   // bsa_fms_state's doubles (selvs, apvsdef read only)
+  uint8_t *fl[4];          // swlnav swvnav abco belco (abco, belco read only)
+  double *tg[5];           // ap_trk ap_tas ap_alt ap_vs selalt
+  int *iactwp;
+  const int *rt_off, *rt_n;
+  const double *rows;
+};
+
+__device__ __forceinline__ fms::Lane fms_load(const FmsArrays &a, int k) {
+  fms::Lane L;
+  L.lat = a.tr[0][k], L.lon = a.tr[1][k], L.alt = a.tr[2][k], L.tas = a.tr[3][k];
+  L.gs = a.tr[4][k], L.trk = a.tr[5][k], L.ax = a.tr[6][k], L.bank = a.tr[7][k];
+  L.wlat = a.st[0][k], L.wlon = a.st[1][k], L.nextaltco = a.st[2][k], L.xtoalt = a.st[3][k];
+  L.spd = a.st[4][k], L.vs = a.st[5][k], L.turndist = a.st[6][k], L.flyby = a.st[7][k];
+  L.next_qdr = a.st[8][k], L.dist2vs = a.st[9][k], L.vnavvs = a.st[10][k], L.swvnavvs = a.st[11][k];
+  L.selspd = a.st[12][k], L.selvs = a.st[13][k], L.apvsdef = a.st[14][k];
+  L.swlnav = a.fl[0][k] != 0, L.swvnav = a.fl[1][k] != 0, L.abco = a.fl[2][k] != 0, L.belco = a.fl[3][k] != 0;
+  L.ap_trk = a.tg[0][k], L.ap_alt = a.tg[2][k], L.ap_vs = a.tg[3][k], L.selalt = a.tg[4][k];
+  L.iactwp = a.iactwp[k];
+  return L;
+}
+
+__device__ __forceinline__ void fms_store(const FmsArrays &a, int k, const fms::Lane &L) {
+  a.st[0][k] = L.wlat, a.st[1][k] = L.wlon, a.st[2][k] = L.nextaltco, a.st[3][k] = L.xtoalt;
+  a.st[4][k] = L.spd, a.st[5][k] = L.vs, a.st[6][k] = L.turndist, a.st[7][k] = L.flyby;
+  a.st[8][k] = L.next_qdr, a.st[9][k] = L.dist2vs, a.st[10][k] = L.vnavvs, a.st[11][k] = L.swvnavvs;
+  a.st[12][k] = L.selspd;
+  a.fl[0][k] = L.swlnav ? 1 : 0, a.fl[1][k] = L.swvnav ? 1 : 0;
+  a.tg[0][k] = L.ap_trk, a.tg[2][k] = L.ap_alt, a.tg[3][k] = L.ap_vs, a.tg[4][k] = L.selalt;
+  a.iactwp[k] = L.iactwp;
+}
+
+// One full Autopilot.update call (forced tick) for aircraft [0, n)
+__global__ __launch_bounds__(64) void k_fms_update(int n, FmsArrays a) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  fms::Lane L = fms_load(a, k);
+  fms::tick(L, a.rows, a.rt_off[k], a.rt_n[k]);
+  fms_store(a, k, L);
+  a.tg[1][k] = fms::vcasormach2tas(L.selspd, L.alt);   // ap.tas, autopilot.py:203
+}
+
+// The undo set of a ticking launch: what the tick may overwrite, as it was at
+// the step's start
+struct FmsUndo {
+  double *r;    // 17 x n: st[0 .. 12], ap_trk, ap_alt, ap_vs, selalt
+  uint8_t *f;   // 2 x n: swlnav, swvnav
+  int *iactwp;  // n
+  int n;
+};
+
+// The resident step's launch, first on the step's stream: rows [rb, re) of the
+// PRE-step state (ap.update is the first call of Traffic.update,
+// traffic.py:395).  TICK: the FMS part, after the lane has copied what it may
+// overwrite into the undo set; always ap.tas (autopilot.py:203).  Behind the
+// batch's sticky abort word it changes nothing.
+template <bool TICK>
+__global__ __launch_bounds__(64) void k_sim_fms(int rb, int re, FmsArrays a, FmsUndo u,
+                                                const unsigned *__restrict__ sticky) {
+  if (*sticky != 0u) return;
+  const int k = rb + blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= re) return;
+  if (TICK) {
+    fms::Lane L = fms_load(a, k);
+    const size_t n = (size_t)u.n;
+    const double keep[kFmsUndoReals] = {L.wlat, L.wlon, L.nextaltco, L.xtoalt, L.spd, L.vs, L.turndist, L.flyby,
+                                        L.next_qdr, L.dist2vs, L.vnavvs, L.swvnavvs, L.selspd, L.ap_trk, L.ap_alt,
+                                        L.ap_vs, L.selalt};  // from the lane's own loads: st[0 .. 12], the targets
+#pragma unroll
+    for (int q = 0; q < kFmsUndoReals; ++q) u.r[q * n + k] = keep[q];
+    u.f[k] = L.swlnav ? 1 : 0, u.f[n + k] = L.swvnav ? 1 : 0;
+    u.iactwp[k] = L.iactwp;
+    fms::tick(L, a.rows, a.rt_off[k], a.rt_n[k]);
+    fms_store(a, k, L);
+    a.tg[1][k] = fms::vcasormach2tas(L.selspd, L.alt);
+  } else {
+    a.tg[1][k] = fms::vcasormach2tas(a.st[12][k], a.tr[2][k]);
+  }
+}
+
+static FmsArrays fms_sim_arrays(Ctx *c) {
+  const size_t n = (size_t)c->n;
+  FmsArrays a;
+  const void *tr[8] = {c->own[0].p, c->own[1].p, c->own[4].p, c->s_tas.p, c->own[3].p, c->own[2].p, c->s_ax.p,
+                       c->s_bank.p};  // lat lon alt tas gs trk ax bank
+  for (int q = 0; q < 8; ++q) a.tr[q] = (const double *)tr[q];
+  for (int q = 0; q < kFmsReals; ++q) a.st[q] = (double *)c->s_fmsr.p + q * n;
+  for (int q = 0; q < 4; ++q) a.fl[q] = (uint8_t *)c->s_fmsf.p + q * n;
+  void *tg[5] = {c->s_aptrk.p, c->s_aptas.p, c->s_apalt.p, c->s_apvs.p, c->s_selalt.p};
+  for (int q = 0; q < 5; ++q) a.tg[q] = (double *)tg[q];
+  a.iactwp = (int *)c->s_fmsi.p;
+  a.rt_off = (const int *)c->s_fmsi.p + n;
+  a.rt_n = (const int *)c->s_fmsi.p + 2 * n;
+  a.rows = (const double *)c->s_fmsrows.p;
+  return a;
+}
+
+int fms_sim_launch(Ctx *c, bool tick) {
+  const int64_t rb = c->sim_rb, re = c->sim_re;
+  if (re <= rb) return 0;
+  const FmsArrays a = fms_sim_arrays(c);
+  const FmsUndo u{(double *)c->s_fmsur.p, (uint8_t *)c->s_fmsuf.p, (int *)c->s_fmsui.p, (int)c->n};
+  const auto K = tick ? k_sim_fms<true> : k_sim_fms<false>;
+  hipLaunchKernelGGL(K, dim3((unsigned)((re - rb + 63) / 64)), dim3(64), 0, c->stream, (int)rb, (int)re, a, u,
+                     (const unsigned *)((const char *)c->sim_ctl.p + kSimCtlSticky));
+  BSA_HIP(c, hipGetLastError());
+  return 0;
+}
+
+int fms_sim_restore(Ctx *c) {
+  const int64_t rb = c->sim_rb, re = c->sim_re;
+  if (re <= rb) return 0;
+  const size_t n = (size_t)c->n, m = (size_t)(re - rb);
+  const FmsArrays a = fms_sim_arrays(c);
+  const double *ur = (const double *)c->s_fmsur.p;
+  for (int q = 0; q < kFmsMutable; ++q)
+    BSA_HIP(c, hipMemcpyAsync(a.st[q] + rb, ur + q * n + rb, m * 8, hipMemcpyDeviceToDevice, c->stream));
+  const int tg[4] = {0, 2, 3, 4};
+  for (int q = 0; q < 4; ++q)
+    BSA_HIP(c, hipMemcpyAsync(a.tg[tg[q]] + rb, ur + (kFmsMutable + q) * n + rb, m * 8, hipMemcpyDeviceToDevice, c->stream));
+  for (int q = 0; q < 2; ++q)
+    BSA_HIP(c, hipMemcpyAsync(a.fl[q] + rb, (const uint8_t *)c->s_fmsuf.p + q * n + rb, m, hipMemcpyDeviceToDevice,
+                              c->stream));
+  BSA_HIP(c, hipMemcpyAsync(a.iactwp + rb, (const int *)c->s_fmsui.p + rb, m * 4, hipMemcpyDeviceToDevice, c->stream));
+  return 0;
+}
+
+// Every index the kernel uses unguarded, checked on the host: each aircraft's
+// rows inside the table, its active waypoint inside its route, and no LNAV
+// without a route (only an aircraft with LNAV on ever reads a row).
+int fms_check_routes(Ctx *c, const char *who, int64_t n, int64_t nrows, const int32_t *rt_off, const int32_t *rt_n,
+                     const int32_t *iactwp, const uint8_t *swlnav) {
+  for (int64_t k = 0; k < n; ++k) {
+    const int64_t off = rt_off[k], m = rt_n[k];
+    if (off < 0 || m < 0 || off + m > nrows)
+      return fail(c, "%s: aircraft %lld: route rows [%lld, %lld) outside the table's %lld", who, (long long)k,
+                  (long long)off, (long long)(off + m), (long long)nrows);
+    if (m == 0) {
+      if (swlnav[k]) return fail(c, "%s: aircraft %lld: LNAV on without a route", who, (long long)k);
+      if (iactwp[k] != -1 && iactwp[k] != 0)
+        return fail(c, "%s: aircraft %lld: active waypoint %d without a route (-1 or 0)", who, (long long)k, iactwp[k]);
+    } else if (iactwp[k] < 0 || iactwp[k] >= m) {
+      return fail(c, "%s: aircraft %lld: active waypoint %d outside [0, %lld)", who, (long long)k, iactwp[k],
+                  (long long)m);
+    }
+  }
+  return 0;
+}
+
+}  // namespace bsa
+
+using bsa::Ctx;
+
+extern "C" int bsa_fms_update(bsa_ctx *cc, int64_t n, int64_t nrows, const double *route_rows, const int32_t *rt_off,
+                              const int32_t *rt_n, int32_t *iactwp, const double *lat, const double *lon,
+                              const double *alt, const double *tas, const double *gs, const double *trk,
+                              const double *ax, const double *bank, const bsa_fms_state *st, double *ap_trk,
+                              double *ap_tas, double *ap_alt, double *ap_vs, double *selalt) {
+  Ctx *c = (Ctx *)cc;
+  if (!c) return -1;
+  if (n < 0 || n > 0x7fffffff) return bsa::fail(c, "bsa_fms_update: bad n");
+  if (nrows < 0 || nrows > 0x7fffffff / bsa::fms::kRouteCols) return bsa::fail(c, "bsa_fms_update: bad route row count");
+  if (!st) return bsa::fail(c, "bsa_fms_update: NULL state");
+  const double *tr[8] = {lat, lon, alt, tas, gs, trk, ax, bank};
+  double *reals[bsa::kFmsReals] = {st->actwp_lat, st->actwp_lon, st->actwp_nextaltco, st->actwp_xtoalt,
+                                   st->actwp_spd, st->actwp_vs, st->actwp_turndist, st->actwp_flyby,
+                                   st->actwp_next_qdr, st->dist2vs, st->vnavvs, st->swvnavvs,
+                                   st->selspd, st->selvs, st->apvsdef};
+  uint8_t *flags[4] = {st->swlnav, st->swvnav, st->abco, st->belco};
+  double *tg[5] = {ap_trk, ap_tas, ap_alt, ap_vs, selalt};
+  for (auto q : tr)
+    if (!q) return bsa::fail(c, "bsa_fms_update: NULL array");
+  for (auto q : reals)
+    if (!q) return bsa::fail(c, "bsa_fms_update: NULL array");
+  for (auto q : flags)
+    if (!q) return bsa::fail(c, "bsa_fms_update: NULL array");
+  for (auto q : tg)
+    if (!q) return bsa::fail(c, "bsa_fms_update: NULL array");
+  if (!rt_off || !rt_n || !iactwp || (nrows > 0 && !route_rows)) return bsa::fail(c, "bsa_fms_update: NULL array");
+  if (bsa::fms_check_routes(c, "bsa_fms_update", n, nrows, rt_off, rt_n, iactwp, st->swlnav)) return -1;
+  if (n == 0) return 0;
+  BSA_HIP(c, hipSetDevice(c->device));
+  // one device block: 8 + 15 + 5 fp64 arrays, 3 int32, 4 uint8, the route table
+  const size_t N8 = ((size_t)n * 8 + 255) / 256 * 256, N4 = ((size_t)n * 4 + 255) / 256 * 256,
+               N1 = ((size_t)n + 255) / 256 * 256;
+  const size_t rb = (size_t)nrows * bsa::fms::kRouteCols * 8;
+  constexpr int kD = 8 + bsa::kFmsReals + 5;
+  bsa::DevBuf buf;
+  struct Rel {
+    bsa::DevBuf *b;
+    ~Rel() { bsa::release(*b); }
+  } rel{&buf};
+  if (!bsa::ensure(c, buf, kD * N8 + 3 * N4 + 4 * N1 + rb + 256, "FMS staging")) return -1;
+  char *base = (char *)buf.p;
+  bsa::FmsArrays a;
+  double *d8[kD];
+  for (int q = 0; q < kD; ++q) d8[q] = (double *)(base + (size_t)q * N8);
+  int *d4[3];
+  for (int q = 0; q < 3; ++q) d4[q] = (int *)(base + kD * N8 + (size_t)q * N4);
+  uint8_t *d1[4];
+  for (int q = 0; q < 4; ++q) d1[q] = (uint8_t *)(base + kD * N8 + 3 * N4 + (size_t)q * N1);
+  double *drows = (double *)(base + kD * N8 + 3 * N4 + 4 * N1);
+  for (int q = 0; q < 8; ++q) {
+    BSA_HIP(c, hipMemcpyAsync(d8[q], tr[q], (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    a.tr[q] = d8[q];
+  }
+  for (int q = 0; q < bsa::kFmsReals; ++q) {
+    BSA_HIP(c, hipMemcpyAsync(d8[8 + q], reals[q], (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    a.st[q] = d8[8 + q];
+  }
+  for (int q = 0; q < 5; ++q) {
+    BSA_HIP(c, hipMemcpyAsync(d8[8 + bsa::kFmsReals + q], tg[q], (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    a.tg[q] = d8[8 + bsa::kFmsReals + q];
+  }
+  const int32_t *h4[3] = {iactwp, rt_off, rt_n};
+  for (int q = 0; q < 3; ++q)
+    BSA_HIP(c, hipMemcpyAsync(d4[q], h4[q], (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  for (int q = 0; q < 4; ++q) {
+    BSA_HIP(c, hipMemcpyAsync(d1[q], flags[q], (size_t)n, hipMemcpyHostToDevice, c->stream));
+    a.fl[q] = d1[q];
+  }
+  if (rb) BSA_HIP(c, hipMemcpyAsync(drows, route_rows, rb, hipMemcpyHostToDevice, c->stream));
+  a.iactwp = d4[0];
+  a.rt_off = d4[1];
+  a.rt_n = d4[2];
+  a.rows = drows;
+  hipLaunchKernelGGL(bsa::k_fms_update, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, (int)n, a);
+  BSA_HIP(c, hipGetLastError());
+  for (int q = 0; q < bsa::kFmsMutable; ++q)   // selvs, apvsdef are inputs only
+    BSA_HIP(c, hipMemcpyAsync(reals[q], d8[8 + q], (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  for (int q = 0; q < 5; ++q)
+    BSA_HIP(c, hipMemcpyAsync(tg[q], d8[8 + bsa::kFmsReals + q], (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  for (int q = 0; q < 2; ++q) BSA_HIP(c, hipMemcpyAsync(flags[q], d1[q], (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  BSA_HIP(c, hipMemcpyAsync(iactwp, d4[0], (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  BSA_HIP(c, hipStreamSynchronize(c->stream));
+  return 0;
+}

@@ -464,6 +464,16 @@ struct Ctx {
   DevBuf s_ftab, s_fmass, s_fout, s_fused, s_fpend;
   DevBuf f_const;  // perf::ForceConst, computed once per context
   bool sim_forces = false;
+  // Autopilot guidance in the step (bsa_sim_set_fms, bsa_fms.hip),
+  // home order: the 15 fp64 arrays of bsa_fms_state (15 x n), its 4 flags
+  // (4 x n u8), iactwp / rt_off / rt_n (3 x n int32), the route table, and the
+  // undo set a ticking launch fills first (17 x n fp64: the 13 mutable reals,
+  // ap_trk / ap_alt / ap_vs / selalt; 2 x n u8; n int32).  fms_simt: the simt of
+  // the next step; fms_t0: Autopilot.t0; fms_ticks: ticks of completed steps
+  DevBuf s_fmsr, s_fmsf, s_fmsi, s_fmsrows, s_fmsur, s_fmsuf, s_fmsui;
+  bool sim_fms = false;
+  double fms_simt = 0.0, fms_t0 = -999.0;
+  int64_t fms_ticks = 0;
   // NORESO / RESOOFF membership (bsa_sim_set_reso_lists, u8 in home order) and
   // the rows whose ResumeNav dropped a pair in the last CD call (u8, home order)
   DevBuf s_noreso, s_resooff, s_dropped;
@@ -512,6 +522,21 @@ WindField wind_field(const Ctx *c);  // device view of the context's 2-D field (
 // is added to fuel_used first (false for the first step of a re-run attempt).
 int forces_consts(Ctx *c);
 int forces_sim_launch(Ctx *c, bool commit);
+
+// Autopilot guidance (bsa_fms.hip).  fms_check_routes: every index the kernels
+// use unguarded, on host arrays.  fms_sim_launch: k_sim_fms of the step about
+// to be enqueued, on this rank's rows (tick: the whole FMS part, after saving
+// the undo set; else ap.tas only).  fms_sim_restore: the undo set back into
+// the state, stream-ordered (after an aborted tick step).
+int fms_check_routes(Ctx *c, const char *who, int64_t n, int64_t nrows, const int32_t *rt_off, const int32_t *rt_n,
+                     const int32_t *iactwp, const uint8_t *swlnav);
+int fms_sim_launch(Ctx *c, bool tick);
+int fms_sim_restore(Ctx *c);
+// bsa_fms_state: its fp64 arrays (the first kFmsMutable are written by a tick;
+// selvs, apvsdef are read only), its flags, iactwp / rt_off / rt_n, and the
+// reals of the undo set (the mutable ones + ap_trk, ap_alt, ap_vs, selalt)
+constexpr int kFmsReals = 15, kFmsMutable = 13, kFmsFlags = 4, kFmsInts = 3, kFmsUndoReals = kFmsMutable + 4;
+inline bool fms_ticks_at(double simt, double t0) { return t0 + 1.01 < simt || simt < t0 || simt < 1.01; }
 
 // ASAS bookkeeping of one CD call (bsa_asas.hip): bk_count before the gate
 // all-reduce and MVP (may raise the gate's bit 1 on resopairs overflow),

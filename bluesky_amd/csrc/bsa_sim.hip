@@ -231,7 +231,8 @@ void sim_release(Ctx *c) {
                    &c->s_atrk, &c->s_atas, &c->s_avs, &c->s_aalt, &c->s_ase, &c->s_asn,
                    &c->s_active, &c->g_send, &c->g_recv, &c->pg_send, &c->pg_recv, &c->sim_ctl, &c->s_altprev, &c->s_ax, &c->s_env,
                    &c->s_ptab, &c->s_ptype, &c->s_phase, &c->s_ftab, &c->s_fmass, &c->s_fout, &c->s_fused, &c->s_fpend,
-                   &c->f_const, &c->s_noreso, &c->s_resooff, &c->s_dropped, &c->s_atm,
+                   &c->f_const, &c->s_fmsr, &c->s_fmsf, &c->s_fmsi, &c->s_fmsrows, &c->s_fmsur, &c->s_fmsuf, &c->s_fmsui,
+                   &c->s_noreso, &c->s_resooff, &c->s_dropped, &c->s_atm,
                    &c->xfer_stage, &c->lbyidx, &c->fetch_stage, &c->tpr_snap, &c->tpr_ctl, &c->nx_alt, &c->nx_vs, &c->nx_gse, &c->nx_gsn};
   for (auto *b : all) release(*b);
   bk_release(c);
@@ -604,6 +605,7 @@ int bsa_sim_init(bsa_ctx *cc, int64_t n, const bsa_sim_state *s, const bsa_sim_p
   c->sim_limits = false;
   c->sim_perf = false;
   c->sim_forces = false;
+  c->sim_fms = false;
   if (bsa::put_home(c, c->s_atrk.p, s->trk, 8, tmp) || bsa::put_home(c, c->s_atas.p, s->tas, 8, tmp)) return -1;
   BSA_HIP(c, hipMemsetAsync(c->s_avs.p, 0, N8, c->stream));
   BSA_HIP(c, hipMemsetAsync(c->s_ase.p, 0, (size_t)n * 4, c->stream));
@@ -659,6 +661,8 @@ int bsa_sim_step(bsa_ctx *cc, int nsteps) {
     if (attempt > 6) return bsa::fail(c, "candidate buffer overflow in the resident step (retries exhausted)");
     const int64_t base = c->sim_steps, base_cd = c->sim_cd_calls;
     const bool derivable0 = c->sim_gs_derivable;
+    const double fms_simt0 = c->fms_simt, fms_t00 = c->fms_t0;  // the FMS clock at the batch base
+    const int64_t fms_ticks0 = c->fms_ticks;
     BSA_HIP(c, hipMemsetAsync((char *)c->sim_ctl.p + bsa::kSimCtlSticky, 0, 40, c->stream));  // sticky, steps_done, demands, stale
     while (c->sim_steps < target) {
       bool cd_step = false;
@@ -666,6 +670,18 @@ int bsa_sim_step(bsa_ctx *cc, int nsteps) {
       // stream (bsa_perf.hip).  The first step of a re-run attempt does not commit
       // the pending fuel: it is the aborted step's own
       if (c->sim_forces && bsa::forces_sim_launch(c, !(attempt > 0 && c->sim_steps == base))) return -1;
+      // Autopilot.update on the pre-step state (bsa_fms.hip): the tick is decided
+      // here, by the reference's rule on the host's copy of simt (autopilot.py:61-62,
+      // simulation.py:119); nothing is read back
+      if (c->sim_fms) {
+        const bool tick = bsa::fms_ticks_at(c->fms_simt, c->fms_t0);
+        if (bsa::fms_sim_launch(c, tick)) return -1;
+        if (tick) {
+          c->fms_t0 = c->fms_simt;
+          c->fms_ticks++;
+        }
+        c->fms_simt += c->simp.simdt;
+      }
       if (c->sim_steps % c->simp.cd_every == 0) {
         // one rank: K2 and this step's K4' as one launch (k24_launch below;
         // BSA_K24=0 off) -- K4' then starts on each workgroup's rows as soon as
@@ -813,6 +829,22 @@ int bsa_sim_step(bsa_ctx *cc, int nsteps) {
     for (int64_t k = base; k < base + done; ++k) cds += (k % c->simp.cd_every == 0) ? 1 : 0;
     c->sim_cd_calls = base_cd + cds;
     c->sim_gathered = c->nranks == 1;
+    if (c->sim_fms) {
+      // the FMS clock of the completed steps, replayed from the batch base; the
+      // aborted step's launch ran (later ones were no-ops): if it ticked, the
+      // undo set it filled holds the step's start -- put it back
+      c->fms_simt = fms_simt0;
+      c->fms_t0 = fms_t00;
+      c->fms_ticks = fms_ticks0;
+      for (int64_t k = 0; k < done; ++k) {
+        if (bsa::fms_ticks_at(c->fms_simt, c->fms_t0)) {
+          c->fms_t0 = c->fms_simt;
+          c->fms_ticks++;
+        }
+        c->fms_simt += c->simp.simdt;
+      }
+      if (bsa::fms_ticks_at(c->fms_simt, c->fms_t0) && bsa::fms_sim_restore(c)) return -1;
+    }
     if (bsa::grow_after_abort(c, ctl)) return -1;
   }
   return 0;
@@ -957,6 +989,85 @@ int bsa_sim_read_forces(bsa_ctx *cc, double *cd0, double *drag, double *thrustra
       fuel_used[i] = fuel_used[i] + pend[i];
     }
   }
+  return 0;
+}
+
+int bsa_sim_set_fms(bsa_ctx *cc, int64_t nrows, const double *route_rows, const int32_t *rt_off, const int32_t *rt_n,
+                    const int32_t *iactwp, const bsa_fms_state *st, double simt, double t0) {
+  Ctx *c = (Ctx *)cc;
+  if (!c) return -1;
+  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_set_fms before bsa_sim_init");
+  BSA_HIP(c, hipSetDevice(c->device));
+  if (!route_rows) {
+    c->sim_fms = false;
+    return 0;
+  }
+  if (nrows < 0 || nrows > 0x7fffffff / 8) return bsa::fail(c, "bsa_sim_set_fms: bad route row count");
+  if (!rt_off || !rt_n || !iactwp || !st) return bsa::fail(c, "bsa_sim_set_fms: NULL array");
+  const double *reals[bsa::kFmsReals] = {st->actwp_lat, st->actwp_lon, st->actwp_nextaltco, st->actwp_xtoalt, st->actwp_spd,
+                             st->actwp_vs, st->actwp_turndist, st->actwp_flyby, st->actwp_next_qdr, st->dist2vs,
+                             st->vnavvs, st->swvnavvs, st->selspd, st->selvs, st->apvsdef};
+  const uint8_t *flags[bsa::kFmsFlags] = {st->swlnav, st->swvnav, st->abco, st->belco};
+  for (auto q : reals)
+    if (!q) return bsa::fail(c, "bsa_sim_set_fms: NULL array");
+  for (auto q : flags)
+    if (!q) return bsa::fail(c, "bsa_sim_set_fms: NULL array");
+  if (!std::isfinite(simt) || std::isnan(t0)) return bsa::fail(c, "bsa_sim_set_fms: simt / t0 not finite");
+  const int64_t n = c->n;
+  if (bsa::fms_check_routes(c, "bsa_sim_set_fms", n, nrows, rt_off, rt_n, iactwp, st->swlnav)) return -1;
+  c->sim_fms = false;
+  const size_t N = (size_t)n;
+  if (!bsa::ensure(c, c->s_fmsr, bsa::kFmsReals * N * 8, "FMS state") || !bsa::ensure(c, c->s_fmsf, bsa::kFmsFlags * N, "FMS flags") ||
+      !bsa::ensure(c, c->s_fmsi, bsa::kFmsInts * N * 4, "route indices") ||
+      !bsa::ensure(c, c->s_fmsrows, (size_t)nrows * 64 + 64, "route table") ||
+      !bsa::ensure(c, c->s_fmsur, bsa::kFmsUndoReals * N * 8, "FMS undo set") || !bsa::ensure(c, c->s_fmsuf, 2 * N, "FMS undo flags") ||
+      !bsa::ensure(c, c->s_fmsui, N * 4, "FMS undo waypoints"))
+    return -1;
+  std::vector<char> tmp;
+  for (int q = 0; q < bsa::kFmsReals; ++q)
+    if (bsa::put_home(c, (double *)c->s_fmsr.p + q * N, reals[q], 8, tmp)) return -1;
+  for (int q = 0; q < bsa::kFmsFlags; ++q)
+    if (bsa::put_home(c, (uint8_t *)c->s_fmsf.p + q * N, flags[q], 1, tmp)) return -1;
+  const int32_t *ints[bsa::kFmsInts] = {iactwp, rt_off, rt_n};
+  for (int q = 0; q < bsa::kFmsInts; ++q)
+    if (bsa::put_home(c, (int32_t *)c->s_fmsi.p + q * N, ints[q], 4, tmp)) return -1;
+  if (nrows) BSA_HIP(c, hipMemcpyAsync(c->s_fmsrows.p, route_rows, (size_t)nrows * 64, hipMemcpyHostToDevice, c->stream));
+  BSA_HIP(c, hipStreamSynchronize(c->stream));
+  c->fms_simt = simt;
+  c->fms_t0 = t0;
+  c->fms_ticks = 0;
+  c->sim_fms = true;
+  return 0;
+}
+
+int bsa_sim_read_fms(bsa_ctx *cc, const bsa_fms_state *st, int32_t *iactwp, double *ap_trk, double *ap_tas,
+                     double *ap_alt, double *ap_vs, double *selalt, double *simt, double *t0, int64_t *ticks) {
+  Ctx *c = (Ctx *)cc;
+  if (!c) return -1;
+  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_read_fms before bsa_sim_init");
+  if (!c->sim_fms) return bsa::fail(c, "no FMS state: bsa_sim_set_fms is off");
+  BSA_HIP(c, hipSetDevice(c->device));
+  const int64_t rb = c->sim_rb, re = c->sim_re;
+  const size_t N = (size_t)c->n;
+  std::vector<char> tmp;
+  if (st) {
+    double *reals[bsa::kFmsReals] = {st->actwp_lat, st->actwp_lon, st->actwp_nextaltco, st->actwp_xtoalt, st->actwp_spd,
+                         st->actwp_vs, st->actwp_turndist, st->actwp_flyby, st->actwp_next_qdr, st->dist2vs,
+                         st->vnavvs, st->swvnavvs, st->selspd, st->selvs, st->apvsdef};
+    uint8_t *flags[bsa::kFmsFlags] = {st->swlnav, st->swvnav, st->abco, st->belco};
+    for (int q = 0; q < bsa::kFmsReals; ++q)
+      if (reals[q] && bsa::get_home(c, reals[q], (const double *)c->s_fmsr.p + q * N, 8, rb, re, tmp)) return -1;
+    for (int q = 0; q < bsa::kFmsFlags; ++q)
+      if (flags[q] && bsa::get_home(c, flags[q], (const uint8_t *)c->s_fmsf.p + q * N, 1, rb, re, tmp)) return -1;
+  }
+  if (iactwp && bsa::get_home(c, iactwp, c->s_fmsi.p, 4, rb, re, tmp)) return -1;
+  double *tg[5] = {ap_trk, ap_tas, ap_alt, ap_vs, selalt};
+  const void *src[5] = {c->s_aptrk.p, c->s_aptas.p, c->s_apalt.p, c->s_apvs.p, c->s_selalt.p};
+  for (int q = 0; q < 5; ++q)
+    if (tg[q] && bsa::get_home(c, tg[q], src[q], 8, rb, re, tmp)) return -1;
+  if (simt) *simt = c->fms_simt;
+  if (t0) *t0 = c->fms_t0;
+  if (ticks) *ticks = c->fms_ticks;
   return 0;
 }
 

@@ -89,6 +89,11 @@ static std::vector<PerAc> per_aircraft(Ctx *c) {
     v.push_back({&c->s_fused, 8, 1});
     v.push_back({&c->s_fpend, 8, 1});
   }
+  if (c->sim_fms) {  // the FMS state, its flags, iactwp / rt_off / rt_n (route rows stay where they are)
+    v.push_back({&c->s_fmsr, 8, kFmsReals});
+    v.push_back({&c->s_fmsf, 1, kFmsFlags});
+    v.push_back({&c->s_fmsi, 4, kFmsInts});
+  }
   return v;
 }
 
@@ -437,6 +442,8 @@ int bsa_sim_delete(bsa_ctx *cc, int64_t k, const int64_t *idx) {
   if (!c) return -1;
   if (bsa::check_sim(c, "bsa_sim_delete")) return -1;
   if (k < 0 || (k > 0 && !idx)) return bsa::fail(c, "bad delete list");
+  if (c->sim_fms && c->nranks > 1)
+    return bsa::fail(c, "bsa_sim_delete with autopilot guidance on several ranks: bsa_sim_set_fms(NULL), delete, set it again");
   const int64_t n = c->n;
   std::vector<int64_t> d(idx, idx + k);
   std::sort(d.begin(), d.end());
@@ -550,6 +557,8 @@ int bsa_sim_create(bsa_ctx *cc, int64_t m, const bsa_sim_state *s) {
   if (m < 1 || !s) return bsa::fail(c, "bad create arguments");
   if (c->sim_limits || c->sim_perf)
     return bsa::fail(c, "bsa_sim_create with OpenAP limits on: switch them off, create, set them again");
+  if (c->sim_fms)
+    return bsa::fail(c, "bsa_sim_create with autopilot guidance on: create, then bsa_sim_set_fms again with the new routes");
   const double *src[] = {s->lat, s->lon, s->alt, s->tas, s->hdg, s->vs, s->gs, s->trk, s->gseast,
                          s->gsnorth, s->ap_trk, s->ap_tas, s->ap_alt, s->ap_vs, s->selalt, s->bank,
                          s->eps, s->accel, s->asas_alt};

@@ -128,6 +128,19 @@ class ResidentSim:
         and fuel_used [kg] so far, of this rank's rows."""
         return self.ctx.sim_read_forces()
 
+    def set_fms(self, rows=None, off=None, n=None, state=None, simt=0.0, t0=-999.):
+        """Autopilot.update (LNAV / VNAV guidance, waypoint switching) at the start
+        of every step, so the aircraft follow their routes inside a batch
+        (bsa_sim_set_fms; ``rows, off, n, state`` from ``bluesky_amd.fms.route_table`` /
+        ``from_bluesky``; ``simt``: the sim time of the next step, ``t0``: Autopilot.t0).
+        None switches it off."""
+        self.ctx.sim_set_fms(rows, off, n, state, simt, t0)
+
+    def read_fms(self):
+        """dict of the FMS state, ``iactwp``, the autopilot targets of this rank's
+        rows, and ``simt``, ``t0``, ``ticks`` (bsa_sim_read_fms)."""
+        return self.ctx.sim_read_fms()
+
     def create(self, state):
         """Append aircraft (Traffic.create; ``state`` as ``initial_state`` returns,
         m long each): indices n..n+m-1 (bsa_sim_create; collective with several ranks)."""

@@ -484,6 +484,54 @@ int bsa_sim_set_forces(bsa_ctx *ctx, int64_t ntypes, const double *ftable, const
  * full-n host arrays (rows as bsa_sim_row_ids); any pointer may be NULL. */
 int bsa_sim_read_forces(bsa_ctx *ctx, double *cd0, double *drag, double *thrustratio, double *thrust,
                         double *fuelflow, double *bank, double *fuel_used);
+/* Autopilot LNAV / VNAV guidance and waypoint switching on the device: one
+ * full Autopilot.update call with a forced FMS tick (autopilot.py:59-203, with
+ * ActiveWaypoint.Reached / calcturn, Route.getnextwp on a route table,
+ * ComputeVNAV and geo.qdrdist) for n aircraft in host arrays.
+ *
+ * The FMS state of the aircraft, arrays of length n.  Doubles: traf.actwp's
+ * nine arrays, ap.dist2vs / vnavvs / swvnavvs (0 or 1), traf.selspd / selvs /
+ * apvsdef; uint8 flags: traf.swlnav / swvnav / abco / belco.  selvs, apvsdef,
+ * abco and belco are only read. */
+typedef struct bsa_fms_state {
+  double *actwp_lat, *actwp_lon, *actwp_nextaltco, *actwp_xtoalt, *actwp_spd, *actwp_vs, *actwp_turndist,
+      *actwp_flyby, *actwp_next_qdr;
+  double *dist2vs, *vnavvs, *swvnavvs, *selspd, *selvs, *apvsdef;
+  uint8_t *swlnav, *swvnav, *abco, *belco;
+} bsa_fms_state;
+/* route_rows: nrows x 8 doubles, one waypoint per row: lat, lon [deg], alt [m]
+ * (< 0: none), spd [CAS m/s or Mach] (-999: none), xtoalt, toalt [m] (the
+ * route's wpxtoalt / wptoalt after Route.calcfp), flyby (1 / 0), nextqdr (the
+ * bearing to the following waypoint, -999 for the last).  Aircraft k owns rows
+ * [rt_off[k], rt_off[k] + rt_n[k]) and flies to its row iactwp[k]; rt_n 0 (no
+ * route) needs swlnav 0 and iactwp -1 or 0.  Every index is range-checked here, before anything
+ * is launched.  lat .. bank: the traffic state the call reads (bank [rad]).
+ * In and out: iactwp, *st, and the autopilot's targets ap_trk / ap_alt / ap_vs
+ * and traf.selalt; out: ap_tas. */
+int bsa_fms_update(bsa_ctx *ctx, int64_t n, int64_t nrows, const double *route_rows, const int32_t *rt_off,
+                   const int32_t *rt_n, int32_t *iactwp, const double *lat, const double *lon, const double *alt,
+                   const double *tas, const double *gs, const double *trk, const double *ax, const double *bank,
+                   const bsa_fms_state *st, double *ap_trk, double *ap_tas, double *ap_alt, double *ap_vs,
+                   double *selalt);
+/* The same inside the resident step, on the pre-step state (ap.update is the
+ * first call of Traffic.update, traffic.py:395), in a launch of its own at the
+ * start of every step, so that resident aircraft follow their routes with no
+ * host work inside a batch.  Arrays as bsa_fms_update, full-n host arrays in
+ * aircraft-index order; the traffic state and ap_trk / ap_tas / ap_alt / ap_vs /
+ * selalt are the sim's own.  simt: the time of the next step; t0: Autopilot.t0
+ * (-999. at start).  The context advances simt by simdt per step and ticks by
+ * the reference's rule (autopilot.py:61-62); a step that does not tick only
+ * evaluates ap.tas.  Exact through aborted and re-run batches.  route_rows ==
+ * NULL switches it off (the default); a second call replaces everything.
+ * bsa_sim_delete carries the arrays along on one rank and is refused on
+ * several; bsa_sim_create is refused while it is on. */
+int bsa_sim_set_fms(bsa_ctx *ctx, int64_t nrows, const double *route_rows, const int32_t *rt_off, const int32_t *rt_n,
+                    const int32_t *iactwp, const bsa_fms_state *st, double simt, double t0);
+/* This rank's rows (bsa_sim_row_ids) of the FMS state, iactwp and the
+ * autopilot's targets into full-n host arrays, the clock and the number of
+ * ticks since bsa_sim_set_fms; any pointer may be NULL. */
+int bsa_sim_read_fms(bsa_ctx *ctx, const bsa_fms_state *st, int32_t *iactwp, double *ap_trk, double *ap_tas,
+                     double *ap_alt, double *ap_vs, double *selalt, double *simt, double *t0, int64_t *ticks);
 /* Traffic.update's atmosphere, traf.p / rho / Temp = vatmos(traf.alt) on the
  * pre-step altitude (traffic.py:389, aero.py:62-74), computed inside the step
  * when on (off after bsa_sim_init: nothing in the step reads them; a host

@@ -20,6 +20,9 @@ and outputs as small ``.npz`` files under ``tests/golden/``:
                          envelope (perfoap.py:211-262) and acceleration()
                          (perfoap.py:271-280) with the reference's own coefficient
                          tables (data/performance/OpenAP)
+* ``fms_<case>.npz``    -- ``Autopilot.update`` (autopilot.py:59-304): one forced FMS
+                         tick (LNAV / VNAV guidance, waypoint switching) by the
+                         reference's own Autopilot / ActiveWaypoint / Route objects
 * ``cd_nonfin_<case>.npz`` -- ``StateBasedCD.detect`` with a non-finite input
                          (``--nonfinite-only`` writes only these)
 * ``cdkwik_<case>.npz`` -- the opt-in KWIK variant: ``StateBasedCD.detect`` with
@@ -624,6 +627,393 @@ def run_forces(name, n, seed):
           % (name, n, fwm.sum(), np.isnan(ref['drag']).sum(), os.path.getsize(path)))
 
 
+def fms_case(n, seed):
+    """Inputs of one forced FMS tick: (list of reference-style route dicts,
+    state dict).  Every aircraft draws its route length, its distance from the
+    active waypoint (50 m .. 50 km, so that turn distance, turn radius and far
+    away all occur), its track (towards / away), altitude and speed constraints
+    and its mode switches independently, so any prefix holds every case."""
+    rng = np.random.default_rng(seed)
+    routes = []
+    st = {k: np.zeros(n) for k in ('lat', 'lon', 'alt', 'tas', 'gs', 'trk', 'ax', 'bank', 'actwp_lat', 'actwp_lon',
+                                   'actwp_nextaltco', 'actwp_xtoalt', 'actwp_spd', 'actwp_vs', 'actwp_turndist',
+                                   'actwp_flyby', 'actwp_next_qdr', 'dist2vs', 'vnavvs', 'swvnavvs', 'selspd',
+                                   'selvs', 'apvsdef', 'ap_trk', 'ap_tas', 'ap_alt', 'ap_vs', 'selalt')}
+    for k in ('swlnav', 'swvnav', 'abco', 'belco'):
+        st[k] = np.zeros(n, dtype=bool)
+    st['iactwp'] = np.zeros(n, dtype=np.int32)
+
+    def spd_value():
+        c = rng.integers(0, 3)
+        return -999. if c == 0 else (f32(rng.uniform(90., 190.)) if c == 1 else f32(rng.uniform(0.55, 0.86)))
+
+    def f32(x):          # values with a float32's digits: the file compresses to under 1 MB
+        return float(np.float32(x))
+
+    for k in range(n):
+        nwp = int(rng.choice([0, 1, 2, 3, 4, int(rng.integers(6, 41))], p=[0.06, 0.14, 0.25, 0.3, 0.2, 0.05]))
+        alt = float(rng.uniform(800., 11500.))
+        south = rng.random() < 0.1
+        lat0, lon0 = float(rng.uniform(-40., -0.3) if south else rng.uniform(0.3, 62.)), float(rng.uniform(-170., 170.))
+        if rng.random() < 0.04:
+            lat0 = float(rng.uniform(-0.02, 0.02))                 # legs across the equator
+        wplat, wplon = [], []
+        la, lo, brg = lat0, lon0, float(rng.uniform(0., 360.))
+        for _ in range(nwp):
+            leg = float(rng.uniform(5000., 60000.))
+            brg = (brg + float(rng.choice([0., 20., -35., 80., -100., 150.])) + float(rng.uniform(-5., 5.))) % 360.
+            la = la + np.degrees(leg * np.cos(np.radians(brg)) / 6371000.)
+            lo = lo + np.degrees(leg * np.sin(np.radians(brg)) / 6371000. / np.cos(np.radians(la)))
+            wplat.append(f32(la))
+            wplon.append(f32(lo))
+        altmode = rng.integers(0, 5, max(nwp, 1))
+        wpalt = [-999. if altmode[i] < 2 else (f32(alt + rng.uniform(-3., 3.)) if altmode[i] == 2 else
+                                               f32(rng.uniform(500., 11000.))) for i in range(nwp)]
+        wptype = [0] * nwp
+        if nwp and rng.random() < 0.15:
+            wptype[-1] = 3                                         # Route.dest: toalt 0
+        r = dict(wplat=wplat, wplon=wplon, wpalt=wpalt, wpspd=[spd_value() for _ in range(nwp)],
+                 wpflyby=[bool(rng.random() < 0.75) for _ in range(nwp)], wptype=wptype,
+                 iactwp=int(rng.integers(0, nwp)) if nwp else -1)
+        routes.append(r)
+        i = r['iactwp']
+        if nwp:
+            wlat, wlon = wplat[i], wplon[i]
+        else:
+            wlat, wlon = lat0 + 0.2, lon0 + 0.2
+        # own position: dist [m] from the active waypoint, on a random side
+        dist = float(np.exp(rng.uniform(np.log(50.), np.log(50000.))))
+        side = float(rng.uniform(0., 360.))
+        st['lat'][k] = wlat + np.degrees(dist * np.cos(np.radians(side)) / 6371000.)
+        st['lon'][k] = wlon + np.degrees(dist * np.sin(np.radians(side)) / 6371000. / np.cos(np.radians(wlat)))
+        towp = (side + 180.) % 360.
+        st['trk'][k] = (towp + float(rng.choice([0., 10., -40., 120., 180., -95.])) + float(rng.uniform(-4., 4.))) % 360.
+        st['alt'][k] = alt
+        st['tas'][k] = float(rng.uniform(80., 260.))
+        st['gs'][k] = st['tas'][k] * float(rng.choice([1.0, 0.1, 1.1]))
+        st['ax'][k] = float(rng.choice([0.0, 0.5, -0.5, 2.0]))
+        st['bank'][k] = np.radians(float(rng.choice([25., 25., 35., 0.])))
+        st['actwp_lat'][k], st['actwp_lon'][k] = wlat, wlon
+        st['actwp_nextaltco'][k] = float(rng.choice([alt - 2000., alt + 1500., alt]))
+        st['actwp_xtoalt'][k] = float(rng.choice([0., 1., 20000.]))
+        st['actwp_spd'][k] = spd_value()
+        st['actwp_vs'][k] = float(rng.uniform(0., 15.))
+        st['actwp_turndist'][k] = float(rng.uniform(0., 3000.))
+        st['actwp_flyby'][k] = float(r['wpflyby'][i]) if nwp else 1.0
+        st['actwp_next_qdr'][k] = -999. if (nwp == 0 or i == nwp - 1 or rng.random() < 0.1) else float(
+            refgeo.qdrdist(wplat[i], wplon[i], wplat[i + 1], wplon[i + 1])[0])
+        st['dist2vs'][k] = float(rng.choice([-999., 99999. * nm, dist * 0.5, dist * 3.0]))
+        st['vnavvs'][k] = float(rng.uniform(0., 12.))
+        st['swvnavvs'][k] = float(rng.random() < 0.5)
+        st['selspd'][k] = float(rng.uniform(90., 190.)) if rng.random() < 0.7 else float(rng.uniform(0.5, 0.85))
+        st['selvs'][k] = float(rng.choice([0.0, 0.05, 5.0, -6.0]))
+        st['apvsdef'][k] = 1500. * fpm
+        st['swlnav'][k] = nwp > 0 and rng.random() < 0.85
+        st['swvnav'][k] = rng.random() < 0.8
+        st['abco'][k] = rng.random() < 0.4
+        st['belco'][k] = (not st['abco'][k]) if rng.random() < 0.9 else bool(st['abco'][k])
+        st['iactwp'][k] = i
+        st['ap_trk'][k] = st['trk'][k]
+        st['ap_alt'][k] = alt
+        st['ap_vs'][k] = 1500. * fpm
+        st['selalt'][k] = alt + float(rng.choice([0., 600., -900.]))
+    for k in st:
+        if st[k].dtype == np.float64:
+            st[k] = st[k].astype(np.float32).astype(np.float64)
+    st['ap_tas'] = st['tas'].copy()
+    # two latitudes of exactly 0: geo.qdrdist's distance is NaN (0 / 0 in res2), as numpy's, so never reached
+    for k in [q for q in range(40, n) if st['swlnav'][q]][:2]:
+        st['lat'][k] = 0.0
+        st['actwp_lat'][k] = 0.0
+        routes[k]['wplat'][routes[k]['iactwp']] = 0.0
+    return routes, st
+
+
+def ref_autopilot(routes, st):
+    """Real Autopilot / ActiveWaypoint / Route objects of the reference holding
+    the case (made without __init__: the TrafficArrays registry wants a parent),
+    and the stand-in bs.traf they read.  calcfp() has run on every route."""
+    from bluesky.traffic.autopilot import Autopilot
+    from bluesky.traffic.activewpdata import ActiveWaypoint
+    from bluesky.traffic.route import Route
+    ap = Autopilot.__new__(Autopilot)
+    ap.t0, ap.dt, ap.steepness = -999., 1.01, 3000. * ft / (10. * nm)
+    for a, kk in (('trk', 'ap_trk'), ('tas', 'ap_tas'), ('alt', 'ap_alt'), ('vs', 'ap_vs'), ('dist2vs', 'dist2vs'),
+                  ('vnavvs', 'vnavvs')):
+        setattr(ap, a, st[kk].copy())
+    ap.swvnavvs = st['swvnavvs'].astype(bool)
+    ap.route = []
+    for r in routes:
+        R = Route()
+        R.wplat, R.wplon, R.wpalt, R.wpspd = list(r['wplat']), list(r['wplon']), list(r['wpalt']), list(r['wpspd'])
+        R.wpflyby, R.wptype = list(r['wpflyby']), list(r['wptype'])
+        R.wpname = ['WP%03d' % i for i in range(len(r['wplat']))]
+        R.calcfp()
+        R.iactwp = r['iactwp']
+        ap.route.append(R)
+    wp = ActiveWaypoint.__new__(ActiveWaypoint)
+    for a in ('lat', 'lon', 'nextaltco', 'xtoalt', 'spd', 'vs', 'turndist', 'flyby', 'next_qdr'):
+        setattr(wp, a, st['actwp_' + a].copy())
+    traf = types.SimpleNamespace(ntraf=len(st['lat']), actwp=wp, ap=ap)
+    for a in ('lat', 'lon', 'alt', 'tas', 'gs', 'trk', 'ax', 'bank', 'selspd', 'selvs', 'apvsdef', 'selalt',
+              'swlnav', 'swvnav', 'abco', 'belco'):
+        setattr(traf, a, st[a].copy())
+    traf.coslat = np.cos(np.deg2rad(traf.lat))       # traffic.py:482
+    return ap, wp, traf
+
+
+def ref_fms_state(ap, wp, traf):
+    out = {'actwp_' + a: np.asarray(getattr(wp, a), dtype=np.float64) for a in
+           ('lat', 'lon', 'nextaltco', 'xtoalt', 'spd', 'vs', 'turndist', 'flyby', 'next_qdr')}
+    out.update(dist2vs=ap.dist2vs, vnavvs=ap.vnavvs, swvnavvs=np.asarray(ap.swvnavvs, dtype=np.float64),
+               selspd=traf.selspd, swlnav=np.asarray(traf.swlnav, dtype=bool), swvnav=np.asarray(traf.swvnav, dtype=bool),
+               iactwp=np.array([r.iactwp for r in ap.route], dtype=np.int32),
+               ap_trk=ap.trk, ap_tas=ap.tas, ap_alt=ap.alt, ap_vs=ap.vs, selalt=traf.selalt)
+    return {k: np.array(v) for k, v in out.items()}
+
+
+def run_fms(name, n, seed):
+    """One forced tick of the reference's own Autopilot.update (autopilot.py:59-203)
+    on real Autopilot / ActiveWaypoint / Route objects and a stand-in bs.traf.
+    tests/fms_np.py and bluesky_amd.fms.route_table are asserted bitwise equal
+    on every output; every case the file must hold is asserted present in the
+    first 257 rows."""
+    import bluesky as bs
+    from bluesky_amd import fms as bfms
+    from tests import fms_np
+    routes, st = fms_case(n, seed)
+    ap, wp, traf = ref_autopilot(routes, st)
+    rows, off, cnt, act = bfms.route_table(ap.route, st['swlnav'])
+    assert np.array_equal(act[cnt > 0], st['iactwp'][cnt > 0])
+    for k, R in enumerate(ap.route):                  # the table against the routes' own getnextqdr / calcfp
+        for i in range(R.nwp):
+            keep, R.iactwp = R.iactwp, i
+            want = (R.wplat[i], R.wplon[i], R.wpalt[i], R.wpspd[i], R.wpxtoalt[i], R.wptoalt[i],
+                    float(R.wpflyby[i]), R.getnextqdr())
+            R.iactwp = keep
+            assert np.array_equal(rows[off[k] + i], np.array(want, dtype=np.float64), equal_nan=True), (k, i)
+        x, t = bfms.flight_plan(R.wplat, R.wplon, R.wpalt, R.wptype)
+        assert list(x) == list(R.wpxtoalt) and list(t) == list(R.wptoalt), k
+    info = {}
+    mine = fms_np.update(st, rows, off, cnt, tick=True, info=info)
+    near = fms_np.near_threshold(st, rows, off, cnt)
+    saved = getattr(bs, 'traf', None)
+    bs.traf = traf
+    try:
+        with np.errstate(all='ignore'):
+            ap.update(0.0)                            # t0 = -999: the tick runs
+    finally:
+        bs.traf = saved
+    ref = ref_fms_state(ap, wp, traf)
+    for k in fms_np.OUTPUTS:
+        assert np.array_equal(np.asarray(mine[k], dtype=ref[k].dtype), ref[k], equal_nan=True), \
+            'helper != reference fms %s' % k
+    assert not near.any(), '%d rows within 1e-9 of a threshold' % near.sum()
+    # ---- every case, in the first 257 rows
+    h = slice(0, 257)
+    re_, nw = info['reached'][h], cnt[h]
+    sw0, sv0 = st['swlnav'][h], st['swvnav'][h]
+    i1 = ref['iactwp'][h]
+    rrow = rows[np.minimum(off[h] + np.maximum(i1, 0), len(rows) - 1)]
+    cases = {
+        'reached by dist < turndist': re_ & info['bydist'][h],
+        'reached by circling only': re_ & info['circling'][h] & ~info['bydist'][h],
+        'end of route: LNAV and VNAV off': re_ & sv0 & ~ref['swlnav'][h] & ~ref['swvnav'][h],
+        'route of 0': nw == 0, 'route of 1': nw == 1, 'route of 2': nw == 2, 'long route': nw > 5,
+        'fly-over waypoint reached': re_ & (ref['actwp_flyby'][h] == 0.0),
+        'fly-over active waypoint': sw0 & (st['actwp_flyby'][h] == 0.0),
+        'next_qdr -999 after a switch': re_ & (ref['actwp_next_qdr'][h] < -900.),
+        'next_qdr -999 before': sw0 & (st['actwp_next_qdr'][h] < -900.),
+        'waypoint altitude given': re_ & (rrow[:, 2] >= -0.01),
+        'waypoint altitude not given': re_ & (rrow[:, 2] < -0.01),
+        'ComputeVNAV toalt < 0': info['vnav'][h] == 1, 'ComputeVNAV VNAV off': info['vnav'][h] == 2,
+        'ComputeVNAV descent': info['vnav'][h] == 3, 'ComputeVNAV urgent descent': info['vnav'][h] == 6,
+        'ComputeVNAV climb': info['vnav'][h] == 4, 'ComputeVNAV level': info['vnav'][h] == 5,
+        'CAS waypoint speed': re_ & (ref['actwp_spd'][h] > 1.0) & (rrow[:, 3] > 1.0) & (ref['actwp_spd'][h] == rrow[:, 3]),
+        'CAS to Mach above crossover': re_ & (rrow[:, 3] > 1.0) & (ref['actwp_spd'][h] > 0) & (ref['actwp_spd'][h] < 1.0),
+        'Mach to CAS below crossover': re_ & (rrow[:, 3] > 0) & (rrow[:, 3] <= 1.0) & (ref['actwp_spd'][h] > 1.0),
+        'waypoint speed -999': re_ & (rrow[:, 3] < -990.),
+        'oldspd > 0 with VNAV on': re_ & ref['swvnav'][h] & (st['actwp_spd'][h] > 0),
+        'LNAV off, VNAV on, inside': ~sw0 & sv0 & (ref['swvnavvs'][h] == 1.0),
+        'LNAV off, VNAV on, outside': ~sw0 & sv0 & (ref['swvnavvs'][h] == 0.0),
+        'selvs below 0.1': (ref['swvnavvs'][h] == 0.0) & (np.abs(st['selvs'][h]) <= 0.1),
+        'selvs above 0.1': (ref['swvnavvs'][h] == 0.0) & (np.abs(st['selvs'][h]) > 0.1),
+        'usespdcon': info['usespdcon'][h], 'no usespdcon': ~info['usespdcon'][h],
+        'swvnavvs by startdescent': sw0 & (ref['swvnavvs'][h] == 1.0),
+        'two latitudes of 0 (NaN dist): not reached': sw0 & ~re_ & (st['lat'][h] == 0.0) & (st['actwp_lat'][h] == 0.0),
+    }
+    for what, m in cases.items():
+        assert m.any(), 'fms %s: no row with "%s" in the first 257' % (name, what)
+    out = {k: v for k, v in st.items()}
+    out.update(route_rows=rows, rt_off=off, rt_n=cnt, near_threshold=near, reached=info['reached'],
+               vnav_path=info['vnav'], numpy_version=np.array(np.__version__))
+    out.update({'out_' + k: ref[k] for k in fms_np.OUTPUTS})
+    out['wp_type'] = np.concatenate([np.array(r['wptype'], dtype=np.int32) for r in routes] + [np.zeros(0, np.int32)])
+    path = os.path.join(OUT, 'fms_%s.npz' % name)
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) < 1000000
+    print('fms_%-17s N=%5d reached %d (first 257: %d), %d route rows, %d bytes; %s'
+          % (name, n, info['reached'].sum(), re_.sum(), len(rows), os.path.getsize(path),
+             ' '.join('%s=%d' % (w.split()[0] + w.split()[-1], m.sum()) for w, m in list(cases.items())[:3])))
+
+
+FLIGHT_TRAFFIC = ('lat', 'lon', 'alt', 'tas', 'hdg', 'vs', 'ax')
+
+
+def fms_flight_case(n, seed):
+    """64 aircraft at 100-150 m/s on routes of 2-4 waypoints, legs 5-15 km, the
+    first waypoint 1-5 km ahead, mixed altitude / speed constraints: in 120 s
+    every aircraft passes at least one waypoint and some finish their route."""
+    rng = np.random.default_rng(seed)
+    routes, st = fms_case(n, seed)            # (for the key set; every value is replaced below)
+    routes = []
+    for k in range(n):
+        tas, alt = float(rng.uniform(100., 150.)), float(rng.uniform(2000., 10000.))
+        lat, lon, trk = float(rng.uniform(48., 56.)), float(rng.uniform(0., 10.)), float(rng.uniform(0., 360.))
+        nwp = int(rng.choice([2, 2, 3, 4]))
+        la, lo, brg = lat, lon, trk
+        wplat, wplon = [], []
+        for i in range(nwp):
+            leg = float(rng.uniform(1000., 5000.) if i == 0 else rng.uniform(5000., 15000.))
+            if nwp == 2 and i == 1:
+                leg = float(rng.uniform(5000., 7000.))           # short routes end within the run
+            turn = float(rng.choice([0., 15., -30., 50., -75.])) if i else 0.0      # the first waypoint lies ahead
+            brg = (brg + turn + float(rng.uniform(-3., 3.))) % 360.
+            la = la + np.degrees(leg * np.cos(np.radians(brg)) / 6371000.)
+            lo = lo + np.degrees(leg * np.sin(np.radians(brg)) / 6371000. / np.cos(np.radians(la)))
+            wplat.append(float(np.float32(la)))
+            wplon.append(float(np.float32(lo)))
+        wpalt = [float(rng.choice([-999., -999., alt, alt - 900., alt + 600.])) for _ in range(nwp)]
+        wpspd = [float(rng.choice([-999., -999., 110., 140., 0.45])) for _ in range(nwp)]
+        routes.append(dict(wplat=wplat, wplon=wplon, wpalt=wpalt, wpspd=wpspd,
+                           wpflyby=[bool(i == 0 or rng.random() < 0.8) for i in range(nwp)], wptype=[0] * nwp,
+                           iactwp=0))   # (a fly-over waypoint is never reached: flyby scales turndist AND turnrad to 0)
+        st['lat'][k], st['lon'][k], st['alt'][k], st['tas'][k], st['trk'][k] = lat, lon, alt, tas, trk
+        st['actwp_lat'][k], st['actwp_lon'][k] = wplat[0], wplon[0]
+        st['actwp_flyby'][k] = float(routes[-1]['wpflyby'][0])
+        st['actwp_next_qdr'][k] = float(refgeo.qdrdist(wplat[0], wplon[0], wplat[1], wplon[1])[0])
+        st['swvnav'][k] = rng.random() < 0.75
+    st['gs'] = st['tas'].copy()
+    st['ax'][:] = 0.0
+    st['bank'][:] = np.radians(25.)
+    st['actwp_nextaltco'] = st['alt'].copy()
+    st['actwp_xtoalt'][:] = 0.0
+    st['actwp_spd'][:] = -999.
+    st['actwp_vs'][:] = 0.0
+    st['actwp_turndist'][:] = 1.0
+    st['dist2vs'][:] = -999.
+    st['vnavvs'][:] = 0.0
+    st['swvnavvs'][:] = 0.0
+    st['selspd'] = np.asarray(fpm * 0 + st['tas'] * 0.85)
+    st['selvs'][:] = 0.0
+    st['apvsdef'][:] = 1500. * fpm
+    st['swlnav'][:] = True
+    st['abco'][:] = False
+    st['belco'][:] = True
+    st['iactwp'][:] = 0
+    st['ap_trk'], st['ap_tas'], st['ap_alt'] = st['trk'].copy(), st['tas'].copy(), st['alt'].copy()
+    st['ap_vs'][:] = 1500. * fpm
+    st['selalt'] = st['alt'].copy()
+    return routes, st
+
+
+def run_fms_flight(name, n, seed, nsteps=2400, every=40, simdt=0.05):
+    """Closed loop of the reference: Autopilot.update -> Pilot.APorASAS (ASAS
+    inactive, no wind) -> UpdateAirSpeed / UpdateGroundSpeed / UpdatePosition
+    with acceleration() = 0.5, simt accumulated as simulation.py:119 does.
+    tests/fms_np.py + oracle/step.py run alongside and are asserted bitwise
+    equal to the reference after every step.  Stored: the initial state, the
+    full state every ``every`` steps, every waypoint switch's step."""
+    import bluesky as bs
+    from bluesky.traffic.pilot import Pilot
+    from bluesky_amd import fms as bfms
+    from oracle import step as ostep
+    from tests import fms_np
+    routes, st = fms_flight_case(n, seed)
+    ap, wp, traf = ref_autopilot(routes, st)
+    rows, off, cnt, _ = bfms.route_table(ap.route, st['swlnav'])
+    traf.hdg, traf.vs = st['trk'].copy(), np.zeros(n)
+    traf.eps = np.full(n, 0.01)
+    traf.pilot = Pilot.__new__(Pilot)
+    traf.asas = types.SimpleNamespace(active=np.zeros(n, dtype=bool), trk=st['trk'].copy(), tas=st['tas'].copy(),
+                                      alt=st['alt'].copy(), vs=np.zeros(n))
+    traf.wind = WindSim()
+    acc = np.full(n, 0.5)
+    traf.perf = types.SimpleNamespace(acceleration=lambda: acc)
+    # the helper's state: fms_np's keys + what oracle/step.py steps
+    me = {k: np.array(v) for k, v in st.items()}
+    me.update(hdg=st['trk'].copy(), vs=np.zeros(n), gseast=st['tas'] * np.sin(np.radians(st['trk'])),
+              gsnorth=st['tas'] * np.cos(np.radians(st['trk'])), eps=np.full(n, 0.01), accel=acc.copy(),
+              asas_trk=st['trk'].copy(), asas_tas=st['tas'].copy(), asas_vs=np.zeros(n), asas_alt=st['alt'].copy(),
+              active=np.zeros(n, dtype=bool))
+    op = dict(simdt=simdt, rpz=RPZ, hpz=HPZ, tla=TLA, reso=False, wind=None, mvp=None)
+    init = {k: np.array(v) for k, v in me.items()}
+    samples = {k: [] for k in FLIGHT_TRAFFIC + fms_np.OUTPUTS + ('simt', 't0')}
+    sw_ac, sw_step, nticks = [], [], 0
+    simt, t0 = 0.0, -999.
+
+    def sample():
+        for k in FLIGHT_TRAFFIC + fms_np.OUTPUTS:
+            samples[k].append(np.array(me[k]))
+        samples['simt'].append(simt)
+        samples['t0'].append(t0)
+
+    saved = getattr(bs, 'traf', None)
+    bs.traf = traf
+    try:
+        with np.errstate(all='ignore'):
+            for step in range(nsteps):
+                if step % every == 0:
+                    sample()
+                tick = fms_np.ticks(simt, t0)
+                if tick:
+                    near = fms_np.near_threshold(me, rows, off, cnt, rel=1e-6)
+                    assert not near.any(), 'step %d: %d aircraft within 1e-6 of a threshold: change the seed' % (
+                        step, near.sum())
+                    t0 = simt
+                    nticks += 1
+                before = me['iactwp'].copy()
+                new = fms_np.update(me, rows, off, cnt, tick=tick)
+                me.update({k: new[k] for k in fms_np.OUTPUTS})
+                for k in np.flatnonzero(me['iactwp'] != before):
+                    sw_ac.append(k)
+                    sw_step.append(step)
+                nxt = ostep.sim_step({k: me[k] for k in init if k not in fms_np.REALS + fms_np.FLAGS + ('iactwp',)},
+                                     op, do_cd=False)
+                me.update({k: nxt[k] for k in ('tas', 'hdg', 'alt', 'vs', 'lat', 'lon', 'gs', 'trk', 'gseast',
+                                               'gsnorth', 'ax')})
+                # ---- the reference
+                ap.update(simt)
+                assert ap.t0 == t0
+                Pilot.APorASAS(traf.pilot)
+                RefTraffic.UpdateAirSpeed(traf, simdt, simt)
+                RefTraffic.UpdateGroundSpeed(traf, simdt)
+                RefTraffic.UpdatePosition(traf, simdt)
+                simt += simdt
+                ref = ref_fms_state(ap, wp, traf)
+                for k in fms_np.OUTPUTS:
+                    assert np.array_equal(np.asarray(me[k], dtype=ref[k].dtype), ref[k], equal_nan=True), \
+                        'step %d: helper != reference %s' % (step, k)
+                for k in FLIGHT_TRAFFIC + ('gs', 'trk'):
+                    assert np.array_equal(me[k], getattr(traf, k)), 'step %d: oracle step != reference %s' % (step, k)
+            sample()
+    finally:
+        bs.traf = saved
+    sw_ac, sw_step = np.array(sw_ac, dtype=np.int32), np.array(sw_step, dtype=np.int32)
+    assert len(np.unique(sw_ac)) == n, 'only %d of %d aircraft pass a waypoint' % (len(np.unique(sw_ac)), n)
+    ended = ~me['swlnav']
+    assert ended.any() and not ended.all()
+    out = {'init_' + k: v for k, v in init.items()}
+    out.update({'s_' + k: np.array(v) for k, v in samples.items()})
+    out.update(route_rows=rows, rt_off=off, rt_n=cnt, sw_ac=sw_ac, sw_step=sw_step, nticks=nticks, simdt=simdt,
+               every=every, nsteps=nsteps, margin_rel=1e-6, numpy_version=np.array(np.__version__))
+    path = os.path.join(OUT, 'fms_%s.npz' % name)
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) < 1000000, os.path.getsize(path)
+    print('fms_%-17s N=%5d steps %d ticks %d switches %d routes ended %d, %d bytes'
+          % (name, n, nsteps, nticks, len(sw_ac), ended.sum(), os.path.getsize(path)))
+
+
 def run_asas(name, traf, ncalls=4, dt=20.0):
     """Reference ASAS.update (asas.py:473-504) incl. ResumeNav on a stand-in
     bs.traf; state advanced along straight tracks between CD calls."""
@@ -766,6 +1156,10 @@ def main():
     if '--forces-only' in sys.argv:
         run_forces('forces3000', 3000, 75)
         return
+    if '--fms-only' in sys.argv:
+        run_fms('update2000', 2000, 77)
+        run_fms_flight('flight64', 64, 79)
+        return
     if '--windfield-only' in sys.argv:
         run_kin('windfield1500', 1500, 34, 0.05, wind=WIND_FIELD)
         return
@@ -795,6 +1189,8 @@ def main():
     run_limits('openap2000', 2000, 71)
     run_perf('openap3000', 3000, 73)
     run_forces('forces3000', 3000, 75)
+    run_fms('update2000', 2000, 77)
+    run_fms_flight('flight64', 64, 79)
     for case in geo_cases():
         run_geo(*case)
 

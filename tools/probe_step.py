@@ -6,9 +6,10 @@ steps (one host synchronisation at its end, no stage events) after SETTLE
 untimed ones (the device at steady clocks, as bench.py's --settle).  Collectives
 (box all-gather, halo send / recv, gate all-reduce) are excluded: they need
 the 8-GPU node.  Prints every rank's ms per step and the slowest.
-Usage: python tools/probe_step.py [WORKLOAD [R [STEPS [RANK [SETTLE]]]]] [--perf | --forces]  (RANK:
+Usage: python tools/probe_step.py [WORKLOAD [R [STEPS [RANK [SETTLE]]]]] [--perf | --forces] [--fms]  (RANK:
 that rank of R only, -1 all; SETTLE default 200; --perf: OpenAP phase / envelope in the step,
---forces: also its drag / thrust / fuel-flow launch)"""
+--forces: also its drag / thrust / fuel-flow launch; --fms: Autopilot.update in the
+step, every aircraft on a generated 4-waypoint route)"""
 import json
 import os
 import sys
@@ -38,7 +39,8 @@ def main():
     # thrust / fuel flow launch (bsa_sim_set_forces) -- its cost is --forces against --perf
     forces = '--forces' in sys.argv
     with_perf = forces or '--perf' in sys.argv
-    sys.argv = [a for a in sys.argv if a not in ('--forces', '--perf')]
+    with_fms = '--fms' in sys.argv           # Autopilot.update in the step (bsa_sim_set_fms): its cost is --fms against none
+    sys.argv = [a for a in sys.argv if a not in ('--forces', '--perf', '--fms')]
     name = sys.argv[1] if len(sys.argv) > 1 else 'global1m'
     R = int(sys.argv[2]) if len(sys.argv) > 2 else 8
     steps = int(sys.argv[3]) if len(sys.argv) > 3 else 40
@@ -47,13 +49,17 @@ def main():
     t = synth.workload(name)
     ctx = _lib.Context(0)
     ctx.set_timing_sample(0)
-    sim = resident.ResidentSim(resident.initial_state(t), resident.params(cd_every=1), ctx=ctx)
+    init = resident.initial_state(t)
+    sim = resident.ResidentSim(init, resident.params(cd_every=1), ctx=ctx)
+    if with_fms:
+        from bluesky_amd import fms
+        sim.set_fms(*fms.synthetic_routes(init, seed=5, nwp=4))
     if with_perf:
         table, tidx, ftable, mass = openap_tables(t.ntraf)
         sim.set_perf(table, tidx)
         if forces:
             sim.set_forces(ftable, mass)
-    out = dict(perf=with_perf, forces=forces)
+    out = dict(perf=with_perf, forces=forces, fms=with_fms)
     for ranks in sorted({1, R}) if only is None else [R]:
         per = []
         for r in range(ranks) if only is None else [only]:
@@ -71,6 +77,10 @@ def main():
             print('%s R=%d rank %d rows [%d, %d): %.4f ms per step' % (name, ranks, r, st['row_begin'],
                                                                       st['row_end'], per[-1]), flush=True)
         out['R=%d' % ranks] = dict(slowest_ms=max(per), per_rank_ms=[round(x, 4) for x in per])
+    if with_fms:
+        f = sim.read_fms()
+        out['fms_ticks'] = f['ticks']
+        out['fms_switched'] = int((f['iactwp'] > 0).sum())
     ctx.sim_probe_rank(0, 1)
     print(json.dumps(dict(workload=name, steps=steps, settle=settle, **out)), flush=True)
 
