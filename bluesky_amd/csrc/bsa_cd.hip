@@ -233,16 +233,7 @@ struct ZeroArgs {
   unsigned *x[3];  // more word regions to zero (the halo plan's buffers: HaloPre), or NULL
   int xn[3];
 };
-// Non-finite tcpa inputs (Ctx::nonfin): producers (the column records'
-// makers) store `epoch` into *word when a column's position or velocity is
-// non-finite; K2 makes every row's tcpamax NaN when *word == epoch, and a
-// row's own when rowbad[row] is set (rows of their own, written by
-// k_prep_rows in index order; NULL when the rows are columns)
-struct NfArgs {
-  unsigned long long *word;
-  unsigned long long epoch;
-  const uint8_t *rowbad;
-};
+// (NfArgs, the non-finite tcpa inputs' word and epoch: bsa_internal.h)
 
 __device__ __forceinline__ bool list_word(int k);
 __device__ __forceinline__ void zero_state(const ZeroArgs &z, int t, int nt) {
@@ -1968,15 +1959,6 @@ __global__ __launch_bounds__(256) void k_scatter(const Counters *__restrict__ cn
   }
 }
 
-// MVP's per-pair vectors written by k_rank in the resident step (pdv == NULL: off)
-struct MvpFuse {
-  bsa_mvp_params p;
-  MvpPairIn in;
-  double4 *pdv;
-  uint8_t *pfl;
-  double4 *rowdv;  // k_rank_rows: each row's folded dv (mvp_fold), or NULL
-};
-
 // One lane per pair slot of the scattered lists (grid-stride over P + L, the
 // device-side counts): the slot's rank among its row segment's columns (the
 // segment is short: ~1.5 pairs per row at the 100k box; any length works)
@@ -2481,31 +2463,15 @@ static int next_events(Ctx *c, hipEvent_t **ev) {
   return 0;
 }
 
-// The detect's A/B and diagnostic environment knobs, all
-// read once at the first use of any of them.  None is a product setting.
-struct DetectEnv {
-  int home_rec;        // BSA_HOME_REC=0/1: home mode stores fp64 column records (-1: home_records' rule)
-  bool stage1_t0;      // BSA_STAGE1_T0!=0: stage 1 at the t = 0 points, not the look-ahead midpoints
-  bool tp_super;       // BSA_TP_SUPER=1: K0d as k_tilepairs (super-tiles) at every size
-  bool k0z;            // BSA_K0Z=1: K0z always launched, never left to the last detect's K2
-  bool tp_halo_all;    // BSA_TP_HALO_ALL=1: halo mode's K0d sweeps all column tiles, not the present ones
-  bool tpr;            // BSA_TPR=0: no tile-pair list reuse
-  bool hk_trace;       // BSA_HK_TRACE=1: one stderr line per host-known rebuild decision (diagnostics)
-  double tpr_sh;       // BSA_TPR_SH>0: the kept list's horizontal budget [m]
-  int pf_pieces;       // BSA_PF_PIECES=1/2/4/8: units per prefilter item
-  int pf_heavy_t0;     // BSA_PF_HEAVY_T0=0..3: PfKnobs::t0
-  int pf_pieces_near;  // BSA_PF_PIECES_NEAR=1/2/4/8: units per near item
-  int fuse_exact;      // BSA_FUSE_EXACT=0/1: K1b fused into the prefilter (-1: detect_decide's rule)
-  int ov_grid_a;       // BSA_OV_GRID_A: workgroups per CU of the overlap's own-tile sweep (<= 0: the whole grid)
-  int k1b_grid;        // BSA_K1B_GRID>0: K1b's grid
-};
-static const DetectEnv &detect_env() {
+// the environment knobs (DetectEnv, bsa_internal.h)
+const DetectEnv &detect_env() {
   static const DetectEnv env = [] {
     const auto num = [](const char *name, int unset) {
       const char *s = getenv(name);
       return s ? atoi(s) : unset;
     };
     const char *sh = getenv("BSA_TPR_SH");
+    const int k4b = num("BSA_K4_BLOCK", 64);
     return DetectEnv{num("BSA_HOME_REC", -1),
                      num("BSA_STAGE1_T0", 0) != 0,
                      num("BSA_TP_SUPER", 0) == 1,
@@ -2519,7 +2485,10 @@ static const DetectEnv &detect_env() {
                      num("BSA_PF_PIECES_NEAR", 0),
                      num("BSA_FUSE_EXACT", -1),
                      num("BSA_OV_GRID_A", 2),
-                     num("BSA_K1B_GRID", 0)};
+                     num("BSA_K1B_GRID", 0),
+                     num("BSA_K24", 1) != 0,
+                     (k4b == 64 || k4b == 128 || k4b == 256) ? k4b : 64,
+                     num("BSA_SIM_PREP", 1) != 0};
   }();
   return env;
 }
@@ -2585,18 +2554,21 @@ static int launch_prep_cols(Ctx *c, hipStream_t stream, unsigned grid, const Pre
   return 0;
 }
 
+bool ensure_col_prep(Ctx *c, int64_t n, bool rec) {
+  return (!rec || ensure(c, c->colrec, n * sizeof(ColRec), "column records")) &&
+         ensure(c, c->pfcol, n * sizeof(PFRec), "prefilter columns") &&
+         ensure(c, c->pfvcol, n * sizeof(PFVel), "prefilter column velocities") &&
+         ensure(c, c->pfpcol, n * sizeof(float4), "prefilter column positions") &&
+         ensure(c, c->tbox_c, ((n + kTile - 1) / kTile) * sizeof(TileBox), "column tile boxes") &&
+         ensure(c, c->gbox_c, ((n + kGroup - 1) / kGroup) * sizeof(TileBox), "column group boxes") &&
+         ensure(c, c->sbox_c, ((n + kSub - 1) / kSub) * sizeof(TileBox), "column sub-group boxes");
+}
+
 int prep_all_tiles(Ctx *c, double rpz, double hpz, double tla, unsigned long long nf_epoch) {
   const int64_t n = c->n;
   if (n <= 0) return 0;
   const int nct = (int)((n + kTile - 1) / kTile);
-  if (!ensure(c, c->colrec, n * sizeof(ColRec), "column records") ||
-      !ensure(c, c->pfcol, n * sizeof(PFRec), "prefilter columns") ||
-      !ensure(c, c->pfvcol, n * sizeof(PFVel), "prefilter column velocities") ||
-      !ensure(c, c->pfpcol, n * sizeof(float4), "prefilter column positions") ||
-      !ensure(c, c->tbox_c, nct * sizeof(TileBox), "column tile boxes") ||
-      !ensure(c, c->gbox_c, ((n + kGroup - 1) / kGroup) * sizeof(TileBox), "column group boxes") ||
-      !ensure(c, c->sbox_c, ((n + kSub - 1) / kSub) * sizeof(TileBox), "column sub-group boxes"))
-    return -1;
+  if (!ensure_col_prep(c, n, true)) return -1;
   // home order, no stored fp64 records, every tile with its fused boxes
   PrepColsLaunch a;
   a.n = (int)n;
@@ -2611,30 +2583,7 @@ int prep_all_tiles(Ctx *c, double rpz, double hpz, double tla, unsigned long lon
   return launch_prep_cols(c, c->stream, (unsigned)nct, a);
 }
 
-// k_rank_rows' arguments (kept for a fused launch, k24_launch)
-struct RankLaunch {
-  unsigned grid;
-  int nrows;
-  Counters *cnt;
-  unsigned long long cap;
-  unsigned *rowoff, *rowcnt;
-  const uint2 *kb;
-  int B;
-  const double *cpay;
-  int rb;
-  int *ci, *cj;
-  double *out;
-  int *li, *lj;
-  unsigned long long *stats, *gate;
-  const unsigned *build;
-  MvpFuse mf;
-  unsigned char *inconf;
-  unsigned long long *tcpamax;
-  Counters *cnext;
-  unsigned long long *wnext;
-  NfArgs nf;
-  unsigned long long *hkp;  // HK: the prediction word K2 moves into gate[2] (NULL: none / fused K4' publishes it)
-};
+// one K2 launch (k_rank_rows; RankLaunch: bsa_internal.h), alone or fused with the step's K4'
 static int rank_launch(Ctx *c, const RankLaunch &a, bool k24, const K24Args &ka) {
   const auto K = k24 ? k_rank_rows<true> : k_rank_rows<false>;
   hipLaunchKernelGGL(K, dim3(a.grid), dim3(kRankThreads), 0, c->stream, a.nrows, a.cnt, a.cap, a.rowoff, a.rowcnt,
@@ -2688,8 +2637,9 @@ static int ov_init(Ctx *c) {
   return 0;
 }
 
-// ---- one detect: DetectPlan (every decision, taken by detect_decide before
-// the first stream operation), DetectRun (the device pointers the stages
+// ---- one detect: DetectPlan (every decision, taken by detect_decide from the
+// DetectRequest and the context's state before the first stream operation),
+// DetectRun (the request, the result and the device pointers the stages
 // share), one function per stage, detect_enqueue runs them in order
 struct DetectPlan {
   double rpz, hpz, tla;
@@ -2801,7 +2751,8 @@ struct DetectPlan {
 struct DetectRun {
   Ctx *c;
   const DetectPlan &p;
-  unsigned long long *gate;  // (device, nullable): receives {overflow, P} for the resident sim step
+  const DetectRequest &q;
+  DetectResult &res;
   SoA6 own, intr;
   Counters *dcnt;
   NfArgs nfa;
@@ -2858,8 +2809,8 @@ struct DetectRun {
 };
 
 // HK (see DetectPlan::hk): the host's rebuild decision for this detect
-static int decide_hk(Ctx *c, DetectPlan &p) {
-  if (p.tpr && c->hk_req && c->hk_on && !c->simp.resume_nav && c->hk_hdev) {
+static int decide_hk(Ctx *c, DetectPlan &p, bool host_decides) {
+  if (p.tpr && host_decides && c->hk_on && !c->simp.resume_nav && c->hk_hdev) {
     if (c->hk_cool > 0) {  // after a stale abort: device-decided for a while
       c->hk_cool--;
       c->hk_ok = false;
@@ -2888,9 +2839,6 @@ static int decide_hk(Ctx *c, DetectPlan &p) {
   } else if (p.tpr) {
     c->hk_ok = false;  // a device-decided detect: the build history is no longer the host's
   }
-  c->hk_cur = p.hk;
-  c->hk_keep = p.hkeep;
-  c->hk_last = p.hm;
   return 0;
 }
 
@@ -2963,12 +2911,13 @@ static int decide_launch(Ctx *c, DetectPlan &p) {
 
 // Every decision of one detect and the host bookkeeping that goes with them,
 // before anything of it is enqueued (the field comments of DetectPlan say why)
-static int detect_decide(Ctx *c, double rpz, double hpz, double tla, int flags, int64_t rb, int64_t re,
-                         DetectPlan *plan) {
+static int detect_decide(Ctx *c, const DetectRequest &q, DetectPlan *plan) {
   const DetectEnv &env = detect_env();
   DetectPlan &p = *plan;
   p = DetectPlan{};
-  c->fuse_done = false;  // set again only if K2 evaluates MVP's per-pair vectors
+  const double rpz = q.rpz, hpz = q.hpz, tla = q.tla;
+  const int flags = q.flags;
+  int64_t rb = q.rb, re = q.re;
   const int64_t n = c->n;
   if (re <= 0) re = n;
   if (rb < 0 || rb > re || re > n)
@@ -2999,7 +2948,7 @@ static int detect_decide(Ctx *c, double rpz, double hpz, double tla, int flags, 
   p.re = re;
   p.nrows = nrows;
   p.distinct = c->has_intruder;
-  p.home = c->det_home;
+  p.home = q.home;
   c->last_home = p.home;
   p.halo = p.home && c->halo_mode != 0;
   p.a0 = (int)(rb / kTile);
@@ -3019,13 +2968,13 @@ static int detect_decide(Ctx *c, double rpz, double hpz, double tla, int flags, 
               c->sim_prep_key[3] == (double)p.mid && c->sim_prep_n == n;
   c->sim_prepped = false;
   if (!nonfin_word(c)) return -1;
-  p.nf_epoch = p.prepped ? c->nf_prep_epoch : (c->nf_force_epoch ? c->nf_force_epoch : ++c->nf_counter);
+  p.nf_epoch = p.prepped ? c->nf_prep_epoch : (q.nf_epoch ? q.nf_epoch : ++c->nf_counter);
   p.tp_list = p.halo && !env.tp_halo_all && !env.tp_super;
   p.tpr = env.tpr && c->tpr_on && p.home && !p.reuse && flags == 0 && !env.tp_super &&
           ((!p.halo && p.prepped && (n + kTile - 1) / kTile <= kTPDirectMax) || p.tp_list);
   const double tkey[6] = {rpz, hpz, tla, (double)p.mid, (double)rb, (double)re};
   p.tvalid = p.tpr && c->tpr_valid && c->tpr_n == n && memcmp(tkey, c->tpr_key, sizeof tkey) == 0;
-  if (decide_hk(c, p)) return -1;
+  if (decide_hk(c, p, q.host_decides)) return -1;
   if (p.tpr) {  // (every rank, also one without rows: the kept state stays collective)
     c->tpr_valid = true;  // (an aborted step or any state change clears it)
     memcpy(c->tpr_key, tkey, sizeof tkey);
@@ -3066,7 +3015,7 @@ static int detect_empty(const DetectRun &R) {
     }
     if (halo_mid(c, p.rb, p.re, &hu, nullptr, p.hkeep)) return -1;
   }
-  if (R.gate) BSA_HIP(c, hipMemsetAsync(R.gate, 0, kGateWords * 8, c->stream));
+  if (R.q.gate) BSA_HIP(c, hipMemsetAsync(R.q.gate, 0, kGateWords * 8, c->stream));
   for (int e = 1; e < 5; ++e)
     if (R.mark(e)) return -1;
   c->ev_valid = c->ev_valid || p.timed;
@@ -3133,11 +3082,7 @@ static int detect_buffers(DetectRun &R) {
       !ensure(c, c->out_cj, cap * 4, "cj") || !ensure(c, c->out_pay, cap * 5 * 8, "conflict outputs") ||
       !ensure(c, c->out_li, cap * 4, "li") || !ensure(c, c->out_lj, cap * 4, "lj"))
     return -1;
-  if (!ensure(c, c->colrec, n * sizeof(ColRec), "column records") ||
-      !ensure(c, c->pfcol, n * sizeof(PFRec), "prefilter columns") ||
-      !ensure(c, c->pfvcol, n * sizeof(PFVel), "prefilter column velocities") ||
-      !ensure(c, c->pfpcol, n * sizeof(float4), "prefilter column positions"))
-    return -1;
+  if (!ensure_col_prep(c, n, true)) return -1;
   if (!p.shared && (!ensure(c, c->rowrec, nrows * sizeof(RowRec), "row records") ||
                     !ensure(c, c->pfrow, nrows * sizeof(PFRec), "prefilter rows") ||
                     !ensure(c, c->pfvrow, nrows * sizeof(PFVel), "prefilter row velocities") ||
@@ -3148,11 +3093,7 @@ static int detect_buffers(DetectRun &R) {
   R.pfrow = p.shared ? (const PFRec *)c->pfcol.p + roff : (const PFRec *)c->pfrow.p;
   R.pfvrow = p.shared ? (const PFVel *)c->pfvcol.p + roff : (const PFVel *)c->pfvrow.p;
   R.pfprow = p.shared ? (const float4 *)c->pfpcol.p + roff : (const float4 *)c->pfprow.p;
-  if (!ensure(c, c->tbox_c, p.nct * sizeof(TileBox), "column tile boxes") ||
-      !ensure(c, c->gbox_c, p.ngc * sizeof(TileBox), "column group boxes") ||
-      !ensure(c, c->sbox_c, p.nsc * sizeof(TileBox), "column sub-group boxes") ||
-      !ensure(c, c->tilepairs, (size_t)p.ntp * kSlicesPerTile * sizeof(uint2), "prefilter items"))
-    return -1;
+  if (!ensure(c, c->tilepairs, (size_t)p.ntp * kSlicesPerTile * sizeof(uint2), "prefilter items")) return -1;
   return 0;
 }
 
@@ -3464,23 +3405,21 @@ static int detect_rank(DetectRun &R) {
                        (unsigned long long *)c->lkey2.p);
     BSA_HIP(c, hipGetLastError());
   }
+  const DetectRequest &q = R.q;
   MvpFuse mf{};
-  c->fuse_done = false;
-  c->fuse_rowdv = false;
-  if (c->fuse_mvp) {
+  if (q.mvp) {
     if (!ensure(c, c->mvp_pdv, std::max<unsigned long long>(cap, 1) * sizeof(double4), "mvp pair dv") ||
         !ensure(c, c->mvp_pfl, std::max<unsigned long long>(cap, 1), "mvp pair flags"))
       return -1;
-    mf.p = *c->fuse_mvp;
-    mf.in = MvpPairIn{c->fuse_gse, c->fuse_gsn, c->fuse_vs, c->fuse_alt, c->fuse_noreso,
-                      c->det_home ? (const unsigned *)c->id2h.p : nullptr};
+    mf.p = *q.mvp;
+    mf.in = MvpPairIn{q.gse, q.gsn, q.vs, q.alt, q.noreso, p.home ? (const unsigned *)c->id2h.p : nullptr};
     mf.pdv = (double4 *)c->mvp_pdv.p;
     mf.pfl = (uint8_t *)c->mvp_pfl.p;
-    c->fuse_done = true;
+    R.res.pairs_done = true;
     if (B) {  // K2 also folds each row's vectors (MvpIn::rowdv)
       if (!ensure(c, c->mvp_rowdv, (size_t)std::max(nrows, 1) * sizeof(double4), "mvp row dv")) return -1;
       mf.rowdv = (double4 *)c->mvp_rowdv.p;
-      c->fuse_rowdv = true;
+      R.res.rows_folded = true;
     }
   }
   if (B) {
@@ -3491,14 +3430,13 @@ static int detect_rank(DetectRun &R) {
     const RankLaunch rl{(unsigned)rank_blocks(nrows), nrows, R.dcnt, cap, (unsigned *)c->rowoff.p,
                         (unsigned *)c->rowcnt.p, (const uint2 *)c->kbuck.p, B, (const double *)c->cpay.p, rb,
                         (int *)c->out_ci.p, (int *)c->out_cj.p, (double *)c->out_pay.p, (int *)c->out_li.p,
-                        (int *)c->out_lj.p, (unsigned long long *)c->stats.p, R.gate, R.build, mf,
+                        (int *)c->out_lj.p, (unsigned long long *)c->stats.p, q.gate, R.build, mf,
                         (unsigned char *)c->inconf.p, (unsigned long long *)c->tcpamax.p,
                         (Counters *)c->counters2.p, (unsigned long long *)c->workq2.p, R.nfa, R.hk_word};
-    if (c->k24_want) {  // bsa_sim_step launches it fused with K4' (k24_launch)
-      c->k24_blob.resize(sizeof rl);
-      memcpy(c->k24_blob.data(), &rl, sizeof rl);
-      c->k24_pending = true;
-      c->k24_ev = p.timed ? p.ev[4] : nullptr;
+    if (q.keep_k2) {  // the step launches it fused with K4' (k24_launch)
+      R.res.k2 = rl;
+      R.res.k2_kept = true;
+      R.res.k2_ev = p.timed ? p.ev[4] : nullptr;
     } else {
       rank_launch(c, rl, false, K24Args{});
     }
@@ -3509,19 +3447,22 @@ static int detect_rank(DetectRun &R) {
                        (const unsigned *)c->cval2.p, (const double *)c->cpay.p,
                        (const unsigned long long *)c->lkey2.p, rb, (int *)c->out_ci.p, (int *)c->out_cj.p,
                        (double *)c->out_pay.p, (int *)c->out_li.p, (int *)c->out_lj.p,
-                       (unsigned long long *)c->stats.p, R.gate, R.build, mf, R.nfa, (unsigned long long *)c->tcpamax.p);
+                       (unsigned long long *)c->stats.p, q.gate, R.build, mf, R.nfa, (unsigned long long *)c->tcpamax.p);
   }
   BSA_HIP(c, hipGetLastError());
   return 0;
 }
 
 // Enqueue one complete detect on the stream (K0-K2), no host synchronisation.
-// gate (device, nullable): receives {overflow, P} for the resident sim step.
-int detect_enqueue(Ctx *c, double rpz, double hpz, double tla, int flags, int64_t rb, int64_t re,
-                   unsigned long long *gate) {
+// *res says what the detect did for its caller (DetectResult, bsa_internal.h).
+int detect_enqueue(Ctx *c, const DetectRequest &q, DetectResult *res) {
+  *res = DetectResult{};
   DetectPlan p;
-  if (detect_decide(c, rpz, hpz, tla, flags, rb, re, &p)) return -1;
-  DetectRun R{c, p, gate, soa(c->own), soa(p.distinct ? c->intr : c->own), (Counters *)c->counters.p,
+  if (detect_decide(c, q, &p)) return -1;
+  res->hk = p.hk;
+  res->hk_keep = p.hkeep;
+  res->hk_m = p.hm;
+  DetectRun R{c, p, q, *res, soa(c->own), soa(p.distinct ? c->intr : c->own), (Counters *)c->counters.p,
               NfArgs{(unsigned long long *)c->nonfin.p, p.nf_epoch, nullptr}};
   if (R.mark(0)) {
     c->reuse_valid = false;  // (detect_decide's optimistic mark: nothing of this detect is enqueued)
@@ -3532,20 +3473,15 @@ int detect_enqueue(Ctx *c, double rpz, double hpz, double tla, int flags, int64_
   if (detect_prefilter(R) || R.mark(2)) return -1;
   if (detect_exact(R) || R.mark(3)) return -1;
   if (detect_rank(R)) return -1;
-  if (!c->k24_pending && R.mark(4)) return -1;
+  if (!res->k2_kept && R.mark(4)) return -1;
   c->ev_valid = c->ev_valid || p.timed;
   return 0;
 }
 
-// the K2 launch kept by detect_enqueue, fused with the step's K4'
-int k24_launch(Ctx *c, const K24Args &ka) {
-  if (!c->k24_pending || c->k24_blob.size() != sizeof(RankLaunch)) return fail(c, "internal: no K2 launch to fuse");
-  RankLaunch rl;
-  memcpy(&rl, c->k24_blob.data(), sizeof rl);
-  c->k24_pending = false;
-  if (rank_launch(c, rl, true, ka)) return -1;
-  if (c->k24_ev) BSA_HIP(c, hipEventRecord(c->k24_ev, c->stream));
-  c->k24_ev = nullptr;
+// the K2 launch a detect kept (DetectResult::k2), fused with the step's K4'
+int k24_launch(Ctx *c, const RankLaunch &k2, hipEvent_t k2_ev, const K24Args &ka) {
+  if (rank_launch(c, k2, true, ka)) return -1;
+  if (k2_ev) BSA_HIP(c, hipEventRecord(k2_ev, c->stream));
   return 0;
 }
 
@@ -3627,10 +3563,10 @@ int detect_finish(Ctx *c, bool *retry) {
   return 0;
 }
 
-int detect(Ctx *c, double rpz, double hpz, double tla, int flags, int64_t rb, int64_t re,
-           int64_t *n_conf, int64_t *n_los) {
+int detect(Ctx *c, const DetectRequest &q, int64_t *n_conf, int64_t *n_los) {
+  DetectResult res;  // (nothing of it is the standalone caller's)
   for (int attempt = 0;; ++attempt) {
-    if (detect_enqueue(c, rpz, hpz, tla, flags, rb, re, nullptr)) return -1;
+    if (detect_enqueue(c, q, &res)) return -1;
     bool retry = false;
     if (detect_finish(c, &retry)) return -1;
     if (!retry) break;

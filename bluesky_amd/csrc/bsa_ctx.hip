@@ -582,7 +582,7 @@ int bsa_detect(bsa_ctx *c, double rpz, double hpz, double tla, int flags, int64_
     return bsa::fail(c, "bsa_detect on a context whose state is a resident sim's (home order): "
                         "bsa_set_state first, or use another context");
   BSA_HIP(c, hipSetDevice(c->device));
-  return bsa::detect(c, rpz, hpz, tla, flags, row_begin, row_end, n_conf, n_los);
+  return bsa::detect(c, bsa::DetectRequest{rpz, hpz, tla, flags, row_begin, row_end}, n_conf, n_los);
 }
 
 int bsa_fetch_pairs(bsa_ctx *c, int32_t *ci, int32_t *cj, double *qdr, double *dist, double *tcpa,

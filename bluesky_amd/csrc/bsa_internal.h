@@ -224,6 +224,7 @@ struct Ctx {
   DevBuf counters;           // Counters
   DevBuf counters2, workq2;  // the next detect's counters / dequeue words (double-buffered, zeroed by K2)
   int64_t zeroed_rows = -1;  // rows of the last detect whose K2 zeroed counters2 / workq2 / rowcnt, or -1
+                             // (state: the next detect of that many rows skips its K0z)
   DevBuf cand;               // uint2 (i, j)
   DevBuf cflag;              // per candidate: bit0 conflict, bit1 LoS
   unsigned long long cand_cap = 0;
@@ -278,12 +279,10 @@ struct Ctx {
   // checks every record against the full budgets: one outside aborts the step
   // (Counters::tpr_stale) and it re-runs with a build.
   bool hk_on = true;                   // BSA_HK=0: the device decides (round-5 behaviour)
-  bool hk_req = false;                 // bsa_sim_step: the detect being enqueued may be host-decided
+  // (state: the decisions of one host-decided detect are read by the next ones)
   bool hk_ok = false;                  // the build history below is this sim's
   bool hk_built[4] = {false, false, false, false};  // build decisions of detects m & 3
-  bool hk_cur = false, hk_keep = false;  // the last detect_enqueue was host-decided / kept its list
   int64_t hk_m = 0;                    // index of the next host-decided detect
-  int64_t hk_last = 0;                 // ... of the last one (its K4' publishes slot hk_last % kHkRing)
   int64_t hk_cool = 0;                 // after a stale abort: device-decided detects left
   int64_t hk_cool_len = 32;            // ... the next such stretch (doubles per stale abort, <= 4096):
                                        // a workload whose lists go stale often ends up device-decided
@@ -353,27 +352,19 @@ struct Ctx {
   // and the detect reads its columns without a gather or a re-sort.  lpos[r]:
   // position of home sim_rb + r among the rank's rows sorted by aircraft index.
   bool home = false;                  // own[] and the sim arrays are in home order
-  bool det_home = false;              // detect_enqueue: home-ordered state (set by sim_cd)
   bool last_home = false;             // the last detect's ci / li are home rows (fetch translates)
   DevBuf h2id, id2h;                  // u32, device
   DevBuf lbyidx;                      // u32, device: this rank's home rows (relative) in ascending index order
   DevBuf fetch_stage;                 // fetch_pairs of a home-order detect: the lists re-ordered on the device
   std::vector<unsigned> h2id_h, id2h_h, lpos_h;  // host copies
   bool sim_ready = false;
-  bool mvp_deferred = false;            // this step's K3 rows run inside K4' (sim_cd -> bsa_sim_step)
-  std::vector<unsigned char> mvp_defer;  // the deferred K3 arguments (MvpIn, bsa_mvp_row.h)
-  // K2 fused with K4' (one rank): sim_cd asks (k24_want), detect_enqueue then
-  // keeps its K2 launch (k24_blob) for k24_launch, with the timed detect's
-  // last stage event; alt / vs / gseast / gsnorth double buffers
-  bool k24_want = false, k24_pending = false;
-  std::vector<unsigned char> k24_blob;
-  hipEvent_t k24_ev = nullptr;
-  DevBuf nx_alt, nx_vs, nx_gse, nx_gsn;
+  DevBuf nx_alt, nx_vs, nx_gse, nx_gsn;  // K2 fused with K4' (one rank): alt / vs / gseast / gsnorth double buffers
   bsa_sim_params simp{};
   int64_t sim_steps = 0, sim_cd_calls = 0, sim_rb = 0, sim_re = 0, sim_rpr = 0;
   int64_t sim_last_conf = 0, sim_last_los = 0;
   bool sim_gathered = true;  // replicas consistent with every rank's rows
   bool sim_gs_derivable = false;  // gseast / gsnorth of every row follow from gs / trk (K4' without wind ran)
+  // (state: written by a step's K4', consumed or invalidated by whichever detect comes next)
   bool sim_prepped = false;       // the last K4' wrote the next detect's column records / boxes (one rank)
   double sim_prep_key[4] = {0, 0, 0, 0};  // ... for rpz, hpz, tla, stage-1 mode
   int64_t sim_prep_n = 0;
@@ -388,8 +379,6 @@ struct Ctx {
   DevBuf nonfin;
   DevBuf rownf;  // rows of their own (not columns): per row (index order), its position / velocity is not finite
   unsigned long long nf_counter = 0, nf_prep_epoch = 0;  // epochs (K0b: a new one; K4' prep: the next detect's)
-  unsigned long long nf_force_epoch = 0;  // != 0: the epoch the next detects take (bsa_sim_detect_rows: the
-                                         // records of every tile, prepared first, carry it)
   DevBuf sim_ctl;  // [0,24) gate {abort / non-finite, P, HK prediction}; [24,28) sticky abort; [32,40) steps
                    // done; [40,48) resopairs demand on a bookkeeping overflow; [48,56) pair-key
                    // block demand (several ranks); [56,64) an HK-kept list went stale in the batch
@@ -434,13 +423,6 @@ struct Ctx {
   DevBuf wfield;
   int64_t wf_nvec = 0;
 
-  // resident step: per-pair MVP vectors evaluated inside K2 (k_rank) when set
-  // (sim_cd sets it around detect_enqueue; full-N device arrays)
-  const bsa_mvp_params *fuse_mvp = nullptr;
-  const double *fuse_gse = nullptr, *fuse_gsn = nullptr, *fuse_vs = nullptr, *fuse_alt = nullptr;
-  bool fuse_done = false;  // the last detect_enqueue produced the per-pair vectors
-  bool fuse_rowdv = false;  // ... and folded them per row (k_rank_rows: mvp_rowdv)
-
   // standalone geo matrices (bsa_geo.hip)
   DevBuf geo_in, geo_pts, geo_out;
   hipEvent_t geo_ev[2] = {nullptr, nullptr};
@@ -480,7 +462,6 @@ struct Ctx {
   DevBuf s_atm;          // traf.p / rho / Temp = vatmos(traf.alt) of the last step (3 x n), when on
   bool sim_atmos = false;
   bool sim_noreso = false, sim_resooff = false;
-  const uint8_t *fuse_noreso = nullptr;  // NORESO list for K2's fused MVP per-pair vectors
   int64_t sim_ntypes = 0;
   void *feed_host = nullptr;
   size_t feed_host_bytes = 0;
@@ -499,11 +480,13 @@ struct MvpDev {
   double *o_tsolv;
 };
 struct MvpIn;
-// defer != NULL (resident step): the per-row kernel is not launched; its
-// arguments go to *defer for the fused MVP + pilot + kinematics kernel
+// pairs_done / rows_folded: K2 of the same detect wrote the per-pair vectors /
+// folded them per row (DetectResult).  defer != NULL (resident step): the
+// per-row kernel is not launched; its arguments go to *defer for the fused
+// MVP + pilot + kinematics kernel
 int mvp_device(Ctx *c, const bsa_mvp_params &p, const MvpDev &d, const unsigned *seg,
                const unsigned long long *gate, unsigned *sticky, const uint8_t *inconf, uint8_t *active,
-               bool resolve, bool pairs_done = false, MvpIn *defer = nullptr);
+               bool resolve, bool pairs_done = false, bool rows_folded = false, MvpIn *defer = nullptr);
 
 // device pointers for the fused kinematics kernel
 struct KinDev {
@@ -572,6 +555,9 @@ const unsigned *halo_list_count(const Ctx *c);  // the probe's halo list length 
 // every column tile's records and boxes (one K0b); nf_epoch != 0: non-finite
 // columns store it into Ctx::nonfin (the detect that takes that epoch sees them)
 int prep_all_tiles(Ctx *c, double rpz, double hpz, double tla, unsigned long long nf_epoch = 0);
+// the buffers a preparer of n columns writes (K0b, or K4' for the next detect):
+// colrec (rec only), pfcol, pfvcol, pfpcol and the tile / group / sub-group boxes
+bool ensure_col_prep(Ctx *c, int64_t n, bool rec);
 
 // exclusive prefix sum of n words, one launch (bsa_cd.hip)
 int scan_excl(Ctx *c, const unsigned *in, unsigned *out, int n);
@@ -620,13 +606,109 @@ void sim_release(Ctx *c);
 void feed_release(Ctx *c);
 int sim_adopt_pairs(Ctx *c);  // after resident steps: the last CD call's pairs become fetchable
 
-// detect entry points (bsa_cd.hip): detect = enqueue + finish (+ retries)
-int detect(Ctx *c, double rpz, double hpz, double tla, int flags, int64_t rb, int64_t re,
-           int64_t *n_conf, int64_t *n_los);
+// ---- one detect (bsa_cd.hip): what the caller asks for and what it gets back.
+// Everything a detect honours is in its DetectRequest; nothing of one call is
+// left on the context for the next.
+// Non-finite tcpa inputs (Ctx::nonfin): producers (the column records'
+// makers) store `epoch` into *word when a column's position or velocity is
+// non-finite; K2 makes every row's tcpamax NaN when *word == epoch, and a
+// row's own when rowbad[row] is set (rows of their own, written by
+// k_prep_rows in index order; NULL when the rows are columns)
+struct NfArgs {
+  unsigned long long *word;
+  unsigned long long epoch;
+  const uint8_t *rowbad;
+};
+// full-N traffic arrays MVP's per-pair vector reads (bsa_mvp_math.h)
+struct MvpPairIn {
+  const double *gseast, *gsnorth, *vs, *alt;
+  const uint8_t *noreso;  // NULL = empty NORESO list
+  const unsigned *id2h;   // resident step (home order): the intruder's home position; NULL = identity
+};
+// MVP's per-pair vectors written by k_rank in the resident step (pdv == NULL: off)
+struct MvpFuse {
+  bsa_mvp_params p;
+  MvpPairIn in;
+  double4 *pdv;
+  uint8_t *pfl;
+  double4 *rowdv;  // k_rank_rows: each row's folded dv (mvp_fold), or NULL
+};
+// k_rank_rows' arguments (a value, so that the step can launch K2 fused with its K4': k24_launch)
+struct RankLaunch {
+  unsigned grid;
+  int nrows;
+  Counters *cnt;
+  unsigned long long cap;
+  unsigned *rowoff, *rowcnt;
+  const uint2 *kb;
+  int B;
+  const double *cpay;
+  int rb;
+  int *ci, *cj;
+  double *out;
+  int *li, *lj;
+  unsigned long long *stats, *gate;
+  const unsigned *build;
+  MvpFuse mf;
+  unsigned char *inconf;
+  unsigned long long *tcpamax;
+  Counters *cnext;
+  unsigned long long *wnext;
+  NfArgs nf;
+  unsigned long long *hkp;  // HK: the prediction word K2 moves into gate[2] (NULL: none / fused K4' publishes it)
+};
+struct DetectRequest {
+  double rpz = 0.0, hpz = 0.0, tla = 0.0;
+  int flags = 0;
+  int64_t rb = 0, re = 0;              // rows (re <= 0: all)
+  unsigned long long *gate = nullptr;  // (device, nullable): receives {overflow, P, HK prediction} for the resident step
+  bool home = false;                   // own[] is in home order (the resident sim's state), rows a 512-aligned home slice
+  bool host_decides = false;           // HK: the tile-pair list's build / keep decision may be the host's
+  unsigned long long nf_epoch = 0;     // != 0: the non-finite epoch this detect takes (records prepared by the caller carry it)
+  // != NULL: K2 evaluates MVP's per-pair vectors as it places each pair (full-N device arrays)
+  const bsa_mvp_params *mvp = nullptr;
+  const double *gse = nullptr, *gsn = nullptr, *vs = nullptr, *alt = nullptr;
+  const uint8_t *noreso = nullptr;     // NORESO list or NULL
+  bool keep_k2 = false;                // K2 (k_rank_rows) is not launched but returned, for a launch fused with K4'
+};
+struct DetectResult {
+  bool pairs_done = false;   // K2 produced MVP's per-pair vectors
+  bool rows_folded = false;  // ... and folded them per row (Ctx::mvp_rowdv)
+  bool hk = false, hk_keep = false;  // the detect was host-decided / kept its list
+  int64_t hk_m = 0;          // its number (the step's K4' publishes ring slot hk_m % kHkRing)
+  bool k2_kept = false;      // K2 was kept (DetectRequest::keep_k2; not with bucket width 0):
+  RankLaunch k2;             // its launch, and the timed detect's last stage event
+  hipEvent_t k2_ev = nullptr;  // (or NULL) to record behind it
+};
+// detect = enqueue + finish, retried with the same request while a buffer overflowed
+int detect(Ctx *c, const DetectRequest &q, int64_t *n_conf, int64_t *n_los);
 bool nonfin_word(Ctx *c);  // Ctx::nonfin allocated (zeroed when new)
-int detect_enqueue(Ctx *c, double rpz, double hpz, double tla, int flags, int64_t rb, int64_t re,
-                   unsigned long long *gate);
+int detect_enqueue(Ctx *c, const DetectRequest &q, DetectResult *res);
 int detect_finish(Ctx *c, bool *retry);
+// the detect's and the resident step's A/B and diagnostic environment knobs
+// (DESIGN.md 3.19), all read once at the first use of any of them.  None is a
+// product setting.
+struct DetectEnv {
+  int home_rec;        // BSA_HOME_REC=0/1: home mode stores fp64 column records (-1: home_records' rule)
+  bool stage1_t0;      // BSA_STAGE1_T0!=0: stage 1 at the t = 0 points, not the look-ahead midpoints
+  bool tp_super;       // BSA_TP_SUPER=1: K0d as k_tilepairs (super-tiles) at every size
+  bool k0z;            // BSA_K0Z=1: K0z always launched, never left to the last detect's K2
+  bool tp_halo_all;    // BSA_TP_HALO_ALL=1: halo mode's K0d sweeps all column tiles, not the present ones
+  bool tpr;            // BSA_TPR=0: no tile-pair list reuse
+  bool hk_trace;       // BSA_HK_TRACE=1: one stderr line per host-known rebuild decision and step abort (diagnostics)
+  double tpr_sh;       // BSA_TPR_SH>0: the kept list's horizontal budget [m]
+  int pf_pieces;       // BSA_PF_PIECES=1/2/4/8: units per prefilter item
+  int pf_heavy_t0;     // BSA_PF_HEAVY_T0=0..3: PfKnobs::t0
+  int pf_pieces_near;  // BSA_PF_PIECES_NEAR=1/2/4/8: units per near item
+  int fuse_exact;      // BSA_FUSE_EXACT=0/1: K1b fused into the prefilter (-1: detect_decide's rule)
+  int ov_grid_a;       // BSA_OV_GRID_A: workgroups per CU of the overlap's own-tile sweep (<= 0: the whole grid)
+  int k1b_grid;        // BSA_K1B_GRID>0: K1b's grid
+  // the resident step (bsa_sim.hip: step_decide)
+  bool k24;            // BSA_K24=0: K2 and K4' as two launches
+  int k4_block;        // BSA_K4_BLOCK=64/128/256: K4' workgroup size (anything else: 64)
+  bool sim_prep;       // BSA_SIM_PREP=0: K4' does not prepare the next detect's records
+};
+const DetectEnv &detect_env();
 #ifdef BSA_PF_TRACE
 int pf_trace_dump(Ctx *c, unsigned long long groups, unsigned long long tiles);  // (diagnostic builds)
 #endif

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void k_mvp_row(int rb, bsa_mvp_params p, MvpIn
 // gate / sticky / inconf / active: resident sim step only.
 int mvp_device(Ctx *c, const bsa_mvp_params &p, const MvpDev &d, const unsigned *seg,
                const unsigned long long *gate, unsigned *sticky, const uint8_t *inconf, uint8_t *active,
-               bool resolve, bool pairs_done, MvpIn *defer) {
+               bool resolve, bool pairs_done, bool rows_folded, MvpIn *defer) {
   const int64_t rb = c->last_rb, re = c->last_re, nrows = std::max<int64_t>(re - rb, 0);
   if (nrows == 0 && !gate) return 0;  // (a resident rank without rows still applies the gate)
   const unsigned long long pcap = std::max<unsigned long long>(c->cand_cap, (unsigned long long)c->last_conf);
@@ -123,7 +123,7 @@ int mvp_device(Ctx *c, const bsa_mvp_params &p, const MvpDev &d, const unsigned 
   in.pdv = (double4 *)c->mvp_pdv.p;
   in.pfl = (uint8_t *)c->mvp_pfl.p;
   // K2 of the same detect folded each row's vectors (k_rank_rows)
-  in.rowdv = pairs_done && c->fuse_rowdv && resolve ? (const double4 *)c->mvp_rowdv.p : nullptr;
+  in.rowdv = pairs_done && rows_folded && resolve ? (const double4 *)c->mvp_rowdv.p : nullptr;
   in.gate = gate;
   in.sticky = sticky;
   in.inconf = inconf;

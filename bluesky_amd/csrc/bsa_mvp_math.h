@@ -9,13 +9,7 @@
 
 namespace bsa {
 
-// full-N traffic arrays the per-pair vector reads
-struct MvpPairIn {
-  const double *gseast, *gsnorth, *vs, *alt;
-  const uint8_t *noreso;  // NULL = empty NORESO list
-  const unsigned *id2h;   // resident step (home order): the intruder's home position; NULL = identity
-};
-
+// (MvpPairIn, the full-N traffic arrays the per-pair vector reads: bsa_internal.h)
 // dv = (dv1, dv2, dv3, tsolV); fl: bit 0 subtract from dv[id1], bit 1 add back (NORESO).
 // id1 indexes the arrays; id2 is the intruder's aircraft index (mapped by id2h)
 __device__ __forceinline__ void mvp_pair(const bsa_mvp_params &p, const MvpPairIn &in, int id1, int id2,

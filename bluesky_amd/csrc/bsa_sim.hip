@@ -398,10 +398,19 @@ void set_rank_rows(Ctx *c) {
   c->sim_re = std::min<int64_t>(n, c->sim_rb + c->sim_rpr);
 }
 
-// one CD step of the batch (enqueue only).  allow_defer: K3's per-row part may
-// run inside the step's K4' (k_sim_pilot_kin<true>); a CD call without
-// kinematics (bsa_sim_cd) launches it itself.
-static int sim_cd(Ctx *c, bool allow_defer) {
+// what one CD call hands to the step that enqueued it
+struct CdOut {
+  DetectResult det;           // (its kept K2 launch, its HK decision)
+  bool mvp_deferred = false;  // K3's rows run inside the step's K4', with
+  MvpIn mv{};                 // ... these arguments
+};
+
+// one CD call (enqueue only).  in_step (a CD step of bsa_sim_step): K3's
+// per-row part may run inside the step's K4' (k_sim_pilot_kin<true>), which
+// also publishes a host-decided detect's prediction, so the host may decide
+// the list; a CD call without kinematics (bsa_sim_cd) launches K3 itself.
+// keep_k2: the detect's K2 is left to the step too (StepPlan::k24).
+static int sim_cd(Ctx *c, bool in_step, bool keep_k2, CdOut *out) {
   const bsa_sim_params &p = c->simp;
   // several ranks: the detect's halo exchange (bsa_halo.hip) refreshes the
   // other ranks' rows this rank reads; one rank holds everything
@@ -409,22 +418,21 @@ static int sim_cd(Ctx *c, bool allow_defer) {
   unsigned long long *gate = (unsigned long long *)c->sim_ctl.p;
   const uint8_t *noreso = c->sim_noreso ? (const uint8_t *)c->s_noreso.p : nullptr;
   const uint8_t *resooff = c->sim_resooff ? (const uint8_t *)c->s_resooff.p : nullptr;
+  DetectRequest q{p.rpz, p.hpz, p.tla, 0, c->sim_rb, c->sim_re, gate};
+  q.home = true;
+  q.host_decides = in_step;
+  q.keep_k2 = keep_k2;
   // MVP's per-pair vectors are evaluated by K2 as it places each pair;
   // k_mvp_row folds them after the gate
   if (p.reso) {
-    c->fuse_mvp = &p.mvp;
-    c->fuse_gse = (const double *)c->s_gse.p;
-    c->fuse_gsn = (const double *)c->s_gsn.p;
-    c->fuse_vs = (const double *)c->own[5].p;
-    c->fuse_alt = (const double *)c->own[4].p;
-    c->fuse_noreso = noreso;
+    q.mvp = &p.mvp;
+    q.gse = (const double *)c->s_gse.p;
+    q.gsn = (const double *)c->s_gsn.p;
+    q.vs = (const double *)c->own[5].p;
+    q.alt = (const double *)c->own[4].p;
+    q.noreso = noreso;
   }
-  c->det_home = true;
-  const int de = detect_enqueue(c, p.rpz, p.hpz, p.tla, 0, c->sim_rb, c->sim_re, gate);
-  c->det_home = false;
-  c->fuse_mvp = nullptr;
-  c->fuse_noreso = nullptr;
-  if (de) return -1;
+  if (detect_enqueue(c, q, &out->det)) return -1;
   c->sim_cd_calls++;
   unsigned *sticky = (unsigned *)((char *)c->sim_ctl.p + bsa::kSimCtlSticky);
   BkDev bk;
@@ -469,35 +477,84 @@ static int sim_cd(Ctx *c, bool allow_defer) {
   // K3 (+ gate, + asas.active = inconf unless ResumeNav runs) on the detect's own row offsets
   // without the bookkeeping (which runs between K3 and K4') K3's rows are
   // deferred into K4' of this step (k_sim_pilot_kin<true>)
-  const bool defer = allow_defer && !p.resume_nav && c->sim_re > c->sim_rb;
-  MvpIn din{};
+  out->mvp_deferred = in_step && !p.resume_nav && c->sim_re > c->sim_rb;
   if (mvp_device(c, p.mvp, d, (const unsigned *)c->rowoff.p, gate, sticky,
                  p.resume_nav ? nullptr : (const uint8_t *)c->inconf.p, (uint8_t *)c->s_active.p, p.reso != 0,
-                 c->fuse_done, defer ? &din : nullptr))
+                 out->det.pairs_done, out->det.rows_folded, out->mvp_deferred ? &out->mv : nullptr))
     return -1;
-  if (defer) {
-    c->mvp_defer.resize(sizeof(MvpIn));
-    memcpy(c->mvp_defer.data(), &din, sizeof(MvpIn));
-    c->mvp_deferred = true;
-  }
   // second half: resopairs rewrite, ResumeNav's asas.active, unique / cumulative counts
   return p.resume_nav ? bk_apply(c, bk) : 0;
 }
 
-// An aborted CD call (ctl = sim_ctl words [16, 48): sticky, steps done,
-// resopairs demand, key-block demand): grow what overflowed on THIS rank (the
-// gate is all-reduced, so every rank aborted at the same step; another rank's
-// overflow re-runs the step here with unchanged buffers)
-static int grow_after_abort(Ctx *c, const unsigned long long *ctl) {
+// the FMS clock over one step: Autopilot.update's tick rule on
+// the host's copy of simt (autopilot.py:61-62, simulation.py:119); returns
+// whether the step ticks.  The enqueue loop and the replay after an abort
+// advance the clock with it.
+static bool fms_clock_step(Ctx *c) {
+  const bool tick = fms_ticks_at(c->fms_simt, c->fms_t0);
+  if (tick) {
+    c->fms_t0 = c->fms_simt;
+    c->fms_ticks++;
+  }
+  c->fms_simt += c->simp.simdt;
+  return tick;
+}
+
+// ---- a batch (the steps of one bsa_sim_step attempt, or one bsa_sim_cd
+// call): enqueued without host synchronisation from the host state kept here,
+// read back once (batch_end), rolled back to the aborted step if it aborted
+struct BatchBase {
+  bool kin;  // the batch runs K4' (bsa_sim_step; a CD call alone moves no state)
+  int64_t steps, cd_calls;
+  bool gs_derivable;
+  double fms_simt, fms_t0;  // the FMS clock
+  int64_t fms_ticks;
+};
+static int batch_begin(Ctx *c, bool kin, BatchBase *b) {
+  *b = BatchBase{kin, c->sim_steps, c->sim_cd_calls, c->sim_gs_derivable, c->fms_simt, c->fms_t0, c->fms_ticks};
+  BSA_HIP(c, hipMemsetAsync((char *)c->sim_ctl.p + kSimCtlSticky, 0, 40, c->stream));  // sticky, steps_done, demands, stale
+  return 0;
+}
+// the batch's only host synchronisation: ctl = sim_ctl words {sticky, steps
+// done, resopairs demand, key-block demand, stale}
+static int batch_end(Ctx *c, unsigned long long ctl[5]) {
+  BSA_HIP(c, hipMemcpyAsync(ctl, (char *)c->sim_ctl.p + kSimCtlSticky, 40, hipMemcpyDeviceToHost, c->stream));
+  BSA_HIP(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// An aborted batch: the state is that of the aborted step's start (step
+// base.steps + ctl[1]).  The gate is all-reduced, so every rank aborted at the
+// same step; each rank grows only what overflowed on IT (another rank's
+// overflow re-runs the step here with unchanged buffers) and all ranks re-run it
+static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long long *ctl) {
   c->reuse_valid = false;  // the re-run rebuilds any reused candidate list
   c->tpr_valid = false;    // ... and any kept tile-pair list / halo plan (every rank aborted alike)
   c->zeroed_rows = -1;     // ... and zeroes every per-detect buffer (an aborted K2 wrote no inconf / tcpamax)
-  {
-    Counters h;
-    BSA_HIP(c, hipMemcpy(&h, c->counters.p, sizeof(h), hipMemcpyDeviceToHost));
-    if (h.halo_miss)
-      return fail(c, "internal error: the halo exchange and the tile-pair cull disagree (rank %d)", c->rank);
+  c->sim_prepped = false;  // (an aborted K4' prepared nothing)
+  c->hk_ok = false;        // (HK: the decisions of the aborted steps never took effect)
+  const int64_t done = (int64_t)ctl[1];
+  c->sim_steps = base.steps + done;
+  c->sim_gs_derivable = done > 0 ? c->simp.winddim == 0 : base.gs_derivable;  // K4' ran for the completed steps only
+  int64_t cds = 0;
+  for (int64_t k = base.steps; k < base.steps + done; ++k) cds += (k % c->simp.cd_every == 0) ? 1 : 0;
+  c->sim_cd_calls = base.cd_calls + cds;
+  if (base.kin) c->sim_gathered = c->nranks == 1;
+  if (base.kin && c->sim_fms) {
+    // the FMS clock of the completed steps, replayed from the batch base; the
+    // aborted step's launch ran (later ones were no-ops): if it ticked, the
+    // undo set it filled holds the step's start -- put it back
+    c->fms_simt = base.fms_simt;
+    c->fms_t0 = base.fms_t0;
+    c->fms_ticks = base.fms_ticks;
+    for (int64_t k = 0; k < done; ++k) fms_clock_step(c);
+    if (fms_ticks_at(c->fms_simt, c->fms_t0) && fms_sim_restore(c)) return -1;
   }
+  // the last detect's counters: every detect after the abort ran on the same, unchanged state
+  Counters h;
+  BSA_HIP(c, hipMemcpy(&h, c->counters.p, sizeof(h), hipMemcpyDeviceToHost));
+  if (h.halo_miss)
+    return fail(c, "internal error: the halo exchange and the tile-pair cull disagree (rank %d)", c->rank);
   // several ranks: every rank takes part in the capacity agreement (collective)
   if (c->halo_mode == 1 && halo_grow(c)) return -1;
   if (ctl[2] > 0)  // this rank's resopairs outgrew their buffer
@@ -518,13 +575,7 @@ static int grow_after_abort(Ctx *c, const unsigned long long *ctl) {
   }
   if (kdem > 0)
     c->bk_kw = std::max<unsigned long long>(2 * c->bk_kw, (unsigned long long)kdem + (unsigned long long)kdem / 4 + 1024);
-  // candidate overflow on this rank: enough for the last detect's demand (its
-  // shard counters keep counting past the capacity; every detect after the
-  // abort ran on the same, unchanged state)
-  Counters h;
-  BSA_HIP(c, hipMemcpy(&h, c->counters.p, sizeof(h), hipMemcpyDeviceToHost));
-  static const bool trace = getenv("BSA_HK_TRACE") && atoi(getenv("BSA_HK_TRACE")) == 1;  // (diagnostics)
-  if (trace)
+  if (detect_env().hk_trace)  // (diagnostics)
     fprintf(stderr, "[bsa hk] rank %d abort at step %lld: stale %d k2 %llu fuse %llu halo %llu/%llu\n", c->rank,
             (long long)c->sim_steps, ctl[4] ? 1 : 0, h.k2_demand, h.fuse_ovf, h.halo_ovf, h.halo_miss);
   if (h.k2_demand) grow_k2_bucket(c, h.k2_demand);  // a K2 row bucket was full on this rank
@@ -532,6 +583,8 @@ static int grow_after_abort(Ctx *c, const unsigned long long *ctl) {
     c->fuse_skip = true;
     c->fuse_retries++;
   }
+  // candidate overflow on this rank: enough for the last detect's demand (its
+  // shard counters keep counting past the capacity)
   unsigned long long worst = 0;
   for (int q = 0; q < kCandShards; ++q) worst = std::max(worst, h.cshard[q][0]);
   if (worst > c->cand_cap / kCandShards)
@@ -544,6 +597,166 @@ static int check_params(Ctx *c, const bsa_sim_params *p) {
   if (p->resume_nav != 0 && p->resume_nav != 1) return fail(c, "resume_nav must be 0 or 1");
   if (p->winddim < 0 || p->winddim > 2) return fail(c, "winddim must be 0, 1 or 2");
   if (p->reso != 0 && p->reso != 1) return fail(c, "reso must be 0 or 1");
+  return 0;
+}
+
+// ---- one step of a batch: StepPlan (every decision, taken by step_decide
+// before anything of the step is enqueued), one function per stage,
+// step_enqueue runs them in order (the detect side: DetectPlan, bsa_cd.hip)
+struct StepPlan {
+  // OpenAP forces: the pending fuel of the step before is committed first --
+  // not by the first step of a re-run attempt: it is the aborted step's own
+  // 
+  bool commit_fuel;
+  // Autopilot.update ticks in this step: decided here, by the reference's rule
+  // on the host's copy of simt (fms_clock_step); nothing is read back
+  bool fms_tick;
+  bool cd;  // a CD step (every cd_every steps)
+  // one rank: K2 and this step's K4' as one launch (k24_launch; BSA_K24=0
+  // off) -- K4' then starts on each workgroup's rows as soon as their fold is
+  // done, instead of behind the whole of K2
+  bool k24;
+  // one rank, the next step a CD step: K4' also prepares that detect's
+  // column records and boxes (its K0b launch is skipped; BSA_SIM_PREP=0 off)
+  bool prep;
+  // K4' workgroup size: one wave (at 100k rows 256-lane groups left half the
+  // CUs one group short, 391 groups on 256 CUs: 0.1753 -> 0.1718 ms per
+  // step with 64; BSA_K4_BLOCK=128/256 for A/B)
+  int k4_block;
+};
+static StepPlan step_decide(const Ctx *c, bool rerun_first) {
+  const DetectEnv &env = detect_env();
+  const int64_t rb = c->sim_rb, re = c->sim_re;
+  StepPlan sp{};
+  sp.commit_fuel = !rerun_first;
+  sp.fms_tick = c->sim_fms && fms_ticks_at(c->fms_simt, c->fms_t0);
+  sp.cd = c->sim_steps % c->simp.cd_every == 0;
+  sp.k24 = sp.cd && env.k24 && c->nranks == 1 && c->halo_mode == 0 && !c->simp.resume_nav && re > rb &&
+           c->k2_bucket > 0;
+  sp.prep = env.sim_prep && c->nranks == 1 && c->home && !c->reuse_on && c->halo_mode == 0 && rb == 0 &&
+            re == c->n && (c->sim_steps + 1) % c->simp.cd_every == 0;
+  sp.k4_block = env.k4_block;  // (PREP: whole waves = whole groups, rb = 0)
+  return sp;
+}
+
+// Autopilot.update on the pre-step state (bsa_fms.hip), and the clock over the step
+static int step_fms(Ctx *c, const StepPlan &sp) {
+  if (fms_sim_launch(c, sp.fms_tick)) return -1;
+  fms_clock_step(c);
+  return 0;
+}
+
+// K4' as the preparer of the next detect's column records and boxes
+// (StepPlan::prep): their buffers, a fresh non-finite epoch and, with a kept
+// tile-pair list, its budgets.  After the step's CD call: Ctx::tpr_valid and
+// Ctx::hk_m are that detect's
+static int step_prep_args(Ctx *c, PrepArgs *out) {
+  PrepArgs &pa = *out;
+  const int64_t n = c->n;
+  pa.rec = home_records(c, n) ? 1 : 0;
+  if (!ensure_col_prep(c, n, pa.rec != 0)) return -1;
+  pa.out = PrepOut{(ColRec *)c->colrec.p, (PFRec *)c->pfcol.p, (PFVel *)c->pfvcol.p, (float4 *)c->pfpcol.p};
+  pa.sbox = (TileBox *)c->sbox_c.p;
+  pa.gbox = (TileBox *)c->gbox_c.p;
+  pa.rpz = c->simp.rpz;
+  pa.hpz = c->simp.hpz;
+  pa.tla = c->simp.tla;
+  pa.mid = stage1_mid(0, false, 0);
+  pa.n = (int)n;
+  if (!nonfin_word(c)) return -1;
+  pa.nf = (unsigned long long *)c->nonfin.p;  // the next detect's records: a fresh epoch
+  pa.nfe = c->nf_prep_epoch = ++c->nf_counter;
+  if (c->tpr_valid && c->tpr_snap.p && c->tpr_ctl.p && c->tpr_n == n) {  // the kept list's budgets
+    pa.snap = (const PFRec *)c->tpr_snap.p;
+    pa.tpr_ctl = (unsigned long long *)c->tpr_ctl.p;
+    pa.dx = c->tpr_dx;
+    pa.ds = c->tpr_ds;
+    pa.dv = c->tpr_dv;
+    // HK: the prediction word of the next detect (index hk_m, if it is host-decided)
+    pa.pred = (unsigned long long *)c->tpr_ctl.p + 6 + (c->hk_m & 1);
+    pa.pf = c->hk_f;
+  }
+  return 0;
+}
+
+// HK: the CD step's K4' (or K2 + K4') publishes a host-decided detect's
+// prediction -- the rank's own word with K2 fused, else gate[2] after K2 and
+// the all-reduce
+static HkPub step_hk_pub(const Ctx *c, const DetectResult &det) {
+  HkPub pub{};
+  if (!det.hk) return pub;
+  pub.slot = c->hk_hdev + (det.hk_m % kHkRing);
+  pub.base = (unsigned long long)(det.hk_m + 1) << 2;
+  if (det.k2_kept) {
+    pub.src = (unsigned long long *)c->tpr_ctl.p + 6 + (det.hk_m & 1);
+    pub.zero = 1;
+  } else {
+    pub.src = (unsigned long long *)c->sim_ctl.p + 2;
+  }
+  return pub;
+}
+
+// K4' of the step, or (the detect kept its K2) K2 + K4' as one launch on
+// double-buffered alt / vs / gse / gsn
+static int step_launch(Ctx *c, const StepPlan &sp, const CdOut &cd, const PrepArgs &pa, const HkPub &pub) {
+  const bsa_sim_params &p = c->simp;
+  const int64_t rb = c->sim_rb, re = c->sim_re, n = c->n;
+  if (cd.det.k2_kept) {
+    if (!cd.mvp_deferred) return fail(c, "internal: fused K2 + K4' without the deferred MVP rows");
+    if (!ensure(c, c->nx_alt, n * 8, "next altitudes") || !ensure(c, c->nx_vs, n * 8, "next vs") ||
+        !ensure(c, c->nx_gse, n * 8, "next gseast") || !ensure(c, c->nx_gsn, n * 8, "next gsnorth"))
+      return -1;
+    SimDev d = sim_dev(c);
+    d.alt_w = (double *)c->nx_alt.p;
+    d.vs_w = (double *)c->nx_vs.p;
+    d.gse_w = (double *)c->nx_gse.p;
+    d.gsn_w = (double *)c->nx_gsn.p;
+    const K24Args ka{d, cd.mv, p.mvp, pa, wind_field(c), p.simdt, p.windnorth, p.windeast, p.winddim,
+                     sp.prep ? 1 : 0, pub};
+    if (k24_launch(c, cd.det.k2, cd.det.k2_ev, ka)) return -1;
+    std::swap(c->own[4], c->nx_alt);
+    std::swap(c->own[5], c->nx_vs);
+    std::swap(c->s_gse, c->nx_gse);
+    std::swap(c->s_gsn, c->nx_gsn);
+  } else {
+    const int blk = sp.k4_block;
+    const int64_t nb = std::max<int64_t>(1, (re - rb + blk - 1) / blk);
+    const auto K4 = cd.mvp_deferred ? (sp.prep ? k_sim_pilot_kin<true, true> : k_sim_pilot_kin<true, false>)
+                                    : (sp.prep ? k_sim_pilot_kin<false, true> : k_sim_pilot_kin<false, false>);
+    hipLaunchKernelGGL(K4, dim3((unsigned)nb), dim3(blk), 0, c->stream, (int)rb, (int)re, p.simdt, p.winddim,
+                       p.windnorth, p.windeast, wind_field(c), sim_dev(c), cd.mv, p.mvp, pa, pub);
+  }
+  BSA_HIP(c, hipGetLastError());
+  return 0;
+}
+
+// one step of the batch (enqueue only), and the host state that follows it
+static int step_enqueue(Ctx *c, const StepPlan &sp) {
+  // (forces and FMS read the pre-step state: first on the step's stream)
+  if (c->sim_forces && forces_sim_launch(c, sp.commit_fuel)) return -1;
+  if (c->sim_fms && step_fms(c, sp)) return -1;
+  CdOut cd;
+  if (sp.cd && sim_cd(c, true, sp.k24, &cd)) {
+    c->hk_ok = false;  // (a detect may have been enqueued without its step's publication)
+    return -1;
+  }
+  PrepArgs pa{};
+  if (sp.prep && step_prep_args(c, &pa)) return -1;
+  if (step_launch(c, sp, cd, pa, step_hk_pub(c, cd.det))) return -1;
+  c->sim_prepped = sp.prep;
+  if (sp.prep) {
+    c->sim_prep_key[0] = pa.rpz;
+    c->sim_prep_key[1] = pa.hpz;
+    c->sim_prep_key[2] = pa.tla;
+    c->sim_prep_key[3] = (double)pa.mid;
+    c->sim_prep_n = c->n;
+  }
+  // every rank's rows now hold K4's gs / trk / gse / gsn: gse / gsn follow
+  // from gs / trk bitwise only without wind (with wind gs / trk derive from
+  // them, traffic.py:463-466, not the other way round)
+  c->sim_gs_derivable = c->simp.winddim == 0;
+  c->sim_gathered = c->nranks == 1;
+  c->sim_steps++;
   return 0;
 }
 
@@ -655,197 +868,20 @@ int bsa_sim_step(bsa_ctx *cc, int nsteps) {
     return bsa::fail(c, "winddim 2 needs a wind field (bsa_set_windfield)");
   if (nsteps < 0) return bsa::fail(c, "negative step count");
   BSA_HIP(c, hipSetDevice(c->device));
-  const int64_t rb = c->sim_rb, re = c->sim_re;
   const int64_t target = c->sim_steps + nsteps;
   for (int attempt = 0; c->sim_steps < target; ++attempt) {
     if (attempt > 6) return bsa::fail(c, "candidate buffer overflow in the resident step (retries exhausted)");
-    const int64_t base = c->sim_steps, base_cd = c->sim_cd_calls;
-    const bool derivable0 = c->sim_gs_derivable;
-    const double fms_simt0 = c->fms_simt, fms_t00 = c->fms_t0;  // the FMS clock at the batch base
-    const int64_t fms_ticks0 = c->fms_ticks;
-    BSA_HIP(c, hipMemsetAsync((char *)c->sim_ctl.p + bsa::kSimCtlSticky, 0, 40, c->stream));  // sticky, steps_done, demands, stale
-    while (c->sim_steps < target) {
-      bool cd_step = false;
-      // OpenAP drag / thrust / fuel flow of the pre-step state, first on the step's
-      // stream (bsa_perf.hip).  The first step of a re-run attempt does not commit
-      // the pending fuel: it is the aborted step's own
-      if (c->sim_forces && bsa::forces_sim_launch(c, !(attempt > 0 && c->sim_steps == base))) return -1;
-      // Autopilot.update on the pre-step state (bsa_fms.hip): the tick is decided
-      // here, by the reference's rule on the host's copy of simt (autopilot.py:61-62,
-      // simulation.py:119); nothing is read back
-      if (c->sim_fms) {
-        const bool tick = bsa::fms_ticks_at(c->fms_simt, c->fms_t0);
-        if (bsa::fms_sim_launch(c, tick)) return -1;
-        if (tick) {
-          c->fms_t0 = c->fms_simt;
-          c->fms_ticks++;
-        }
-        c->fms_simt += c->simp.simdt;
-      }
-      if (c->sim_steps % c->simp.cd_every == 0) {
-        // one rank: K2 and this step's K4' as one launch (k24_launch below;
-        // BSA_K24=0 off) -- K4' then starts on each workgroup's rows as soon as
-        // their fold is done, instead of behind the whole of K2
-        static const bool k24_env = !(getenv("BSA_K24") && atoi(getenv("BSA_K24")) == 0);
-        c->k24_want = k24_env && c->nranks == 1 && c->halo_mode == 0 && !c->simp.resume_nav && re > rb &&
-                      c->k2_bucket > 0;
-        c->hk_req = true;  // (HK: this detect's list decision may be the host's)
-        const int r = bsa::sim_cd(c, true);
-        c->hk_req = false;
-        c->k24_want = false;
-        if (r) {
-          c->k24_pending = false;
-          c->hk_ok = false;  // (a detect may have been enqueued without its step's publication)
-          return -1;
-        }
-        cd_step = true;
-      }
-      // K4' workgroup size: one wave (at 100k rows 256-lane groups left half the
-      // CUs one group short, 391 groups on 256 CUs: 0.1753 -> 0.1718 ms per
-      // step with 64; BSA_K4_BLOCK=128/256 for A/B)
-      static const int k4b = [] {
-        const int v = getenv("BSA_K4_BLOCK") ? atoi(getenv("BSA_K4_BLOCK")) : 64;
-        return (v == 64 || v == 128 || v == 256) ? v : 64;
-      }();
-      // one rank, the next step a CD step: K4' also prepares that detect's
-      // column records and boxes (its K0b launch is skipped; BSA_SIM_PREP=0 off)
-      static const bool prep_env = !(getenv("BSA_SIM_PREP") && atoi(getenv("BSA_SIM_PREP")) == 0);
-      const bool prep = prep_env && c->nranks == 1 && c->home && !c->reuse_on && c->halo_mode == 0 && rb == 0 &&
-                        re == c->n && (c->sim_steps + 1) % c->simp.cd_every == 0;
-      bsa::PrepArgs pa{};
-      if (prep) {
-        const int64_t n = c->n;
-        pa.rec = bsa::home_records(c, n) ? 1 : 0;
-        if ((pa.rec && !bsa::ensure(c, c->colrec, n * sizeof(bsa::ColRec), "column records")) ||
-            !bsa::ensure(c, c->pfcol, n * sizeof(bsa::PFRec), "prefilter columns") ||
-            !bsa::ensure(c, c->pfvcol, n * sizeof(bsa::PFVel), "prefilter column velocities") ||
-            !bsa::ensure(c, c->pfpcol, n * sizeof(float4), "prefilter column positions") ||
-            !bsa::ensure(c, c->tbox_c, ((n + bsa::kTile - 1) / bsa::kTile) * sizeof(bsa::TileBox), "column tile boxes") ||
-            !bsa::ensure(c, c->gbox_c, ((n + bsa::kGroup - 1) / bsa::kGroup) * sizeof(bsa::TileBox), "column group boxes") ||
-            !bsa::ensure(c, c->sbox_c, ((n + bsa::kSub - 1) / bsa::kSub) * sizeof(bsa::TileBox), "column sub-group boxes"))
-          return -1;
-        pa.out = bsa::PrepOut{(bsa::ColRec *)c->colrec.p, (bsa::PFRec *)c->pfcol.p, (bsa::PFVel *)c->pfvcol.p,
-                              (float4 *)c->pfpcol.p};
-        pa.sbox = (bsa::TileBox *)c->sbox_c.p;
-        pa.gbox = (bsa::TileBox *)c->gbox_c.p;
-        pa.rpz = c->simp.rpz;
-        pa.hpz = c->simp.hpz;
-        pa.tla = c->simp.tla;
-        pa.mid = bsa::stage1_mid(0, false, 0);
-        pa.n = (int)n;
-        if (!bsa::nonfin_word(c)) return -1;
-        pa.nf = (unsigned long long *)c->nonfin.p;  // the next detect's records: a fresh epoch
-        pa.nfe = c->nf_prep_epoch = ++c->nf_counter;
-        if (c->tpr_valid && c->tpr_snap.p && c->tpr_ctl.p && c->tpr_n == n) {  // the kept list's budgets
-          pa.snap = (const bsa::PFRec *)c->tpr_snap.p;
-          pa.tpr_ctl = (unsigned long long *)c->tpr_ctl.p;
-          pa.dx = c->tpr_dx;
-          pa.ds = c->tpr_ds;
-          pa.dv = c->tpr_dv;
-          // HK: the prediction word of the next detect (index hk_m, if it is host-decided)
-          pa.pred = (unsigned long long *)c->tpr_ctl.p + 6 + (c->hk_m & 1);
-          pa.pf = c->hk_f;
-        }
-      }
-      const int blk = k4b;  // (PREP: whole waves = whole groups, rb = 0)
-      const int64_t nb = std::max<int64_t>(1, (re - rb + blk - 1) / blk);
-      bsa::MvpIn mv{};
-      if (c->mvp_deferred) memcpy(&mv, c->mvp_defer.data(), sizeof(mv));
-      // HK: the CD step's K4' (or K2 + K4') publishes the detect's prediction --
-      // the rank's own word with K2 fused, else gate[2] after K2 and the all-reduce
-      bsa::HkPub pub{};
-      if (cd_step && c->hk_cur) {
-        pub.slot = c->hk_hdev + (c->hk_last % bsa::kHkRing);
-        pub.base = (unsigned long long)(c->hk_last + 1) << 2;
-        if (c->k24_pending) {
-          pub.src = (unsigned long long *)c->tpr_ctl.p + 6 + (c->hk_last & 1);
-          pub.zero = 1;
-        } else {
-          pub.src = (unsigned long long *)c->sim_ctl.p + 2;
-        }
-      }
-      if (c->k24_pending) {  // K2 of this step's detect, fused with K4' (double-buffered alt / vs / gse / gsn)
-        const int64_t n = c->n;
-        if (!c->mvp_deferred) return bsa::fail(c, "internal: fused K2 + K4' without the deferred MVP rows");
-        if (!bsa::ensure(c, c->nx_alt, n * 8, "next altitudes") || !bsa::ensure(c, c->nx_vs, n * 8, "next vs") ||
-            !bsa::ensure(c, c->nx_gse, n * 8, "next gseast") || !bsa::ensure(c, c->nx_gsn, n * 8, "next gsnorth"))
-          return -1;
-        bsa::SimDev d = bsa::sim_dev(c);
-        d.alt_w = (double *)c->nx_alt.p;
-        d.vs_w = (double *)c->nx_vs.p;
-        d.gse_w = (double *)c->nx_gse.p;
-        d.gsn_w = (double *)c->nx_gsn.p;
-        const bsa::K24Args ka{d, mv, c->simp.mvp, pa, bsa::wind_field(c), c->simp.simdt, c->simp.windnorth,
-                              c->simp.windeast, c->simp.winddim, prep ? 1 : 0, pub};
-        if (bsa::k24_launch(c, ka)) return -1;
-        std::swap(c->own[4], c->nx_alt);
-        std::swap(c->own[5], c->nx_vs);
-        std::swap(c->s_gse, c->nx_gse);
-        std::swap(c->s_gsn, c->nx_gsn);
-      } else {
-        const auto K4 = c->mvp_deferred ? (prep ? bsa::k_sim_pilot_kin<true, true> : bsa::k_sim_pilot_kin<true, false>)
-                                        : (prep ? bsa::k_sim_pilot_kin<false, true> : bsa::k_sim_pilot_kin<false, false>);
-        hipLaunchKernelGGL(K4, dim3((unsigned)nb), dim3(blk), 0, c->stream, (int)rb, (int)re, c->simp.simdt,
-                           c->simp.winddim, c->simp.windnorth, c->simp.windeast, bsa::wind_field(c), bsa::sim_dev(c),
-                           mv, c->simp.mvp, pa, pub);
-      }
-      c->mvp_deferred = false;
-      c->sim_prepped = prep;
-      if (prep) {
-        c->sim_prep_key[0] = pa.rpz;
-        c->sim_prep_key[1] = pa.hpz;
-        c->sim_prep_key[2] = pa.tla;
-        c->sim_prep_key[3] = (double)pa.mid;
-        c->sim_prep_n = c->n;
-      }
-      BSA_HIP(c, hipGetLastError());
-      // every rank's rows now hold K4's gs / trk / gse / gsn: gse / gsn follow
-      // from gs / trk bitwise only without wind (with wind gs / trk derive from
-      // them, traffic.py:463-466, not the other way round)
-      c->sim_gs_derivable = c->simp.winddim == 0;
-      c->sim_gathered = c->nranks == 1;
-      c->sim_steps++;
-    }
-    // the batch's only host synchronisation: did every step complete?
+    bsa::BatchBase base;
+    if (bsa::batch_begin(c, true, &base)) return -1;
+    while (c->sim_steps < target)
+      if (bsa::step_enqueue(c, bsa::step_decide(c, attempt > 0 && c->sim_steps == base.steps))) return -1;
     unsigned long long ctl[5] = {0, 0, 0, 0, 0};
-    BSA_HIP(c, hipMemcpyAsync(ctl, (char *)c->sim_ctl.p + bsa::kSimCtlSticky, 40, hipMemcpyDeviceToHost, c->stream));
-    BSA_HIP(c, hipStreamSynchronize(c->stream));
+    if (bsa::batch_end(c, ctl)) return -1;  // did every step complete?
 #ifdef BSA_PF_TRACE
     if (bsa::pf_trace_dump(c, 0, 0)) return -1;  // (diagnostic builds: the batch's last prefilter)
 #endif
     if ((unsigned)ctl[0] == 0) break;
-    // aborted at step base + done: the state is that of the step's start.  The
-    // gate is all-reduced, so every rank aborted at the same step; each rank
-    // grows only the buffers that overflowed on IT (another rank's overflow
-    // re-runs the step with unchanged buffers here) and all ranks re-run it
-    c->reuse_valid = false;  // the re-run rebuilds any reused candidate list
-    c->sim_prepped = false;  // (an aborted K4' prepared nothing)
-    c->tpr_valid = false;  // (tile-pair list / halo plan reuse: rebuilt at the next detect)
-    c->hk_ok = false;      // (HK: the decisions of the aborted steps never took effect)
-    const int64_t done = (int64_t)ctl[1];
-    c->sim_steps = base + done;
-    c->sim_gs_derivable = done > 0 ? c->simp.winddim == 0 : derivable0;  // K4' ran for the completed steps only
-    int64_t cds = 0;
-    for (int64_t k = base; k < base + done; ++k) cds += (k % c->simp.cd_every == 0) ? 1 : 0;
-    c->sim_cd_calls = base_cd + cds;
-    c->sim_gathered = c->nranks == 1;
-    if (c->sim_fms) {
-      // the FMS clock of the completed steps, replayed from the batch base; the
-      // aborted step's launch ran (later ones were no-ops): if it ticked, the
-      // undo set it filled holds the step's start -- put it back
-      c->fms_simt = fms_simt0;
-      c->fms_t0 = fms_t00;
-      c->fms_ticks = fms_ticks0;
-      for (int64_t k = 0; k < done; ++k) {
-        if (bsa::fms_ticks_at(c->fms_simt, c->fms_t0)) {
-          c->fms_t0 = c->fms_simt;
-          c->fms_ticks++;
-        }
-        c->fms_simt += c->simp.simdt;
-      }
-      if (bsa::fms_ticks_at(c->fms_simt, c->fms_t0) && bsa::fms_sim_restore(c)) return -1;
-    }
-    if (bsa::grow_after_abort(c, ctl)) return -1;
+    if (bsa::batch_rollback(c, base, ctl)) return -1;
   }
   return 0;
 }
@@ -1174,11 +1210,10 @@ int bsa_sim_detect_rows(bsa_ctx *cc, int64_t row_begin, int64_t row_end, int64_t
   if (bsa::prep_all_tiles(c, c->simp.rpz, c->simp.hpz, c->simp.tla, e)) return -1;
   const int hm = c->halo_mode;
   c->halo_mode = 2;
-  c->det_home = true;
-  c->nf_force_epoch = e;  // (retries of the detect too)
-  const int r = bsa::detect(c, c->simp.rpz, c->simp.hpz, c->simp.tla, 0, row_begin, row_end, n_conf, n_los);
-  c->nf_force_epoch = 0;
-  c->det_home = false;
+  bsa::DetectRequest q{c->simp.rpz, c->simp.hpz, c->simp.tla, 0, row_begin, row_end};
+  q.home = true;
+  q.nf_epoch = e;  // (retries of the detect too)
+  const int r = bsa::detect(c, q, n_conf, n_los);
   c->halo_mode = hm;
   return r;
 }
@@ -1318,17 +1353,15 @@ int bsa_sim_cd(bsa_ctx *cc) {
   BSA_HIP(c, hipSetDevice(c->device));
   for (int attempt = 0;; ++attempt) {
     if (attempt > 6) return bsa::fail(c, "candidate buffer overflow in the CD call (retries exhausted)");
-    const int64_t base_cd = c->sim_cd_calls;
-    BSA_HIP(c, hipMemsetAsync((char *)c->sim_ctl.p + bsa::kSimCtlSticky, 0, 40, c->stream));  // sticky, steps_done, demands, stale
-    if (bsa::sim_cd(c, false)) return -1;
+    bsa::BatchBase base;
+    bsa::CdOut cd;
+    if (bsa::batch_begin(c, false, &base) || bsa::sim_cd(c, false, false, &cd)) return -1;
     unsigned long long ctl[5] = {0, 0, 0, 0, 0};
-    BSA_HIP(c, hipMemcpyAsync(ctl, (char *)c->sim_ctl.p + bsa::kSimCtlSticky, 40, hipMemcpyDeviceToHost, c->stream));
-    BSA_HIP(c, hipStreamSynchronize(c->stream));
+    if (bsa::batch_end(c, ctl)) return -1;
     if ((unsigned)ctl[0] == 0) break;
     // aborted: nothing persistent was written (the state did not move, so
     // the replicas stay consistent); grow and re-run
-    c->sim_cd_calls = base_cd;
-    if (bsa::grow_after_abort(c, ctl)) return -1;
+    if (bsa::batch_rollback(c, base, ctl)) return -1;
   }
   return 0;
 }

@@ -167,6 +167,7 @@ struct K24Args {
   int winddim, prep;
   HkPub pub;          // HK: this detect's prediction to the host (slot NULL: none)
 };
-int k24_launch(Ctx *c, const K24Args &ka);  // the deferred K2 launch of the last detect, fused (bsa_cd.hip)
+// the K2 launch a detect kept (DetectResult::k2, k2_ev), fused (bsa_cd.hip)
+int k24_launch(Ctx *c, const RankLaunch &k2, hipEvent_t k2_ev, const K24Args &ka);
 
 }  // namespace bsa

@@ -502,3 +502,63 @@ def test_resident_nonfinite_aircraft(ctx, field):
         got = full_state(init, sim.read())
         compare(got, exp, k)
         prev = got
+
+
+def test_nothing_of_one_call_leaks_into_the_next():
+    """Standalone detects, resident steps, a rank's share (sim_detect_rows), a
+    CD call alone and more steps on ONE context: each call takes its options
+    from its own request (home order, forced non-finite epoch, host-decided
+    list, K2's MVP vectors, the kept K2 launch), so every standalone detect's
+    pairs equal those of the same call on a fresh context and the sim ends in
+    the state and with the stats of a fresh context that ran only the sim
+    calls -- bitwise.  1536 aircraft: three 512-row tiles, so a home-order
+    slice, a middle tile and row offsets all exist.  (bsa_set_state replaces a
+    resident sim, so after the second standalone detect the sim continues from
+    the state read before it, on both contexts alike.)"""
+    t = synth.box(1536, 60.0, seed=61)
+    u = synth.box(1536, 60.0, seed=62)
+    init = resident.initial_state(t)
+    p = resident.params(cd_every=1)
+    cd = (synth.RPZ, synth.HPZ, synth.TLOOKAHEAD)
+
+    def standalone(c, tr):
+        c.set_state(tr.lat, tr.lon, tr.trk, tr.gs, tr.alt, tr.vs)
+        nc, nl = c.detect(*cd)
+        return c.fetch_pairs(nc, nl)
+
+    def same(a, b, what):
+        assert a.keys() == b.keys(), what
+        for k in a:
+            if a[k] is not None or b[k] is not None:
+                assert np.array_equal(a[k], b[k], equal_nan=True), '%s: %s' % (what, k)
+
+    def sim_calls(c, between=lambda: None):
+        sim = resident.ResidentSim(init, p, ctx=c)
+        sim.step(2)
+        share = c.sim_detect_rows(512, 1024)
+        share_pairs = c.fetch_pairs(*share)
+        carried = full_state(init, sim.read())
+        carried.pop('active')
+        between()
+        sim = resident.ResidentSim(carried, p, ctx=c)
+        c.sim_cd()
+        sim.step(1)
+        return share_pairs, sim.read(), sim.stats()
+
+    ctxs = [_lib.Context(0) for _ in range(4)]
+    mixed, fresh1, fresh2, simonly = ctxs
+    try:
+        got = {}
+        got['first'] = standalone(mixed, t)
+        share, state, stats = sim_calls(mixed, lambda: got.update(second=standalone(mixed, u)))
+        same(got['first'], standalone(fresh1, t), 'first standalone detect')
+        same(got['second'], standalone(fresh2, u), 'second standalone detect')
+        assert len(got['first']['ci']) > 0 and len(got['second']['ci']) > 0
+        exp_share, exp_state, exp_stats = sim_calls(simonly)
+        same(share, exp_share, 'sim_detect_rows(512, 1024)')
+        assert len(share['ci']) > 0
+        same(state, exp_state, 'final sim state')
+        assert stats == exp_stats and stats['steps'] == 1 and stats['n_conf'] > 0, (stats, exp_stats)
+    finally:
+        for c in ctxs:
+            c.close()
