@@ -176,17 +176,15 @@ extern "C" int bsa_fms_update(bsa_ctx *cc, int64_t n, int64_t nrows, const doubl
   if (nrows < 0 || nrows > 0x7fffffff / bsa::fms::kRouteCols) return bsa::fail(c, "bsa_fms_update: bad route row count");
   if (!st) return bsa::fail(c, "bsa_fms_update: NULL state");
   const double *tr[8] = {lat, lon, alt, tas, gs, trk, ax, bank};
-  double *reals[bsa::kFmsReals] = {st->actwp_lat, st->actwp_lon, st->actwp_nextaltco, st->actwp_xtoalt,
-                                   st->actwp_spd, st->actwp_vs, st->actwp_turndist, st->actwp_flyby,
-                                   st->actwp_next_qdr, st->dist2vs, st->vnavvs, st->swvnavvs,
-                                   st->selspd, st->selvs, st->apvsdef};
-  uint8_t *flags[4] = {st->swlnav, st->swvnav, st->abco, st->belco};
+  const bsa::FmsFields ff = bsa::fms_fields(*st);
+  double *const *reals = ff.reals;
+  uint8_t *const *flags = ff.flags;
   double *tg[5] = {ap_trk, ap_tas, ap_alt, ap_vs, selalt};
   for (auto q : tr)
     if (!q) return bsa::fail(c, "bsa_fms_update: NULL array");
-  for (auto q : reals)
+  for (auto q : ff.reals)
     if (!q) return bsa::fail(c, "bsa_fms_update: NULL array");
-  for (auto q : flags)
+  for (auto q : ff.flags)
     if (!q) return bsa::fail(c, "bsa_fms_update: NULL array");
   for (auto q : tg)
     if (!q) return bsa::fail(c, "bsa_fms_update: NULL array");

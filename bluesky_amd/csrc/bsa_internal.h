@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -470,6 +471,122 @@ struct Ctx {
   int64_t feed_steps = 0, feed_rb = 0, feed_re = 0;
 };
 
+// ---- the resident sim's per-aircraft arrays, described once
+struct BufRef {  // a DevBuf of the context: c->*m, or c->own[own] when m is NULL
+  DevBuf Ctx::*m;
+  int own;
+};
+inline DevBuf &buf_at(Ctx *c, BufRef r) { return r.m ? c->*r.m : c->own[r.own]; }
+// pointer k of an ABI struct that holds array pointers only
+inline void *ptr_at(const void *strct, int k) { return ((void *const *)strct)[k]; }
+
+// kSimArrays: every persistent per-aircraft array (home order).  sim_release,
+// bsa_sim_delete / bsa_sim_create and the re-partition on several ranks walk
+// it (bsa_traffic.hip: per_aircraft), bsa_sim_init allocates its kSimAlways rows
+// guard: kSimAlways allocated by bsa_sim_init; kSimDetect the last detect's per-row outputs (the detect's to
+// allocate); kSimOnUse once allocated (the reso lists); the others while Ctx::sim_<switch> is on
+enum SimGuard { kSimAlways, kSimDetect, kSimOnUse, kSimLimits, kSimPerf, kSimForces, kSimFms, kSimAtmos };
+struct SimArray {
+  BufRef buf;
+  int esz, count;  // element size; sub-arrays of length n in the buffer
+  bool gathered;   // bsa_sim_init allocates the all-gather length (nranks x rpr)
+  SimGuard guard;
+};
+// bsa_fms_state: its fp64 arrays (the first kFmsMutable are written by a tick;
+// selvs, apvsdef are read only), its flags, iactwp / rt_off / rt_n, and the
+// reals of the undo set (the mutable ones + ap_trk, ap_alt, ap_vs, selalt)
+constexpr int kFmsReals = 15, kFmsMutable = 13, kFmsFlags = 4, kFmsInts = 3, kFmsUndoReals = kFmsMutable + 4;
+inline const SimArray kSimArrays[] = {
+    {{nullptr, 0}, 8, 1, true, kSimAlways},         {{nullptr, 1}, 8, 1, true, kSimAlways},
+    {{nullptr, 2}, 8, 1, true, kSimAlways},         {{nullptr, 3}, 8, 1, true, kSimAlways},
+    {{nullptr, 4}, 8, 1, true, kSimAlways},         {{nullptr, 5}, 8, 1, true, kSimAlways},
+    {{&Ctx::s_tas}, 8, 1, true, kSimAlways},        {{&Ctx::s_hdg}, 8, 1, true, kSimAlways},
+    {{&Ctx::s_gse}, 8, 1, true, kSimAlways},        {{&Ctx::s_gsn}, 8, 1, true, kSimAlways},
+    {{&Ctx::s_aptrk}, 8, 1, false, kSimAlways},     {{&Ctx::s_aptas}, 8, 1, false, kSimAlways},
+    {{&Ctx::s_apalt}, 8, 1, false, kSimAlways},     {{&Ctx::s_apvs}, 8, 1, false, kSimAlways},
+    {{&Ctx::s_selalt}, 8, 1, false, kSimAlways},    {{&Ctx::s_bank}, 8, 1, false, kSimAlways},
+    {{&Ctx::s_eps}, 8, 1, false, kSimAlways},       {{&Ctx::s_accel}, 8, 1, false, kSimAlways},
+    {{&Ctx::s_atrk}, 8, 1, false, kSimAlways},      {{&Ctx::s_atas}, 8, 1, false, kSimAlways},
+    {{&Ctx::s_avs}, 8, 1, false, kSimAlways},       {{&Ctx::s_aalt}, 8, 1, false, kSimAlways},
+    {{&Ctx::s_altprev}, 8, 1, false, kSimAlways},   {{&Ctx::s_ax}, 8, 1, false, kSimAlways},
+    {{&Ctx::tcpamax}, 8, 1, false, kSimDetect},     {{&Ctx::s_ase}, 4, 1, false, kSimAlways},
+    {{&Ctx::s_asn}, 4, 1, false, kSimAlways},       {{&Ctx::s_active}, 1, 1, false, kSimAlways},
+    {{&Ctx::inconf}, 1, 1, false, kSimDetect},      {{&Ctx::s_noreso}, 1, 1, false, kSimOnUse},
+    {{&Ctx::s_resooff}, 1, 1, false, kSimOnUse},    {{&Ctx::s_dropped}, 1, 1, false, kSimAlways},
+    {{&Ctx::s_env}, 8, 6, false, kSimLimits},       {{&Ctx::s_atm}, 8, 3, false, kSimAtmos},
+    {{&Ctx::s_ptype}, 4, 1, false, kSimPerf},       {{&Ctx::s_phase}, 1, 1, false, kSimPerf},
+    {{&Ctx::s_fmass}, 8, 1, false, kSimForces},     {{&Ctx::s_fout}, 8, 6, false, kSimForces},
+    {{&Ctx::s_fused}, 8, 1, false, kSimForces},     {{&Ctx::s_fpend}, 8, 1, false, kSimForces},
+    {{&Ctx::s_fmsr}, 8, kFmsReals, false, kSimFms}, {{&Ctx::s_fmsf}, 1, kFmsFlags, false, kSimFms},
+    {{&Ctx::s_fmsi}, 4, kFmsInts, false, kSimFms},
+};
+// is the array part of the sim now (to be carried through a delete / create)?
+inline bool sim_array_on(Ctx *c, const SimArray &a) {
+  switch (a.guard) {
+    case kSimOnUse: return buf_at(c, a.buf).p != nullptr;
+    case kSimLimits: return c->sim_limits;
+    case kSimPerf: return c->sim_perf;
+    case kSimForces: return c->sim_forces;
+    case kSimFms: return c->sim_fms;
+    case kSimAtmos: return c->sim_atmos;
+    default: return true;
+  }
+}
+
+// kSimFields: the arrays of bsa_sim_state in its declaration order, row k for
+// the pointer at byte 8 k (bsa_sim_init, bsa_sim_create, bsa_sim_update; the
+// first kSimOutFields are bsa_sim_out's, at the same offsets).  An array of
+// kSimArrays that no row names, as `buf` or as `also`, starts at zero
+struct SimField {
+  BufRef buf;         // its array
+  bool replicated;    // the all-gather completes it on every rank
+  bool cd_input;      // CD reads it: an update invalidates what was derived from it
+  DevBuf Ctx::*also;  // a second array new aircraft start from this field (asas.py:402-407; the feed's
+};                    // pre-step altitude), or NULL
+inline const SimField kSimFields[] = {
+    {{nullptr, 0}, true, true, nullptr},           {{nullptr, 1}, true, true, nullptr},            // lat lon
+    {{nullptr, 4}, true, true, &Ctx::s_altprev},   {{&Ctx::s_tas}, false, true, &Ctx::s_atas},     // alt tas
+    {{&Ctx::s_hdg}, false, true, nullptr},         {{nullptr, 5}, true, true, nullptr},            // hdg vs
+    {{nullptr, 3}, true, true, nullptr},           {{nullptr, 2}, true, true, &Ctx::s_atrk},       // gs trk
+    {{&Ctx::s_gse}, true, true, nullptr},          {{&Ctx::s_gsn}, true, true, nullptr},           // gseast gsnorth
+    {{&Ctx::s_aptrk}, false, false, nullptr},      {{&Ctx::s_aptas}, false, false, nullptr},       // ap_trk ap_tas
+    {{&Ctx::s_apalt}, false, false, nullptr},      {{&Ctx::s_apvs}, false, false, nullptr},        // ap_alt ap_vs
+    {{&Ctx::s_selalt}, false, false, nullptr},     {{&Ctx::s_bank}, false, false, nullptr},        // selalt bank
+    {{&Ctx::s_eps}, false, false, nullptr},        {{&Ctx::s_accel}, false, false, nullptr},       // eps accel
+    {{&Ctx::s_aalt}, false, false, nullptr},                                                       // asas_alt
+};
+constexpr int kSimStateFields = sizeof(kSimFields) / sizeof(kSimFields[0]), kSimOutFields = 10;
+static_assert(kSimStateFields * sizeof(double *) == sizeof(bsa_sim_state) &&
+                  offsetof(bsa_sim_state, asas_alt) == (kSimStateFields - 1) * sizeof(double *),
+              "one kSimFields row per bsa_sim_state array");
+static_assert(offsetof(bsa_sim_out, gsnorth) == offsetof(bsa_sim_state, gsnorth), "bsa_sim_out starts as bsa_sim_state");
+inline bool sim_field_names(Ctx *c, const DevBuf *b) {
+  for (const SimField &f : kSimFields)
+    if (&buf_at(c, f.buf) == b || (f.also && &(c->*f.also) == b)) return true;
+  return false;
+}
+
+// the ASAS outputs in bsa_asas_out's field order (bsa_sim_read: the first four and active)
+struct AsasArray {
+  DevBuf Ctx::*buf;
+  int esz;
+};
+inline const AsasArray kAsasArrays[8] = {{&Ctx::s_atrk, 8}, {&Ctx::s_atas, 8}, {&Ctx::s_avs, 8},    {&Ctx::s_aalt, 8},
+                                         {&Ctx::s_ase, 4},  {&Ctx::s_asn, 4},  {&Ctx::s_active, 1}, {&Ctx::s_dropped, 1}};
+static_assert(8 * sizeof(void *) == sizeof(bsa_asas_out), "one kAsasArrays row per bsa_asas_out array");
+
+// bsa_fms_state's arrays in declaration order
+struct FmsFields {
+  double *reals[kFmsReals];
+  uint8_t *flags[kFmsFlags];
+};
+inline FmsFields fms_fields(const bsa_fms_state &st) {
+  return {{st.actwp_lat, st.actwp_lon, st.actwp_nextaltco, st.actwp_xtoalt, st.actwp_spd, st.actwp_vs,
+           st.actwp_turndist, st.actwp_flyby, st.actwp_next_qdr, st.dist2vs, st.vnavvs, st.swvnavvs, st.selspd,
+           st.selvs, st.apvsdef},
+          {st.swlnav, st.swvnav, st.abco, st.belco}};
+}
+
 // device pointers for the MVP kernel (full-N traffic arrays, per-row outputs)
 struct MvpDev {
   const double *gseast, *gsnorth, *vs, *alt, *trk, *gs, *selalt, *apvs;
@@ -515,10 +632,6 @@ int fms_check_routes(Ctx *c, const char *who, int64_t n, int64_t nrows, const in
                      const int32_t *iactwp, const uint8_t *swlnav);
 int fms_sim_launch(Ctx *c, bool tick);
 int fms_sim_restore(Ctx *c);
-// bsa_fms_state: its fp64 arrays (the first kFmsMutable are written by a tick;
-// selvs, apvsdef are read only), its flags, iactwp / rt_off / rt_n, and the
-// reals of the undo set (the mutable ones + ap_trk, ap_alt, ap_vs, selalt)
-constexpr int kFmsReals = 15, kFmsMutable = 13, kFmsFlags = 4, kFmsInts = 3, kFmsUndoReals = kFmsMutable + 4;
 inline bool fms_ticks_at(double simt, double t0) { return t0 + 1.01 < simt || simt < t0 || simt < 1.01; }
 
 // ASAS bookkeeping of one CD call (bsa_asas.hip): bk_count before the gate

@@ -75,7 +75,6 @@ __global__ __launch_bounds__(256) void k_sim_pilot_kin(int rb, int re, double si
   pilot_kin_row<FUSE, PREP>(rb, k, simdt, winddim, vwn, vwe, wf, d, mv, mp, pa);
 }
 
-
 // field list of one all-gather: fp64 arrays (full n) + optionally one uint8 array
 struct Fields {
   double *f[8];
@@ -226,147 +225,121 @@ int sim_adopt_pairs(Ctx *c) {
 }
 
 void sim_release(Ctx *c) {
-  DevBuf *all[] = {&c->red, &c->s_tas, &c->s_hdg, &c->s_gse, &c->s_gsn, &c->s_aptrk, &c->s_aptas,
-                   &c->s_apalt, &c->s_apvs, &c->s_selalt, &c->s_bank, &c->s_eps, &c->s_accel,
-                   &c->s_atrk, &c->s_atas, &c->s_avs, &c->s_aalt, &c->s_ase, &c->s_asn,
-                   &c->s_active, &c->g_send, &c->g_recv, &c->pg_send, &c->pg_recv, &c->sim_ctl, &c->s_altprev, &c->s_ax, &c->s_env,
-                   &c->s_ptab, &c->s_ptype, &c->s_phase, &c->s_ftab, &c->s_fmass, &c->s_fout, &c->s_fused, &c->s_fpend,
-                   &c->f_const, &c->s_fmsr, &c->s_fmsf, &c->s_fmsi, &c->s_fmsrows, &c->s_fmsur, &c->s_fmsuf, &c->s_fmsui,
-                   &c->s_noreso, &c->s_resooff, &c->s_dropped, &c->s_atm,
-                   &c->xfer_stage, &c->lbyidx, &c->fetch_stage, &c->tpr_snap, &c->tpr_ctl, &c->nx_alt, &c->nx_vs, &c->nx_gse, &c->nx_gsn};
-  for (auto *b : all) release(*b);
+  for (const SimArray &a : kSimArrays) release(buf_at(c, a.buf));
+  // not per aircraft: staging, control words, tables, the FMS undo set, K2 + K4' double buffers
+  DevBuf *rest[] = {&c->red, &c->g_send, &c->g_recv, &c->pg_send, &c->pg_recv, &c->sim_ctl, &c->s_ptab, &c->s_ftab,
+                    &c->f_const, &c->s_fmsrows, &c->s_fmsur, &c->s_fmsuf, &c->s_fmsui, &c->xfer_stage, &c->lbyidx,
+                    &c->fetch_stage, &c->tpr_snap, &c->tpr_ctl, &c->nx_alt, &c->nx_vs, &c->nx_gse, &c->nx_gsn};
+  for (auto *b : rest) release(*b);
   bk_release(c);
   halo_release(c);
   comm_release(c);
 }
 
 // ---- home order (host side): arrays cross the ABI in aircraft-index order
-// and live on the device in home order (Ctx::h2id_h)
-template <typename F>
-static void by_size(size_t esz, F f) {
-  if (esz == 8) f((const uint64_t *)nullptr);
-  else if (esz == 4) f((const uint32_t *)nullptr);
-  else f((const uint8_t *)nullptr);
-}
-
-// Batched home-order transfers of whole arrays (h in [0, n)): the host
-// arrays cross PCIe as they are, in aircraft-index order (one async copy
-// each into a device staging area), and ONE kernel permutes every field on
-// the device -- dst[h] = stage[h2id[h]] on upload, stage[h2id[h]] = src[h] on
-// download -- with one stream synchronisation per batch.  (Per array, the
-// host-side permutation loop and a synchronisation each cost the ASAS drop-in
-// ~0.2 ms per array at 100k aircraft.)
-constexpr int kXferMax = 24;
+// and live on the device in home order (Ctx::h2id_h).  HomeBatch is the one
+// way between the two: the arrays of a batch cross PCIe
+// through the pinned stage in ONE DMA, ONE kernel moves every field between
+// the device arrays and the staging area, one stream synchronisation per batch
+// (a host permutation loop and a synchronisation per array cost the ASAS
+// drop-in ~0.2 ms per array at 100k aircraft).  Upload and download of all
+// rows: index order in the staging area, stage[h2id[h]] <-> dev[h].  Download
+// of a rank's rows [hb, he): packed, stage[h - hb] = dev[h]; the host then
+// writes host[h2id[h]] for these rows and no other entry
+constexpr int kXferMax = 32;  // (bsa_sim_read_fms moves 25 arrays)
+enum XferMode { kXferUp, kXferDown, kXferDownPacked };
 struct XferFields {
   void *dev[kXferMax];
   unsigned long long off[kXferMax];  // byte offset of the field in the staging area
   int esz[kXferMax];
-  int nf, up;
+  int nf, mode;
 };
-__global__ __launch_bounds__(256) void k_home_xfer(int n, XferFields f, const unsigned *__restrict__ h2id,
+template <typename T>
+__device__ __forceinline__ void xfer_one(void *dev, void *stage, int h, unsigned i, bool up) {
+  if (up) ((T *)dev)[h] = ((const T *)stage)[i];
+  else ((T *)stage)[i] = ((const T *)dev)[h];
+}
+__global__ __launch_bounds__(256) void k_home_xfer(int hb, int he, XferFields f, const unsigned *__restrict__ h2id,
                                                    unsigned char *__restrict__ stage) {
-  const int h = blockIdx.x * blockDim.x + threadIdx.x;
-  if (h >= n) return;
-  const unsigned i = h2id[h];
+  const int h = hb + blockIdx.x * blockDim.x + threadIdx.x;
+  if (h >= he) return;
+  const unsigned i = f.mode == kXferDownPacked ? (unsigned)(h - hb) : h2id[h];
+  const bool up = f.mode == kXferUp;
   for (int q = 0; q < f.nf; ++q) {
-    unsigned char *sp = stage + f.off[q];
-    unsigned char *dp = (unsigned char *)f.dev[q];
-    if (f.esz[q] == 8) {
-      if (f.up) ((unsigned long long *)dp)[h] = ((const unsigned long long *)sp)[i];
-      else ((unsigned long long *)sp)[i] = ((const unsigned long long *)dp)[h];
-    } else if (f.esz[q] == 4) {
-      if (f.up) ((unsigned *)dp)[h] = ((const unsigned *)sp)[i];
-      else ((unsigned *)sp)[i] = ((const unsigned *)dp)[h];
-    } else {
-      if (f.up) dp[h] = sp[i];
-      else sp[i] = dp[h];
-    }
+    if (f.esz[q] == 8) xfer_one<unsigned long long>(f.dev[q], stage + f.off[q], h, i, up);
+    else if (f.esz[q] == 4) xfer_one<unsigned>(f.dev[q], stage + f.off[q], h, i, up);
+    else xfer_one<unsigned char>(f.dev[q], stage + f.off[q], h, i, up);
   }
+}
+
+template <typename T>
+static void scatter_rows(void *dst, const void *src, const unsigned *ids, int64_t rows) {
+  for (int64_t r = 0; r < rows; ++r) ((T *)dst)[ids[r]] = ((const T *)src)[r];
 }
 
 struct HomeBatch {
   Ctx *c;
-  bool up;
+  int64_t hb, he;  // home rows (an upload: all)
   XferFields f{};
   const void *hsrc[kXferMax] = {};
   void *hdst[kXferMax] = {};
   size_t bytes = 0;
-  HomeBatch(Ctx *cc, bool upload) : c(cc), up(upload) { f.up = upload ? 1 : 0; }
+  HomeBatch(Ctx *cc, bool upload, int64_t hb_ = 0, int64_t he_ = -1) : c(cc), hb(hb_), he(he_ < 0 ? cc->n : he_) {
+    f.mode = upload ? kXferUp : hb == 0 && he == c->n ? kXferDown : kXferDownPacked;
+  }
   // upload: device array dev <- host src (index order); download: host dst <- dev
-  int add(void *dev, const void *hsrc_, void *hdst_, int esz) {
+  int add(const void *dev, const void *hsrc_, void *hdst_, int esz) {
     if (f.nf == kXferMax && run()) return -1;
     const int q = f.nf++;
-    f.dev[q] = dev;
+    f.dev[q] = const_cast<void *>(dev);
     f.esz[q] = esz;
     f.off[q] = bytes;
     hsrc[q] = hsrc_;
     hdst[q] = hdst_;
-    bytes += ((size_t)c->n * esz + 255) / 256 * 256;
+    bytes += ((size_t)std::max<int64_t>(he - hb, 0) * esz + 255) / 256 * 256;
     return 0;
   }
   int run() {
-    const int64_t n = c->n;
-    if (f.nf == 0 || n <= 0) return 0;
-    if (!ensure(c, c->xfer_stage, bytes, "transfer staging")) return -1;
+    const int64_t rows = he - hb;
+    const bool up = f.mode == kXferUp;
+    const int nf = f.nf;
+    const size_t total = bytes;
+    f.nf = 0;  // (the batch is empty again, whatever happens below)
+    bytes = 0;
+    if (nf == 0 || rows <= 0) return 0;  // (a rank without rows: nothing to launch)
+    if (!ensure(c, c->xfer_stage, total, "transfer staging")) return -1;
     unsigned char *st = (unsigned char *)c->xfer_stage.p;
     // the host side through the pinned staging: one parallel host copy and
     // ONE DMA of the whole batch (pin_stage, bsa_ctx.hip)
-    unsigned char *pin = pin_stage(c, bytes);
+    unsigned char *pin = pin_stage(c, total);
     if (!pin) return -1;
     HostCopy jobs[kXferMax];
     if (up) {
-      for (int q = 0; q < f.nf; ++q) jobs[q] = HostCopy{pin + f.off[q], hsrc[q], (size_t)n * f.esz[q]};
-      host_copy(jobs, f.nf);
-      BSA_HIP(c, hipMemcpyAsync(st, pin, bytes, hipMemcpyHostToDevice, c->stream));
+      for (int q = 0; q < nf; ++q) jobs[q] = HostCopy{pin + f.off[q], hsrc[q], (size_t)rows * f.esz[q]};
+      host_copy(jobs, nf);
+      BSA_HIP(c, hipMemcpyAsync(st, pin, total, hipMemcpyHostToDevice, c->stream));
     }
-    hipLaunchKernelGGL(k_home_xfer, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (int)n, f,
+    XferFields g = f;
+    g.nf = nf;
+    hipLaunchKernelGGL(k_home_xfer, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, (int)hb, (int)he, g,
                        (const unsigned *)c->h2id.p, st);
     BSA_HIP(c, hipGetLastError());
-    if (!up) BSA_HIP(c, hipMemcpyAsync(pin, st, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (!up) BSA_HIP(c, hipMemcpyAsync(pin, st, total, hipMemcpyDeviceToHost, c->stream));
     BSA_HIP(c, hipStreamSynchronize(c->stream));
-    if (!up) {
-      for (int q = 0; q < f.nf; ++q) jobs[q] = HostCopy{hdst[q], pin + f.off[q], (size_t)n * f.esz[q]};
-      host_copy(jobs, f.nf);
+    if (f.mode == kXferDown) {
+      for (int q = 0; q < nf; ++q) jobs[q] = HostCopy{hdst[q], pin + f.off[q], (size_t)rows * f.esz[q]};
+      host_copy(jobs, nf);
+    } else if (f.mode == kXferDownPacked) {
+      const unsigned *ids = c->h2id_h.data() + hb;
+      for (int q = 0; q < nf; ++q) {
+        const int e = f.esz[q];
+        const auto scatter = e == 8 ? scatter_rows<uint64_t> : e == 4 ? scatter_rows<uint32_t> : scatter_rows<uint8_t>;
+        scatter(hdst[q], pin + f.off[q], ids, rows);
+      }
     }
-    f.nf = 0;
-    bytes = 0;
     return 0;
   }
 };
-
-// dst[h] (device) = src[h2id[h]] (host), h in [0, n)
-static int put_home(Ctx *c, void *dst, const void *src, size_t esz, std::vector<char> &tmp) {
-  const int64_t n = c->n;
-  tmp.resize((size_t)n * esz + 8);
-  const unsigned *H = c->h2id_h.data();
-  by_size(esz, [&](auto tag) {
-    using T = std::remove_const_t<std::remove_pointer_t<decltype(tag)>>;
-    T *t = (T *)tmp.data();
-    const T *q = (const T *)src;
-    for (int64_t h = 0; h < n; ++h) t[h] = q[H[h]];
-  });
-  BSA_HIP(c, hipMemcpyAsync(dst, tmp.data(), (size_t)n * esz, hipMemcpyHostToDevice, c->stream));
-  BSA_HIP(c, hipStreamSynchronize(c->stream));
-  return 0;
-}
-
-// out[h2id[h]] (host) = src[h] (device), h in [hb, he)
-static int get_home(Ctx *c, void *out, const void *src, size_t esz, int64_t hb, int64_t he,
-                    std::vector<char> &tmp) {
-  if (he <= hb) return 0;
-  tmp.resize((size_t)(he - hb) * esz + 8);
-  BSA_HIP(c, hipMemcpyAsync(tmp.data(), (const char *)src + (size_t)hb * esz, (size_t)(he - hb) * esz,
-                            hipMemcpyDeviceToHost, c->stream));
-  BSA_HIP(c, hipStreamSynchronize(c->stream));
-  const unsigned *H = c->h2id_h.data();
-  by_size(esz, [&](auto tag) {
-    using T = std::remove_const_t<std::remove_pointer_t<decltype(tag)>>;
-    const T *t = (const T *)tmp.data();
-    T *o = (T *)out;
-    for (int64_t h = hb; h < he; ++h) o[H[h]] = t[h - hb];
-  });
-  return 0;
-}
 
 // the maps of a home order h2id_h (host + device) and this rank's lpos
 int set_home_maps(Ctx *c) {
@@ -776,55 +749,34 @@ int bsa_sim_init(bsa_ctx *cc, int64_t n, const bsa_sim_state *s, const bsa_sim_p
   if (n <= 0 || n > 0x7fffffff) return bsa::fail(c, "bad n");
   if (bsa::check_params(c, p)) return -1;
   BSA_HIP(c, hipSetDevice(c->device));
-  const double *src[] = {s->lat, s->lon, s->alt, s->tas, s->hdg, s->vs, s->gs, s->trk, s->gseast,
-                         s->gsnorth, s->ap_trk, s->ap_tas, s->ap_alt, s->ap_vs, s->selalt, s->bank,
-                         s->eps, s->accel, s->asas_alt};
-  for (auto q : src)
-    if (!q) return bsa::fail(c, "bsa_sim_init: NULL array");
+  for (int k = 0; k < bsa::kSimStateFields; ++k)
+    if (!bsa::ptr_at(s, k)) return bsa::fail(c, "bsa_sim_init: NULL array");
   // aircraft-index order first: the home order is the spatial order of this state
   if (bsa_set_state(cc, n, s->lat, s->lon, s->trk, s->gs, s->alt, s->vs)) return -1;
   if (bsa::home_order(c, p->tla, c->h2id_h)) return -1;
   bsa::set_rank_rows(c);
   if (bsa::set_home_maps(c)) return -1;
-  // the all-gathered arrays hold nranks x rpr entries (in-place all-gather)
-  const size_t NG = (size_t)std::max<int64_t>(n, c->sim_rpr * c->nranks) * 8;
-  for (int k = 0; k < 6; ++k)
-    if (!bsa::ensure_keep(c, c->own[k], NG, "gathered state")) return -1;
-  std::vector<char> tmp;
-  const double *st6[6] = {s->lat, s->lon, s->trk, s->gs, s->alt, s->vs};
-  for (int k = 0; k < 6; ++k)
-    if (bsa::put_home(c, c->own[k].p, st6[k], 8, tmp)) return -1;
-  bsa::DevBuf *dst[] = {&c->s_tas, &c->s_hdg, &c->s_gse, &c->s_gsn, &c->s_aptrk, &c->s_aptas,
-                        &c->s_apalt, &c->s_apvs, &c->s_selalt, &c->s_bank, &c->s_eps, &c->s_accel,
-                        &c->s_aalt};
-  const double *hs[] = {s->tas, s->hdg, s->gseast, s->gsnorth, s->ap_trk, s->ap_tas, s->ap_alt,
-                        s->ap_vs, s->selalt, s->bank, s->eps, s->accel, s->asas_alt};
-  const size_t N8 = (size_t)n * 8;
-  for (int k = 0; k < 13; ++k) {
-    if (!bsa::ensure(c, *dst[k], k < 4 ? NG : N8, "sim state")) return -1;
-    if (bsa::put_home(c, dst[k]->p, hs[k], 8, tmp)) return -1;
-  }
-  // ASAS arrays: asas.trk/tas start at traf.trk/tas (asas.py:405-409), vs 0, inactive
-  if (!bsa::ensure(c, c->s_atrk, N8, "asas trk") || !bsa::ensure(c, c->s_atas, N8, "asas tas") ||
-      !bsa::ensure(c, c->s_avs, N8, "asas vs") || !bsa::ensure(c, c->s_ase, (size_t)n * 4, "asase") ||
-      !bsa::ensure(c, c->s_asn, (size_t)n * 4, "asasn") || !bsa::ensure(c, c->s_active, n, "active") ||
-      !bsa::ensure(c, c->s_altprev, N8, "pre-step altitude") || !bsa::ensure(c, c->s_ax, N8, "ax") ||
-      !bsa::ensure(c, c->s_dropped, n, "ResumeNav drops"))
-    return -1;
-  BSA_HIP(c, hipMemsetAsync(c->s_dropped.p, 0, n, c->stream));
   c->sim_noreso = c->sim_resooff = false;  // empty NORESO / RESOOFF lists
-  c->sim_atmos = false;
-  BSA_HIP(c, hipMemsetAsync(c->s_ax.p, 0, N8, c->stream));   // traf.ax: 0 at create
-  c->sim_limits = false;
-  c->sim_perf = false;
-  c->sim_forces = false;
-  c->sim_fms = false;
-  if (bsa::put_home(c, c->s_atrk.p, s->trk, 8, tmp) || bsa::put_home(c, c->s_atas.p, s->tas, 8, tmp)) return -1;
-  BSA_HIP(c, hipMemsetAsync(c->s_avs.p, 0, N8, c->stream));
-  BSA_HIP(c, hipMemsetAsync(c->s_ase.p, 0, (size_t)n * 4, c->stream));
-  BSA_HIP(c, hipMemsetAsync(c->s_asn.p, 0, (size_t)n * 4, c->stream));
-  BSA_HIP(c, hipMemsetAsync(c->s_active.p, 0, n, c->stream));
-  BSA_HIP(c, hipStreamSynchronize(c->stream));
+  c->sim_atmos = c->sim_limits = c->sim_perf = c->sim_forces = c->sim_fms = false;
+  // every always-present array (kSimArrays); the all-gathered ones hold nranks
+  // x rpr entries (in-place all-gather).  Zero unless a state field fills it:
+  // asas.vs, asase / asasn, inactive, traf.ax, no ResumeNav drops
+  const size_t NG = (size_t)std::max<int64_t>(n, c->sim_rpr * c->nranks);
+  for (const bsa::SimArray &a : bsa::kSimArrays) {
+    if (a.guard != bsa::kSimAlways) continue;
+    bsa::DevBuf &b = bsa::buf_at(c, a.buf);
+    if (!bsa::ensure(c, b, (a.gathered ? NG : (size_t)n) * a.esz, "sim state")) return -1;
+    if (!bsa::sim_field_names(c, &b)) BSA_HIP(c, hipMemsetAsync(b.p, 0, (size_t)n * a.esz, c->stream));
+  }
+  // the state, and what starts at it: asas.trk / tas at traf.trk / tas (asas.py:405-409)
+  bsa::HomeBatch up(c, true);
+  for (int k = 0; k < bsa::kSimStateFields; ++k) {
+    const bsa::SimField &f = bsa::kSimFields[k];
+    if (up.add(bsa::buf_at(c, f.buf).p, bsa::ptr_at(s, k), nullptr, 8) ||
+        (f.also && up.add((c->*f.also).p, bsa::ptr_at(s, k), nullptr, 8)))
+      return -1;
+  }
+  if (up.run()) return -1;
   if (!bsa::ensure(c, c->sim_ctl, 64, "sim control words")) return -1;
   BSA_HIP(c, hipMemsetAsync(c->sim_ctl.p, 0, 64, c->stream));
   BSA_HIP(c, hipStreamSynchronize(c->stream));
@@ -901,9 +853,10 @@ int bsa_sim_set_limits(bsa_ctx *cc, const double *hmax, const double *vmin, cons
     if (!q) return bsa::fail(c, "bsa_sim_set_limits: NULL envelope array");
   const size_t N8 = (size_t)c->n * 8;
   if (!bsa::ensure(c, c->s_env, 6 * N8, "OpenAP envelope")) return -1;
-  std::vector<char> tmp;
+  bsa::HomeBatch up(c, true);
   for (int k = 0; k < 6; ++k)
-    if (bsa::put_home(c, (char *)c->s_env.p + k * N8, src[k], 8, tmp)) return -1;
+    if (up.add((char *)c->s_env.p + k * N8, src[k], nullptr, 8)) return -1;
+  if (up.run()) return -1;
   c->sim_limits = true;
   return 0;
 }
@@ -933,8 +886,8 @@ int bsa_sim_set_perf(bsa_ctx *cc, int64_t ntypes, const double *table, const int
       !bsa::ensure(c, c->s_phase, (size_t)n, "flight phase"))
     return -1;
   BSA_HIP(c, hipMemcpyAsync(c->s_ptab.p, table, tb, hipMemcpyHostToDevice, c->stream));
-  std::vector<char> tmp;
-  if (bsa::put_home(c, c->s_ptype.p, type_idx, 4, tmp)) return -1;
+  bsa::HomeBatch up(c, true);
+  if (up.add(c->s_ptype.p, type_idx, nullptr, 4) || up.run()) return -1;
   BSA_HIP(c, hipMemsetAsync(c->s_phase.p, 0, (size_t)n, c->stream));
   BSA_HIP(c, hipStreamSynchronize(c->stream));
   c->sim_perf = true;
@@ -947,13 +900,10 @@ int bsa_sim_read_perf(bsa_ctx *cc, uint8_t *phase, double *ax) {
   if (!c) return -1;
   if (!c->sim_ready) return bsa::fail(c, "bsa_sim_read_perf before bsa_sim_init");
   BSA_HIP(c, hipSetDevice(c->device));
-  std::vector<char> tmp;
-  if (phase) {
-    if (!c->sim_perf) return bsa::fail(c, "no flight phase: bsa_sim_set_perf is off");
-    if (bsa::get_home(c, phase, c->s_phase.p, 1, c->sim_rb, c->sim_re, tmp)) return -1;
-  }
-  if (ax && bsa::get_home(c, ax, c->s_ax.p, 8, c->sim_rb, c->sim_re, tmp)) return -1;
-  return 0;
+  if (phase && !c->sim_perf) return bsa::fail(c, "no flight phase: bsa_sim_set_perf is off");
+  bsa::HomeBatch down(c, false, c->sim_rb, c->sim_re);
+  if ((phase && down.add(c->s_phase.p, nullptr, phase, 1)) || (ax && down.add(c->s_ax.p, nullptr, ax, 8))) return -1;
+  return down.run();
 }
 
 int bsa_sim_set_forces(bsa_ctx *cc, int64_t ntypes, const double *ftable, const double *mass) {
@@ -990,8 +940,8 @@ int bsa_sim_set_forces(bsa_ctx *cc, int64_t ntypes, const double *ftable, const 
   if (bsa::forces_consts(c)) return -1;
   BSA_HIP(c, hipMemcpyAsync(c->s_ftab.p, ftable, (size_t)ntypes * bsa::perf::kForceCols * 8, hipMemcpyHostToDevice,
                             c->stream));
-  std::vector<char> tmp;
-  if (bsa::put_home(c, c->s_fmass.p, mass, 8, tmp)) return -1;
+  bsa::HomeBatch up(c, true);
+  if (up.add(c->s_fmass.p, mass, nullptr, 8) || up.run()) return -1;
   // switching on: outputs (perf.bank among them) and the fuel accumulators start at 0
   BSA_HIP(c, hipMemsetAsync(c->s_fout.p, 0, 6 * N8, c->stream));
   BSA_HIP(c, hipMemsetAsync(c->s_fused.p, 0, N8, c->stream));
@@ -1009,21 +959,19 @@ int bsa_sim_read_forces(bsa_ctx *cc, double *cd0, double *drag, double *thrustra
   if (!c->sim_forces) return bsa::fail(c, "no forces: bsa_sim_set_forces is off");
   BSA_HIP(c, hipSetDevice(c->device));
   const int64_t n = c->n, rb = c->sim_rb, re = c->sim_re;
-  std::vector<char> tmp;
+  bsa::HomeBatch down(c, false, rb, re);
   double *dst[6] = {cd0, drag, thrustratio, thrust, fuelflow, bank};
   for (int k = 0; k < 6; ++k)
-    if (dst[k] && bsa::get_home(c, dst[k], (const double *)c->s_fout.p + (size_t)k * n, 8, rb, re, tmp)) return -1;
-  if (fuel_used && re > rb) {
-    // the committed steps + the last completed step's share, added here as the
-    // next step's launch will add it (one fp64 add: the same bits)
-    std::vector<double> pend((size_t)n, 0.0);
-    if (bsa::get_home(c, fuel_used, c->s_fused.p, 8, rb, re, tmp) ||
-        bsa::get_home(c, pend.data(), c->s_fpend.p, 8, rb, re, tmp))
-      return -1;
-    for (int64_t h = rb; h < re; ++h) {
-      const unsigned i = c->h2id_h[(size_t)h];
-      fuel_used[i] = fuel_used[i] + pend[i];
-    }
+    if (dst[k] && down.add((const double *)c->s_fout.p + (size_t)k * n, nullptr, dst[k], 8)) return -1;
+  // fuel burnt: the committed steps + the last completed step's share, added
+  // here as the next step's launch will add it (one fp64 add: the same bits)
+  std::vector<double> pend(fuel_used ? (size_t)n : 0, 0.0);
+  if (fuel_used && (down.add(c->s_fused.p, nullptr, fuel_used, 8) || down.add(c->s_fpend.p, nullptr, pend.data(), 8)))
+    return -1;
+  if (down.run()) return -1;
+  for (int64_t h = rb; fuel_used && h < re; ++h) {
+    const unsigned i = c->h2id_h[(size_t)h];
+    fuel_used[i] = fuel_used[i] + pend[i];
   }
   return 0;
 }
@@ -1040,13 +988,10 @@ int bsa_sim_set_fms(bsa_ctx *cc, int64_t nrows, const double *route_rows, const 
   }
   if (nrows < 0 || nrows > 0x7fffffff / 8) return bsa::fail(c, "bsa_sim_set_fms: bad route row count");
   if (!rt_off || !rt_n || !iactwp || !st) return bsa::fail(c, "bsa_sim_set_fms: NULL array");
-  const double *reals[bsa::kFmsReals] = {st->actwp_lat, st->actwp_lon, st->actwp_nextaltco, st->actwp_xtoalt, st->actwp_spd,
-                             st->actwp_vs, st->actwp_turndist, st->actwp_flyby, st->actwp_next_qdr, st->dist2vs,
-                             st->vnavvs, st->swvnavvs, st->selspd, st->selvs, st->apvsdef};
-  const uint8_t *flags[bsa::kFmsFlags] = {st->swlnav, st->swvnav, st->abco, st->belco};
-  for (auto q : reals)
+  const bsa::FmsFields ff = bsa::fms_fields(*st);
+  for (auto q : ff.reals)
     if (!q) return bsa::fail(c, "bsa_sim_set_fms: NULL array");
-  for (auto q : flags)
+  for (auto q : ff.flags)
     if (!q) return bsa::fail(c, "bsa_sim_set_fms: NULL array");
   if (!std::isfinite(simt) || std::isnan(t0)) return bsa::fail(c, "bsa_sim_set_fms: simt / t0 not finite");
   const int64_t n = c->n;
@@ -1059,14 +1004,15 @@ int bsa_sim_set_fms(bsa_ctx *cc, int64_t nrows, const double *route_rows, const 
       !bsa::ensure(c, c->s_fmsur, bsa::kFmsUndoReals * N * 8, "FMS undo set") || !bsa::ensure(c, c->s_fmsuf, 2 * N, "FMS undo flags") ||
       !bsa::ensure(c, c->s_fmsui, N * 4, "FMS undo waypoints"))
     return -1;
-  std::vector<char> tmp;
-  for (int q = 0; q < bsa::kFmsReals; ++q)
-    if (bsa::put_home(c, (double *)c->s_fmsr.p + q * N, reals[q], 8, tmp)) return -1;
-  for (int q = 0; q < bsa::kFmsFlags; ++q)
-    if (bsa::put_home(c, (uint8_t *)c->s_fmsf.p + q * N, flags[q], 1, tmp)) return -1;
+  bsa::HomeBatch up(c, true);
   const int32_t *ints[bsa::kFmsInts] = {iactwp, rt_off, rt_n};
+  for (int q = 0; q < bsa::kFmsReals; ++q)
+    if (up.add((double *)c->s_fmsr.p + q * N, ff.reals[q], nullptr, 8)) return -1;
+  for (int q = 0; q < bsa::kFmsFlags; ++q)
+    if (up.add((uint8_t *)c->s_fmsf.p + q * N, ff.flags[q], nullptr, 1)) return -1;
   for (int q = 0; q < bsa::kFmsInts; ++q)
-    if (bsa::put_home(c, (int32_t *)c->s_fmsi.p + q * N, ints[q], 4, tmp)) return -1;
+    if (up.add((int32_t *)c->s_fmsi.p + q * N, ints[q], nullptr, 4)) return -1;
+  if (up.run()) return -1;
   if (nrows) BSA_HIP(c, hipMemcpyAsync(c->s_fmsrows.p, route_rows, (size_t)nrows * 64, hipMemcpyHostToDevice, c->stream));
   BSA_HIP(c, hipStreamSynchronize(c->stream));
   c->fms_simt = simt;
@@ -1083,24 +1029,21 @@ int bsa_sim_read_fms(bsa_ctx *cc, const bsa_fms_state *st, int32_t *iactwp, doub
   if (!c->sim_ready) return bsa::fail(c, "bsa_sim_read_fms before bsa_sim_init");
   if (!c->sim_fms) return bsa::fail(c, "no FMS state: bsa_sim_set_fms is off");
   BSA_HIP(c, hipSetDevice(c->device));
-  const int64_t rb = c->sim_rb, re = c->sim_re;
   const size_t N = (size_t)c->n;
-  std::vector<char> tmp;
+  bsa::HomeBatch down(c, false, c->sim_rb, c->sim_re);
   if (st) {
-    double *reals[bsa::kFmsReals] = {st->actwp_lat, st->actwp_lon, st->actwp_nextaltco, st->actwp_xtoalt, st->actwp_spd,
-                         st->actwp_vs, st->actwp_turndist, st->actwp_flyby, st->actwp_next_qdr, st->dist2vs,
-                         st->vnavvs, st->swvnavvs, st->selspd, st->selvs, st->apvsdef};
-    uint8_t *flags[bsa::kFmsFlags] = {st->swlnav, st->swvnav, st->abco, st->belco};
+    const bsa::FmsFields ff = bsa::fms_fields(*st);
     for (int q = 0; q < bsa::kFmsReals; ++q)
-      if (reals[q] && bsa::get_home(c, reals[q], (const double *)c->s_fmsr.p + q * N, 8, rb, re, tmp)) return -1;
+      if (ff.reals[q] && down.add((const double *)c->s_fmsr.p + q * N, nullptr, ff.reals[q], 8)) return -1;
     for (int q = 0; q < bsa::kFmsFlags; ++q)
-      if (flags[q] && bsa::get_home(c, flags[q], (const uint8_t *)c->s_fmsf.p + q * N, 1, rb, re, tmp)) return -1;
+      if (ff.flags[q] && down.add((const uint8_t *)c->s_fmsf.p + q * N, nullptr, ff.flags[q], 1)) return -1;
   }
-  if (iactwp && bsa::get_home(c, iactwp, c->s_fmsi.p, 4, rb, re, tmp)) return -1;
+  if (iactwp && down.add(c->s_fmsi.p, nullptr, iactwp, 4)) return -1;
   double *tg[5] = {ap_trk, ap_tas, ap_alt, ap_vs, selalt};
   const void *src[5] = {c->s_aptrk.p, c->s_aptas.p, c->s_apalt.p, c->s_apvs.p, c->s_selalt.p};
   for (int q = 0; q < 5; ++q)
-    if (tg[q] && bsa::get_home(c, tg[q], src[q], 8, rb, re, tmp)) return -1;
+    if (tg[q] && down.add(src[q], nullptr, tg[q], 8)) return -1;
+  if (down.run()) return -1;
   if (simt) *simt = c->fms_simt;
   if (t0) *t0 = c->fms_t0;
   if (ticks) *ticks = c->fms_ticks;
@@ -1113,27 +1056,18 @@ int bsa_sim_update(bsa_ctx *cc, const bsa_sim_state *s) {
   if (!s) return bsa::fail(c, "NULL sim state");
   if (!c->sim_ready) return bsa::fail(c, "bsa_sim_update before bsa_sim_init");
   BSA_HIP(c, hipSetDevice(c->device));
-  struct {
-    const double *src;
-    void *dst;
-  } cp[] = {{s->lat, c->own[0].p},     {s->lon, c->own[1].p},     {s->trk, c->own[2].p},
-            {s->gs, c->own[3].p},      {s->alt, c->own[4].p},     {s->vs, c->own[5].p},
-            {s->tas, c->s_tas.p},      {s->hdg, c->s_hdg.p},      {s->gseast, c->s_gse.p},
-            {s->gsnorth, c->s_gsn.p},  {s->ap_trk, c->s_aptrk.p}, {s->ap_tas, c->s_aptas.p},
-            {s->ap_alt, c->s_apalt.p}, {s->ap_vs, c->s_apvs.p},   {s->selalt, c->s_selalt.p},
-            {s->bank, c->s_bank.p},    {s->eps, c->s_eps.p},      {s->accel, c->s_accel.p},
-            {s->asas_alt, c->s_aalt.p}};
   // the replicated CD inputs are rewritten on every rank (in the sim's home order)
   bool any_cd = false, all_rep = true;
   bsa::HomeBatch hb(c, true);
-  for (int k = 0; k < 19; ++k) {
-    const bool rep = k < 6 || k == 8 || k == 9;  // the arrays the all-gather replicates
-    if (!cp[k].src) {
-      all_rep = all_rep && !rep;
+  for (int k = 0; k < bsa::kSimStateFields; ++k) {
+    const bsa::SimField &f = bsa::kSimFields[k];
+    const void *src = bsa::ptr_at(s, k);
+    if (!src) {
+      all_rep = all_rep && !f.replicated;
       continue;
     }
-    if (k < 10) any_cd = true;
-    if (hb.add(cp[k].dst, cp[k].src, nullptr, 8)) return -1;
+    any_cd = any_cd || f.cd_input;
+    if (hb.add(bsa::buf_at(c, f.buf).p, src, nullptr, 8)) return -1;
   }
   if (hb.run()) return -1;
   c->sim_prepped = false;  // prepared records are of the old state
@@ -1156,19 +1090,16 @@ int bsa_sim_read(bsa_ctx *cc, bsa_sim_out *o) {
   if (!c->sim_ready) return bsa::fail(c, "bsa_sim_read before bsa_sim_init");
   BSA_HIP(c, hipSetDevice(c->device));
   if (bsa::sim_gather(c) || bsa::sim_gather_asas(c)) return -1;
-  struct {
-    void *dst;
-    const void *src;
-    size_t esz;
-  } cp[] = {{o->lat, c->own[0].p, 8},      {o->lon, c->own[1].p, 8},      {o->alt, c->own[4].p, 8},
-            {o->tas, c->s_tas.p, 8},       {o->hdg, c->s_hdg.p, 8},       {o->vs, c->own[5].p, 8},
-            {o->gs, c->own[3].p, 8},       {o->trk, c->own[2].p, 8},      {o->gseast, c->s_gse.p, 8},
-            {o->gsnorth, c->s_gsn.p, 8},   {o->asas_trk, c->s_atrk.p, 8}, {o->asas_tas, c->s_atas.p, 8},
-            {o->asas_vs, c->s_avs.p, 8},   {o->asas_alt, c->s_aalt.p, 8},
-            {o->active, c->s_active.p, 1}};
+  // bsa_sim_out starts as bsa_sim_state does; then asas trk / tas / vs / alt and active
   bsa::HomeBatch hb(c, false);
-  for (auto &e : cp)
-    if (e.dst && hb.add(const_cast<void *>(e.src), nullptr, e.dst, (int)e.esz)) return -1;
+  for (int k = 0; k < bsa::kSimOutFields; ++k)
+    if (bsa::ptr_at(o, k) && hb.add(bsa::buf_at(c, bsa::kSimFields[k].buf).p, nullptr, bsa::ptr_at(o, k), 8)) return -1;
+  void *asas[5] = {o->asas_trk, o->asas_tas, o->asas_vs, o->asas_alt, o->active};
+  const int from[5] = {0, 1, 2, 3, 6};
+  for (int k = 0; k < 5; ++k) {
+    const bsa::AsasArray &a = bsa::kAsasArrays[from[k]];
+    if (asas[k] && hb.add((c->*a.buf).p, nullptr, asas[k], a.esz)) return -1;
+  }
   return hb.run();
 }
 
@@ -1384,21 +1315,23 @@ int bsa_sim_set_reso_lists(bsa_ctx *cc, const uint8_t *noreso, const uint8_t *re
   if (!c) return -1;
   if (!c->sim_ready) return bsa::fail(c, "bsa_sim_set_reso_lists before bsa_sim_init");
   BSA_HIP(c, hipSetDevice(c->device));
-  std::vector<char> tmp;
   struct {
     const uint8_t *h;
     bsa::DevBuf *b;
     bool *on;
   } ls[2] = {{noreso, &c->s_noreso, &c->sim_noreso}, {resooff, &c->s_resooff, &c->sim_resooff}};
-  for (auto &l : ls) {
-    *l.on = false;
-    if (!l.h) continue;
-    std::vector<uint8_t> v(l.h, l.h + c->n);
-    for (auto &x : v) x = x ? 1 : 0;
-    if (!bsa::ensure(c, *l.b, (size_t)c->n, "NORESO / RESOOFF list") || bsa::put_home(c, l.b->p, v.data(), 1, tmp))
+  std::vector<uint8_t> v[2];  // membership normalised to 0 / 1
+  bsa::HomeBatch up(c, true);
+  for (int k = 0; k < 2; ++k) {
+    *ls[k].on = false;
+    if (!ls[k].h) continue;
+    v[k].assign(ls[k].h, ls[k].h + c->n);
+    for (auto &x : v[k]) x = x ? 1 : 0;
+    if (!bsa::ensure(c, *ls[k].b, (size_t)c->n, "NORESO / RESOOFF list") || up.add(ls[k].b->p, v[k].data(), nullptr, 1))
       return -1;
-    *l.on = true;
   }
+  if (up.run()) return -1;
+  for (auto &l : ls) *l.on = l.h != nullptr;
   return 0;
 }
 
@@ -1407,23 +1340,12 @@ int bsa_sim_read_asas(bsa_ctx *cc, bsa_asas_out *o) {
   if (!c || !o) return -1;
   if (!c->sim_ready) return bsa::fail(c, "bsa_sim_read_asas before bsa_sim_init");
   BSA_HIP(c, hipSetDevice(c->device));
-  struct {
-    void *dst;
-    const void *src;
-    size_t esz;
-  } cp[] = {{o->trk, c->s_atrk.p, 8},   {o->tas, c->s_atas.p, 8},     {o->vs, c->s_avs.p, 8},
-            {o->alt, c->s_aalt.p, 8},   {o->asase, c->s_ase.p, 4},    {o->asasn, c->s_asn.p, 4},
-            {o->active, c->s_active.p, 1}, {o->dropped, c->s_dropped.p, 1}};
-  if (c->sim_rb == 0 && c->sim_re == c->n) {  // one rank: every row, one batch
-    bsa::HomeBatch hb(c, false);
-    for (auto &e : cp)
-      if (e.dst && hb.add(const_cast<void *>(e.src), nullptr, e.dst, (int)e.esz)) return -1;
-    return hb.run();
+  bsa::HomeBatch down(c, false, c->sim_rb, c->sim_re);
+  for (int k = 0; k < 8; ++k) {
+    const bsa::AsasArray &a = bsa::kAsasArrays[k];
+    if (bsa::ptr_at(o, k) && down.add((c->*a.buf).p, nullptr, bsa::ptr_at(o, k), a.esz)) return -1;
   }
-  std::vector<char> tmp;
-  for (auto &e : cp)
-    if (e.dst && bsa::get_home(c, e.dst, e.src, e.esz, c->sim_rb, c->sim_re, tmp)) return -1;
-  return 0;
+  return down.run();
 }
 
 int bsa_sim_set_atmos(bsa_ctx *cc, int on) {
@@ -1444,12 +1366,11 @@ int bsa_sim_read_atmos(bsa_ctx *cc, double *p, double *rho, double *temp) {
   if (!c) return -1;
   if (!c->sim_ready || !c->sim_atmos) return bsa::fail(c, "bsa_sim_read_atmos: atmosphere outputs are off");
   BSA_HIP(c, hipSetDevice(c->device));
-  std::vector<char> tmp;
+  bsa::HomeBatch down(c, false, c->sim_rb, c->sim_re);
   double *dst[3] = {p, rho, temp};
   for (int k = 0; k < 3; ++k)
-    if (dst[k] && bsa::get_home(c, dst[k], (const char *)c->s_atm.p + (size_t)k * c->n * 8, 8, c->sim_rb, c->sim_re, tmp))
-      return -1;
-  return 0;
+    if (dst[k] && down.add((const double *)c->s_atm.p + (size_t)k * c->n, nullptr, dst[k], 8)) return -1;
+  return down.run();
 }
 
 }  // extern "C"

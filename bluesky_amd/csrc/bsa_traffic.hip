@@ -61,39 +61,11 @@ struct PerAc {
   int count;  // sub-arrays of length n in the buffer (the envelope holds 6)
 };
 
-// every persistent per-aircraft array of the resident sim
+// every per-aircraft array that is part of the sim now (kSimArrays, bsa_internal.h)
 static std::vector<PerAc> per_aircraft(Ctx *c) {
   std::vector<PerAc> v;
-  for (int k = 0; k < 6; ++k) v.push_back({&c->own[k], 8, 1});
-  DevBuf *f64[] = {&c->s_tas,   &c->s_hdg,   &c->s_gse,    &c->s_gsn,   &c->s_aptrk, &c->s_aptas,
-                   &c->s_apalt, &c->s_apvs,  &c->s_selalt, &c->s_bank,  &c->s_eps,   &c->s_accel,
-                   &c->s_atrk,  &c->s_atas,  &c->s_avs,    &c->s_aalt,  &c->s_altprev, &c->s_ax,
-                   &c->tcpamax};
-  for (auto *b : f64) v.push_back({b, 8, 1});
-  v.push_back({&c->s_ase, 4, 1});
-  v.push_back({&c->s_asn, 4, 1});
-  v.push_back({&c->s_active, 1, 1});
-  v.push_back({&c->inconf, 1, 1});
-  // NORESO / RESOOFF membership and the last ResumeNav's drops (allocated on use)
-  for (auto *b : {&c->s_noreso, &c->s_resooff, &c->s_dropped})
-    if (b->p) v.push_back({b, 1, 1});
-  if (c->sim_limits) v.push_back({&c->s_env, 8, 6});
-  if (c->sim_atmos) v.push_back({&c->s_atm, 8, 3});
-  if (c->sim_perf) {
-    v.push_back({&c->s_ptype, 4, 1});
-    v.push_back({&c->s_phase, 1, 1});
-  }
-  if (c->sim_forces) {  // mass, the six outputs, fuel burnt and the last step's pending share
-    v.push_back({&c->s_fmass, 8, 1});
-    v.push_back({&c->s_fout, 8, 6});
-    v.push_back({&c->s_fused, 8, 1});
-    v.push_back({&c->s_fpend, 8, 1});
-  }
-  if (c->sim_fms) {  // the FMS state, its flags, iactwp / rt_off / rt_n (route rows stay where they are)
-    v.push_back({&c->s_fmsr, 8, kFmsReals});
-    v.push_back({&c->s_fmsf, 1, kFmsFlags});
-    v.push_back({&c->s_fmsi, 4, kFmsInts});
-  }
+  for (const SimArray &a : kSimArrays)
+    if (sim_array_on(c, a)) v.push_back({&buf_at(c, a.buf), a.esz, a.count});
   return v;
 }
 
@@ -369,7 +341,7 @@ static size_t rows_alloc(const Ctx *c, int64_t n) {
 
 static int multi_end(Ctx *c, Multi &m, const std::vector<int> &nh, const std::vector<int> &nid, int64_t created) {
   if (!m.on) return 0;
-  const int64_t n = c->n, rb = c->sim_rb, nr = c->sim_re - c->sim_rb;
+  const int64_t rb = c->sim_rb, nr = c->sim_re - c->sim_rb;
   // this rank's rows of the last detect's per-row outputs
   if (!ensure_keep(c, c->inconf, (size_t)std::max<int64_t>(nr, 1), "inconf") ||
       !ensure_keep(c, c->tcpamax, (size_t)std::max<int64_t>(nr, 1) * 8, "tcpamax"))
@@ -426,7 +398,6 @@ static int multi_end(Ctx *c, Multi &m, const std::vector<int> &nh, const std::ve
       BSA_HIP(c, hipStreamSynchronize(c->stream));
     }
   }
-  (void)n;
   // the halo plan's capacities for the new partition (every replica is complete)
   return halo_init_caps(c);
 }
@@ -559,11 +530,8 @@ int bsa_sim_create(bsa_ctx *cc, int64_t m, const bsa_sim_state *s) {
     return bsa::fail(c, "bsa_sim_create with OpenAP limits on: switch them off, create, set them again");
   if (c->sim_fms)
     return bsa::fail(c, "bsa_sim_create with autopilot guidance on: create, then bsa_sim_set_fms again with the new routes");
-  const double *src[] = {s->lat, s->lon, s->alt, s->tas, s->hdg, s->vs, s->gs, s->trk, s->gseast,
-                         s->gsnorth, s->ap_trk, s->ap_tas, s->ap_alt, s->ap_vs, s->selalt, s->bank,
-                         s->eps, s->accel, s->asas_alt};
-  for (auto q : src)
-    if (!q) return bsa::fail(c, "bsa_sim_create: NULL array");
+  for (int k = 0; k < bsa::kSimStateFields; ++k)
+    if (!bsa::ptr_at(s, k)) return bsa::fail(c, "bsa_sim_create: NULL array");
   const int64_t n = c->n, nn = n + m;
   if (nn > 0x7fffffff) return bsa::fail(c, "n would exceed 2^31-1");
   BSA_HIP(c, hipSetDevice(c->device));
@@ -572,43 +540,35 @@ int bsa_sim_create(bsa_ctx *cc, int64_t m, const bsa_sim_state *s) {
   if (bsa::multi_begin(c, mu)) return -1;
   std::vector<bsa::PerAc> arrs = bsa::change_arrays(c, mu);
   const size_t NA = bsa::rows_alloc(c, nn);
-  for (auto &pa : arrs)
+  for (auto &pa : arrs) {
     if (!bsa::ensure_keep(c, *pa.b, (pa.count == 1 ? NA : (size_t)nn) * pa.esz * pa.count, "traffic array"))
       return -1;
-  const size_t M8 = (size_t)m * 8;
-  struct {
-    bsa::DevBuf *b;
-    const double *h;
-  } put[] = {{&c->own[0], s->lat},      {&c->own[1], s->lon},      {&c->own[2], s->trk},
-             {&c->own[3], s->gs},       {&c->own[4], s->alt},      {&c->own[5], s->vs},
-             {&c->s_tas, s->tas},       {&c->s_hdg, s->hdg},       {&c->s_gse, s->gseast},
-             {&c->s_gsn, s->gsnorth},   {&c->s_aptrk, s->ap_trk},  {&c->s_aptas, s->ap_tas},
-             {&c->s_apalt, s->ap_alt},  {&c->s_apvs, s->ap_vs},    {&c->s_selalt, s->selalt},
-             {&c->s_bank, s->bank},     {&c->s_eps, s->eps},       {&c->s_accel, s->accel},
-             {&c->s_atrk, s->trk},      {&c->s_atas, s->tas},      {&c->s_aalt, s->asas_alt},  // asas.py:402-407
-             {&c->s_altprev, s->alt}};
-  for (auto &e : put)
-    BSA_HIP(c, hipMemcpyAsync((char *)e.b->p + (size_t)n * 8, e.h, M8, hipMemcpyHostToDevice, c->stream));
-  // defaults of TrafficArrays.create (trafficarrays.py:73-95): 0 / False
-  struct {
-    bsa::DevBuf *b;
-    int esz;
-  } zero[] = {{&c->s_avs, 8}, {&c->s_ax, 8}, {mu.on ? &mu.gtcp : &c->tcpamax, 8}, {&c->s_ase, 4}, {&c->s_asn, 4},
-              {&c->s_active, 1}, {mu.on ? &mu.ginc : &c->inconf, 1}};
-  for (auto &z : zero)
-    BSA_HIP(c, hipMemsetAsync((char *)z.b->p + (size_t)n * z.esz, 0, (size_t)m * z.esz, c->stream));
-  for (auto *b : {&c->s_noreso, &c->s_resooff, &c->s_dropped})  // not in the lists, nothing dropped
-    if (b->p) BSA_HIP(c, hipMemsetAsync((char *)b->p + n, 0, (size_t)m, c->stream));
-  if (c->sim_atmos) {  // the atmosphere's three sub-arrays move to the new stride n + m (via a copy:
-    bsa::DevBuf tmp;    // the old and new places of a sub-array may overlap)
-    if (!bsa::ensure(c, tmp, (size_t)n * 24, "atmosphere")) return -1;
-    BSA_HIP(c, hipMemcpyAsync(tmp.p, c->s_atm.p, (size_t)n * 24, hipMemcpyDeviceToDevice, c->stream));
-    BSA_HIP(c, hipMemsetAsync(c->s_atm.p, 0, (size_t)nn * 24, c->stream));
-    for (int k = 0; k < 3; ++k)
-      BSA_HIP(c, hipMemcpyAsync((char *)c->s_atm.p + (size_t)k * nn * 8, (char *)tmp.p + (size_t)k * n * 8,
-                                (size_t)n * 8, hipMemcpyDeviceToDevice, c->stream));
+    if (pa.count == 1) continue;
+    // sub-arrays move to the new stride n + m (via a copy: the old and new places of a sub-array may overlap)
+    const size_t sub = (size_t)n * pa.esz, nsub = (size_t)nn * pa.esz;
+    bsa::DevBuf tmp;
+    if (!bsa::ensure(c, tmp, sub * pa.count, "restrided traffic array")) return -1;
+    BSA_HIP(c, hipMemcpyAsync(tmp.p, pa.b->p, sub * pa.count, hipMemcpyDeviceToDevice, c->stream));
+    for (int k = 0; k < pa.count; ++k)
+      BSA_HIP(c, hipMemcpyAsync((char *)pa.b->p + k * nsub, (char *)tmp.p + k * sub, sub, hipMemcpyDeviceToDevice,
+                                c->stream));
     BSA_HIP(c, hipStreamSynchronize(c->stream));
     bsa::release(tmp);
+  }
+  // the new aircraft's state, and what starts at it: asas.trk / tas at trk / tas (asas.py:402-407)
+  for (int k = 0; k < bsa::kSimStateFields; ++k) {
+    const bsa::SimField &f = bsa::kSimFields[k];
+    bsa::DevBuf *to[2] = {&bsa::buf_at(c, f.buf), f.also ? &(c->*f.also) : nullptr};
+    for (bsa::DevBuf *b : to)
+      if (b) BSA_HIP(c, hipMemcpyAsync((char *)b->p + (size_t)n * 8, bsa::ptr_at(s, k), (size_t)m * 8,
+                                       hipMemcpyHostToDevice, c->stream));
+  }
+  // every other array: the defaults of TrafficArrays.create (trafficarrays.py:73-95), 0 / False -- in
+  // neither reso list, nothing dropped
+  for (auto &pa : arrs) {
+    if (bsa::sim_field_names(c, pa.b)) continue;
+    for (int k = 0; k < pa.count; ++k)
+      BSA_HIP(c, hipMemsetAsync((char *)pa.b->p + ((size_t)k * nn + n) * pa.esz, 0, (size_t)m * pa.esz, c->stream));
   }
   BSA_HIP(c, hipStreamSynchronize(c->stream));
   // new aircraft have no resopairs and were in no previous pair set: empty CSR rows

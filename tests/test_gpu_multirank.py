@@ -775,3 +775,134 @@ def test_sharded_nonfinite_aircraft_equal_world1(ctx):
     for k in ('ci', 'cj', 'qdr', 'dist', 'tcpa', 'tinconf', 'li', 'lj', 'inconf'):
         assert np.array_equal(pairs[k], exp_pairs[k]), k
     assert np.isnan(pairs['tcpamax']).all()
+
+
+# ---------------------------------------------------------------- the per-rank reads (home-order range downloads)
+def union_of_rank_reads(res, n):
+    """res: each rank's (raw reads on sentinel-filled arrays, its row ids).  No
+    rank wrote outside its rows; returns the ranks' own entries put together."""
+    from tests.test_gpu_sim import sentinel, untouched
+    ids = np.concatenate([i for _, i in res])
+    assert np.array_equal(np.sort(ids), np.arange(n))
+    full = {}
+    for k in res[0][0]:
+        full[k] = sentinel(n, res[0][0][k].dtype.type)
+        for r, (got, i) in enumerate(res):
+            assert len(got[k]) == n and untouched(got[k], i), 'rank %d wrote %s outside its rows' % (r, k)
+            full[k][i] = got[k][i]
+    return full
+
+
+def same_bits(got, exp, what=''):
+    from tests.test_gpu_sim import bits
+    assert got.keys() == exp.keys()
+    for k in exp:
+        assert np.array_equal(bits(got[k]), bits(exp[k])), what + k
+
+
+def test_rank_reads_leave_other_rows_alone(ctx):
+    """Two ranks, 1100 aircraft (rank 0: 1024 rows, rank 1: 76 in a partial tile),
+    limits, perf, forces, atmosphere and reso lists on, 3 steps: bsa_sim_read_asas
+    / _perf / _forces / _atmos write this rank's entries of sentinel-filled arrays
+    and nothing else, and both ranks' entries together are the one-rank run's, bitwise."""
+    from tests.test_gpu_sim import features_case, features_sim, raw_reads
+    n = 1100
+    case = features_case(n, 101, False)
+    ref = features_sim(case, ctx)
+    ref.step(3)
+    exp = raw_reads(ctx, False)
+
+    def rank(r, c, g):
+        sim = features_sim(case, c, rank=r, world=2, group=g)
+        sim.step(3)
+        return raw_reads(c, False), sim.row_ids()
+
+    res = run_ranks(2, rank)
+    assert [len(i) for _, i in res] == [1024, 76]
+    same_bits(union_of_rank_reads(res, n), exp)
+    assert exp['forces_fuel_used'].max() > 0 and exp['atmos_p'].min() > 0
+
+
+@pytest.mark.parametrize('case', ['flight64', 'box1100'])
+def test_rank_read_fms_leaves_other_rows_alone(ctx, case):
+    """bsa_sim_read_fms on two ranks, 25 steps: the flight golden's 64 aircraft
+    (rank 1 holds no rows) and 1100 with generated routes (1024 + 76 rows)."""
+    from tests.test_gpu_fms import flight_case, fms_sim, fms_traffic, quiet_params
+    from tests.test_gpu_sim import raw_read_fms
+    if case == 'flight64':
+        g, init, rt = flight_case()
+        p = quiet_params(g)
+    else:
+        init, rt = fms_traffic(1100, 61)
+        p = resident.params(cd_every=1)
+    n = len(init['lat'])
+    ref = fms_sim(init, rt, p, ctx)
+    ref.step(25)
+    exp = raw_read_fms(ctx)
+    ref.set_fms(None)
+
+    def rank(r, c, g):
+        sim = fms_sim(init, rt, p, c, rank=r, world=2, group=g)
+        sim.step(25)
+        return raw_read_fms(c), sim.row_ids()
+
+    res = run_ranks(2, rank)
+    assert [len(i) for _, i in res] == ([64, 0] if case == 'flight64' else [1024, 76])
+    same_bits(union_of_rank_reads(res, n), exp)
+    assert (exp['fms_iactwp'] > 0).any() or case == 'flight64'
+
+
+def test_sharded_delete_carries_every_array(ctx):
+    """tests/test_gpu_sim.py's delete of 50 aircraft across home position 512 on
+    two ranks (700 aircraft: 512 + 188 rows; FMS off, the combination is refused
+    with it on): the ranks' reads after the delete, put together, equal np.delete
+    of those before, bitwise, and so does the gathered state."""
+    from tests.test_gpu_sim import delete_across_rank_edge, features_case, features_sim, raw_reads
+    n = 700
+    case = features_case(n, 113, False)
+    gone = delete_across_rank_edge(case, n)
+
+    def rank(r, c, g):
+        sim = features_sim(case, c, rank=r, world=2, group=g)
+        sim.step(4)
+        before = (raw_reads(c, False), sim.row_ids(), sim.read())
+        sim.delete(gone)
+        after = (raw_reads(c, False), sim.row_ids(), sim.read())
+        sim.step(2)
+        return before, after, sim.stats()['steps'], len(sim.read()['lat'])
+
+    res = run_ranks(2, rank)
+    before = union_of_rank_reads([x[0][:2] for x in res], n)
+    after = union_of_rank_reads([x[1][:2] for x in res], n - 50)
+    same_bits(after, {k: np.delete(v, gone) for k, v in before.items()})
+    for b, a, steps, left in res:
+        for k, v in b[2].items():
+            assert np.array_equal(a[2][k], np.delete(v, gone)), k
+        assert steps == 6 and left == n - 50
+    assert before['forces_fuel_used'].max() > 0
+
+
+def test_reads_on_a_rank_without_rows(ctx):
+    """Two ranks, 300 aircraft: rank 0 holds all of them, rank 1 none.  Every
+    _read call succeeds on rank 1 and leaves its sentinel-filled arrays as they
+    were; rank 0's are the one-rank run's (as is the collective bsa_sim_read's
+    state on both)."""
+    from tests.test_gpu_sim import features_case, features_sim, raw_reads
+    n = 300
+    case = features_case(n, 127, True)
+    ref = features_sim(case, ctx)
+    ref.step(3)
+    exp, exp_st = raw_reads(ctx, True), ref.read()
+    ref.set_fms(None)
+
+    def rank(r, c, g):
+        sim = features_sim(case, c, rank=r, world=2, group=g)
+        sim.step(3)
+        return raw_reads(c, True), sim.row_ids(), sim.read()
+
+    res = run_ranks(2, rank)
+    assert [len(i) for _, i, _ in res] == [n, 0]
+    same_bits(union_of_rank_reads([x[:2] for x in res], n), exp)
+    for _, _, st in res:
+        for k, v in exp_st.items():
+            assert np.array_equal(st[k], v), k

@@ -562,3 +562,146 @@ def test_nothing_of_one_call_leaks_into_the_next():
     finally:
         for c in ctxs:
             c.close()
+
+
+# ---------------------------------------------------------------- the per-aircraft arrays and their home-order transfers
+# sentinels of the raw reads below: a fixed quiet-NaN bit pattern for floats, 0xA5 bytes for integers
+SENTINEL = {np.float64: (np.uint64, 0x7ff8a5a5a5a5a5a5), np.float32: (np.uint32, 0x7fc0a5a5),
+            np.int32: (np.uint32, 0xa5a5a5a5), np.uint8: (np.uint8, 0xa5)}
+CPTR = {np.float64: _lib._c_dp, np.float32: _lib._c_fp, np.int32: _lib._c_i32p, np.uint8: _lib._c_u8p}
+
+
+def sentinel(n, dtype):
+    u, v = SENTINEL[dtype]
+    return np.full(n, v, u).view(dtype)
+
+
+def bits(a):
+    return a.view(SENTINEL[a.dtype.type][0])
+
+
+def untouched(a, rows):
+    """Every entry of ``a`` outside ``rows`` still holds its sentinel's bit pattern."""
+    other = np.ones(len(a), bool)
+    other[rows] = False
+    return bool((bits(a)[other] == SENTINEL[a.dtype.type][1]).all())
+
+
+def raw_reads(c, fms_on):
+    """bsa_sim_read_asas / _perf / _forces / _atmos (and _fms) called directly (not
+    through the zero-filling wrappers) on sentinel-filled full-n arrays."""
+    import ctypes
+    n = c.n
+
+    def P(a):
+        return _lib.ptr(a, CPTR[a.dtype.type])
+
+    def f8():
+        return sentinel(n, np.float64)
+
+    o = {'asas_' + k: f8() for k in ('trk', 'tas', 'vs', 'alt')}
+    o.update(asas_asase=sentinel(n, np.float32), asas_asasn=sentinel(n, np.float32),
+             asas_active=sentinel(n, np.uint8), asas_dropped=sentinel(n, np.uint8))
+    ao = _lib.AsasOut(**{k[5:]: P(v) for k, v in o.items()})
+    c.check(c.lib.bsa_sim_read_asas(c.h, ctypes.byref(ao)), 'bsa_sim_read_asas')
+    o.update(perf_phase=sentinel(n, np.uint8), perf_ax=f8())
+    c.check(c.lib.bsa_sim_read_perf(c.h, P(o['perf_phase']), P(o['perf_ax'])), 'bsa_sim_read_perf')
+    fk = _lib.FORCE_OUTPUTS + ('fuel_used',)
+    o.update({'forces_' + k: f8() for k in fk})
+    c.check(c.lib.bsa_sim_read_forces(c.h, *[P(o['forces_' + k]) for k in fk]), 'bsa_sim_read_forces')
+    o.update({'atmos_' + k: f8() for k in ('p', 'rho', 'temp')})
+    c.check(c.lib.bsa_sim_read_atmos(c.h, *[P(o['atmos_' + k]) for k in ('p', 'rho', 'temp')]), 'bsa_sim_read_atmos')
+    if fms_on:
+        o.update(raw_read_fms(c))
+    return o
+
+
+def raw_read_fms(c):
+    import ctypes
+    n = c.n
+    o = {'fms_' + k: sentinel(n, np.float64) for k in _lib.FMS_REALS + _lib.FMS_TARGETS}
+    o.update({'fms_' + k: sentinel(n, np.uint8) for k in _lib.FMS_FLAGS})
+    o['fms_iactwp'] = sentinel(n, np.int32)
+    st = _lib.FmsState(**{k: _lib.ptr(o['fms_' + k]) for k in _lib.FMS_REALS},
+                       **{k: _lib.ptr(o['fms_' + k], _lib._c_u8p) for k in _lib.FMS_FLAGS})
+    c.check(c.lib.bsa_sim_read_fms(c.h, ctypes.byref(st), _lib.ptr(o['fms_iactwp'], _lib._c_i32p),
+                                   *[_lib.ptr(o['fms_' + k]) for k in _lib.FMS_TARGETS], None, None, None),
+            'bsa_sim_read_fms')
+    return o
+
+
+def features_case(n, seed, fms_on):
+    """Traffic with OpenAP types, an envelope, both reso lists and (``fms_on``) routes:
+    everything ``features_sim`` switches on, built once per test."""
+    from bluesky_amd import fms
+    from tests.test_gpu_perf_forces import traffic
+    tr = traffic(n, seed, spread=30.0)
+    rng = np.random.default_rng(seed)
+    tr['env'] = dict(hmax=np.full(n, 11500.0), vmin=rng.uniform(70., 90., n), vmax=rng.uniform(140., 160., n),
+                     vsmin=np.full(n, -15.0), vsmax=rng.uniform(8., 12., n), axmax=np.full(n, 2.0))
+    tr['lists'] = (rng.random(n) < 0.2, rng.random(n) < 0.2)
+    tr['routes'] = fms.synthetic_routes(tr['init'], seed=seed) if fms_on else None
+    return tr
+
+
+def features_sim(case, ctx, **kw):
+    """A resident sim (CD every step, ResumeNav) with limits, perf, forces, the
+    atmosphere, both reso lists and the case's routes, if any, switched on."""
+    p = resident.params(cd_every=1, resume_nav=True)
+    p.mvp.swnoreso = p.mvp.swresooff = 1
+    sim = resident.ResidentSim(case['init'], p, ctx=ctx, limits=case['env'], **kw)
+    sim.set_perf(case['table'], case['tidx'])
+    sim.set_forces(case['ftable'], case['mass'])
+    sim.ctx.sim_set_atmos(True)
+    sim.ctx.sim_set_reso_lists(*case['lists'])
+    if case['routes'] is not None:
+        sim.set_fms(*case['routes'])
+    return sim
+
+
+def delete_across_rank_edge(case, n):
+    """50 indices: 0, n - 1 and 24 from either side of home position 512 (the home
+    order is that of the initial traffic: a scratch sim playing rank 0 of 2 names
+    the aircraft of homes [0, 512))."""
+    c = _lib.Context(0)
+    try:
+        resident.ResidentSim(case['init'], resident.params(), ctx=c)
+        c.sim_probe_rank(0, 2)
+        low = c.sim_row_ids()
+    finally:
+        c.close()
+    assert len(low) == 512
+    high = np.setdiff1d(np.arange(n), low)
+    rng = np.random.default_rng(n)
+    gone = np.concatenate([[0, n - 1], rng.choice(np.setdiff1d(low, [0, n - 1]), 24, replace=False),
+                           rng.choice(np.setdiff1d(high, [0, n - 1]), 24, replace=False)])
+    assert len(np.unique(gone)) == 50
+    return np.sort(gone)
+
+
+def test_every_per_aircraft_array_follows_a_delete(ctx):
+    """One rank, 700 aircraft, every optional per-aircraft array on (limits, perf,
+    forces, atmosphere, both reso lists, FMS): after 4 steps 50 aircraft from both
+    sides of home position 512, index 0 and n - 1 among them, are deleted.  Every
+    array any _read call returns equals np.delete of the read before, bitwise, and
+    the step runs on the carried state."""
+    n = 700
+    case = features_case(n, 113, True)
+    gone = delete_across_rank_edge(case, n)
+    sim = features_sim(case, ctx)
+    sim.step(4)
+
+    def reads():
+        o = raw_reads(ctx, True)
+        o.update({'state_' + k: np.asarray(v).view(np.uint8) if v.dtype == bool else v for k, v in sim.read().items()})
+        return o
+
+    before = reads()
+    assert before['forces_fuel_used'].max() > 0 and before['perf_phase'].any() and before['atmos_p'].min() > 0
+    sim.delete(gone)
+    after = reads()
+    for k, b in before.items():
+        assert len(b) == n and np.array_equal(bits(np.delete(b, gone)), bits(after[k])), k
+    sim.step(2)
+    assert sim.stats()['steps'] == 6 and len(sim.read()['lat']) == n - 50
+    sim.set_fms(None)
