@@ -229,6 +229,10 @@ SIGNATURES.update({
     'bsa_sim_set_fms': (ctypes.c_int, [_vp, ctypes.c_int64, _c_dp, _c_i32p, _c_i32p, _c_i32p, ctypes.POINTER(FmsState),
                                        ctypes.c_double, ctypes.c_double]),
     'bsa_sim_read_fms': (ctypes.c_int, [_vp, ctypes.POINTER(FmsState), _c_i32p] + [_c_dp] * 7 + [_c_i64p]),
+    'bsa_fms_recover': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _c_dp, _c_i32p, _c_i32p, _c_i32p] +
+                        [_c_dp] * 7 + [ctypes.POINTER(FmsState), _c_dp, _c_i32p]),
+    'bsa_sim_set_recovery': (ctypes.c_int, [_vp, ctypes.c_int]),
+    'bsa_sim_read_dropcount': (ctypes.c_int, [_vp, _c_i32p]),
 })
 
 UNIQUE_ID_BYTES = 128
@@ -731,6 +735,46 @@ class Context:
                                            *[ptr(out[k]) for k in FMS_TARGETS]), 'bsa_fms_update')
         for k in FMS_FLAGS:
             out[k] = out[k].astype(bool)
+        return out
+
+    def fms_recover(self, rows, rt_off, rt_n, state, count):
+        """bsa_fms_recover: Route.findact + Route.direct applied ``count[k]`` times to
+        aircraft k.  ``rows`` / ``rt_off`` / ``rt_n`` / ``state`` as ``fms_update`` takes
+        them (of FMS_TRAFFIC ``ax`` is not read and may be absent; of FMS_TARGETS only
+        ``ap_alt``).  Returns a new dict of FMS_REALS, FMS_FLAGS, ``ap_alt`` and
+        ``iactwp`` after the call."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] != ROUTE_COLS:
+            raise ValueError('route table must be nrows x %d' % ROUTE_COLS)
+        off = np.ascontiguousarray(rt_off, dtype=np.int32).ravel()
+        cnt = np.ascontiguousarray(rt_n, dtype=np.int32).ravel()
+        count = np.ascontiguousarray(count, dtype=np.int32).ravel()
+        n = len(off)
+        names = [k for k in FMS_TRAFFIC if k != 'ax']
+        tr = [f64(state[k]).ravel() for k in names]
+        out = {k: np.array(state[k], dtype=np.float64).ravel() for k in FMS_REALS + ('ap_alt',)}
+        out.update({k: np.array(state[k]).astype(np.uint8).ravel() for k in FMS_FLAGS})
+        out['iactwp'] = np.array(state['iactwp'], dtype=np.int32).ravel()
+        for k, a in list(zip(names, tr)) + list(out.items()) + [('rt_n', cnt), ('count', count)]:
+            if len(a) != n:
+                raise ValueError('FMS array %s has length %d != %d' % (k, len(a), n))
+        st = FmsState(**{k: ptr(out[k]) for k in FMS_REALS}, **{k: ptr(out[k], _c_u8p) for k in FMS_FLAGS})
+        self.check(self.lib.bsa_fms_recover(self.h, n, rows.shape[0], ptr(rows), ptr(off, _c_i32p), ptr(cnt, _c_i32p),
+                                            ptr(out['iactwp'], _c_i32p), *[ptr(a) for a in tr], ctypes.byref(st),
+                                            ptr(out['ap_alt']), ptr(count, _c_i32p)), 'bsa_fms_recover')
+        for k in FMS_FLAGS:
+            out[k] = out[k].astype(bool)
+        return out
+
+    def sim_set_recovery(self, on=True):
+        """bsa_sim_set_recovery: waypoint recovery after ResumeNav in the resident step."""
+        self.check(self.lib.bsa_sim_set_recovery(self.h, 1 if on else 0), 'bsa_sim_set_recovery')
+
+    def sim_read_dropcount(self):
+        """bsa_sim_read_dropcount: resopairs ResumeNav dropped per ownship in the last CD
+        call (this rank's rows of a full-n int32 array, other rows 0)."""
+        out = np.zeros(self.n, np.int32)
+        self.check(self.lib.bsa_sim_read_dropcount(self.h, ptr(out, _c_i32p)), 'bsa_sim_read_dropcount')
         return out
 
     def sim_set_fms(self, rows=None, rt_off=None, rt_n=None, state=None, simt=0.0, t0=-999.):

@@ -58,12 +58,9 @@ struct BkIn {
   unsigned *ncol;
   uint8_t *active;         // full-N
   uint8_t *dropped;        // full-N (home order) or NULL: the row dropped a pair this call
+  int *dropcnt;            // ... and how many (a deleted intruder's pair counts like any other)
   unsigned long long *stats;
 };
-
-__device__ __forceinline__ bool bk_aborted(const unsigned long long *gate, const unsigned *sticky) {
-  return sticky[0] != 0 || gate[0] >= kGateOverflow;
-}
 
 // ResumeNav's decision for resopair (i, j), asas.py:424-452.  j == kDangling:
 // the intruder was deleted (bsa_sim_delete) -- idx2 < 0 switches ASAS off for
@@ -134,18 +131,20 @@ __global__ __launch_bounds__(256) void k_bk_write(BkIn in) {
   if (r >= in.nrows) return;
   const int i = in.rb + r;
   unsigned pos = in.nptr[r];
-  bool any = false, seen = false, drop = false;
+  bool any = false, seen = false;
+  int drop = 0;
   bk_merge(in, r, [&](unsigned j) {
     seen = true;
     if (bk_keep(in, i, (int)j)) {
       in.ncol[pos++] = j;
       any = true;
     } else {
-      drop = true;  // asas.py:454-468: ASAS off, waypoint recovery (route.direct) for the ownship
+      ++drop;  // asas.py:454-468: ASAS off, waypoint recovery (findact + route.direct) for the ownship, per pair
     }
   });
   if (seen) in.active[i] = any ? 1 : 0;
   if (in.dropped) in.dropped[i] = drop ? 1 : 0;
+  if (in.dropcnt) in.dropcnt[i] = drop;
 }
 
 // is (r, c) in the CSR (ptr over rows 0.., ascending cols)?
@@ -361,6 +360,7 @@ static BkIn bk_in(Ctx *c, const BkDev &d) {
   in.ncol = (unsigned *)c->bk_ncol.p;
   in.active = d.active;
   in.dropped = d.dropped;
+  in.dropcnt = d.dropcnt;
   in.stats = (unsigned long long *)c->bk_stats.p;
   return in;
 }

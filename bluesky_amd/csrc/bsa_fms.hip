@@ -139,6 +139,65 @@ int fms_sim_restore(Ctx *c) {
   return 0;
 }
 
+// ---- waypoint recovery: findact + direct once per resopair
+// that ResumeNav dropped for the aircraft.  The lane loads and stores only what
+// fms::fms_recover reads and writes (tr[6], traf.ax, is not read).
+__device__ __forceinline__ void recover_lane(const FmsArrays &a, int k, int count) {
+  const int nwp = a.rt_n[k];
+  if (nwp <= 0) return;   // findact: -1, nothing is touched
+  fms::Lane L;
+  L.lat = a.tr[0][k], L.lon = a.tr[1][k], L.alt = a.tr[2][k], L.tas = a.tr[3][k];
+  L.gs = a.tr[4][k], L.trk = a.tr[5][k], L.bank = a.tr[7][k];
+  L.wlat = a.st[0][k], L.wlon = a.st[1][k], L.nextaltco = a.st[2][k], L.xtoalt = a.st[3][k];
+  L.spd = a.st[4][k], L.vs = a.st[5][k], L.turndist = a.st[6][k], L.flyby = a.st[7][k];
+  L.dist2vs = a.st[9][k], L.selspd = a.st[12][k];
+  L.swlnav = a.fl[0][k] != 0, L.swvnav = a.fl[1][k] != 0;
+  L.ap_alt = a.tg[2][k];
+  L.iactwp = a.iactwp[k];
+  fms::fms_recover(L, a.rows + (size_t)a.rt_off[k] * fms::kRouteCols, nwp, count);
+  a.st[0][k] = L.wlat, a.st[1][k] = L.wlon, a.st[2][k] = L.nextaltco, a.st[3][k] = L.xtoalt;
+  a.st[4][k] = L.spd, a.st[5][k] = L.vs, a.st[6][k] = L.turndist, a.st[7][k] = L.flyby;
+  a.st[9][k] = L.dist2vs, a.st[12][k] = L.selspd;
+  a.fl[0][k] = L.swlnav ? 1 : 0;
+  a.tg[2][k] = L.ap_alt;
+  a.iactwp[k] = L.iactwp;
+}
+
+// The standalone call: aircraft [0, n), count[k] applications each.  A wave
+// without a non-zero count leaves after loading its counts.
+__global__ __launch_bounds__(64) void k_fms_recover(int n, FmsArrays a, const int *__restrict__ count) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const int cnt = count[k];
+  if (cnt <= 0) return;
+  recover_lane(a, k, cnt);
+}
+
+// The resident step's launch after k_bk_write of a CD step (resume_nav), on rows
+// [rb, re) of the PRE-step state, before K4' forms pilot.alt from ap.alt.
+// count: k_bk_write's pairs dropped per row in this call (home order).  Behind
+// the abort test of the bookkeeping kernels it changes nothing.
+__global__ __launch_bounds__(64) void k_sim_recover(int rb, int re, FmsArrays a, const int *__restrict__ count,
+                                                    const unsigned long long *__restrict__ gate,
+                                                    const unsigned *__restrict__ sticky) {
+  if (bk_aborted(gate, sticky)) return;
+  const int k = rb + blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= re) return;
+  const int cnt = count[k];
+  if (cnt <= 0) return;
+  recover_lane(a, k, cnt);
+}
+
+int fms_sim_recover(Ctx *c) {
+  const int64_t rb = c->sim_rb, re = c->sim_re;
+  if (re <= rb) return 0;
+  hipLaunchKernelGGL(k_sim_recover, dim3((unsigned)((re - rb + 63) / 64)), dim3(64), 0, c->stream, (int)rb, (int)re,
+                     fms_sim_arrays(c), (const int *)c->s_dropcnt.p, (const unsigned long long *)c->sim_ctl.p,
+                     (const unsigned *)((const char *)c->sim_ctl.p + kSimCtlSticky));
+  BSA_HIP(c, hipGetLastError());
+  return 0;
+}
+
 // Every index the kernel uses unguarded, checked on the host: each aircraft's
 // rows inside the table, its active waypoint inside its route, and no LNAV
 // without a route (only an aircraft with LNAV on ever reads a row).
@@ -243,6 +302,87 @@ extern "C" int bsa_fms_update(bsa_ctx *cc, int64_t n, int64_t nrows, const doubl
   for (int q = 0; q < 5; ++q)
     BSA_HIP(c, hipMemcpyAsync(tg[q], d8[8 + bsa::kFmsReals + q], (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
   for (int q = 0; q < 2; ++q) BSA_HIP(c, hipMemcpyAsync(flags[q], d1[q], (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  BSA_HIP(c, hipMemcpyAsync(iactwp, d4[0], (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+  BSA_HIP(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+extern "C" int bsa_fms_recover(bsa_ctx *cc, int64_t n, int64_t nrows, const double *route_rows, const int32_t *rt_off,
+                               const int32_t *rt_n, int32_t *iactwp, const double *lat, const double *lon,
+                               const double *alt, const double *tas, const double *gs, const double *trk,
+                               const double *bank, const bsa_fms_state *st, double *ap_alt, const int32_t *count) {
+  Ctx *c = (Ctx *)cc;
+  if (!c) return -1;
+  if (n < 0 || n > 0x7fffffff) return bsa::fail(c, "bsa_fms_recover: bad n");
+  if (nrows < 0 || nrows > 0x7fffffff / bsa::fms::kRouteCols) return bsa::fail(c, "bsa_fms_recover: bad route row count");
+  if (!st) return bsa::fail(c, "bsa_fms_recover: NULL state");
+  const double *tr[7] = {lat, lon, alt, tas, gs, trk, bank};
+  const bsa::FmsFields ff = bsa::fms_fields(*st);
+  for (auto q : tr)
+    if (!q) return bsa::fail(c, "bsa_fms_recover: NULL array");
+  for (auto q : ff.reals)
+    if (!q) return bsa::fail(c, "bsa_fms_recover: NULL array");
+  for (auto q : ff.flags)
+    if (!q) return bsa::fail(c, "bsa_fms_recover: NULL array");
+  if (!rt_off || !rt_n || !iactwp || !ap_alt || !count || (nrows > 0 && !route_rows))
+    return bsa::fail(c, "bsa_fms_recover: NULL array");
+  if (bsa::fms_check_routes(c, "bsa_fms_recover", n, nrows, rt_off, rt_n, iactwp, st->swlnav)) return -1;
+  for (int64_t k = 0; k < n; ++k)
+    if (count[k] < 0) return bsa::fail(c, "bsa_fms_recover: aircraft %lld: negative count %d", (long long)k, count[k]);
+  if (n == 0) return 0;
+  BSA_HIP(c, hipSetDevice(c->device));
+  // one device block: 7 + 15 + 1 fp64 arrays, 4 int32, 4 uint8, the route table
+  const size_t N8 = ((size_t)n * 8 + 255) / 256 * 256, N4 = ((size_t)n * 4 + 255) / 256 * 256,
+               N1 = ((size_t)n + 255) / 256 * 256;
+  const size_t rb = (size_t)nrows * bsa::fms::kRouteCols * 8;
+  constexpr int kD = 7 + bsa::kFmsReals + 1;
+  bsa::DevBuf buf;
+  struct Rel {
+    bsa::DevBuf *b;
+    ~Rel() { bsa::release(*b); }
+  } rel{&buf};
+  if (!bsa::ensure(c, buf, kD * N8 + 4 * N4 + 4 * N1 + rb + 256, "FMS recovery staging")) return -1;
+  char *base = (char *)buf.p;
+  bsa::FmsArrays a{};
+  double *d8[kD];
+  for (int q = 0; q < kD; ++q) d8[q] = (double *)(base + (size_t)q * N8);
+  int *d4[4];
+  for (int q = 0; q < 4; ++q) d4[q] = (int *)(base + kD * N8 + (size_t)q * N4);
+  uint8_t *d1[4];
+  for (int q = 0; q < 4; ++q) d1[q] = (uint8_t *)(base + kD * N8 + 4 * N4 + (size_t)q * N1);
+  double *drows = (double *)(base + kD * N8 + 4 * N4 + 4 * N1);
+  const int slot[7] = {0, 1, 2, 3, 4, 5, 7};   // FmsArrays::tr without traf.ax
+  for (int q = 0; q < 7; ++q) {
+    BSA_HIP(c, hipMemcpyAsync(d8[q], tr[q], (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    a.tr[slot[q]] = d8[q];
+  }
+  for (int q = 0; q < bsa::kFmsReals; ++q) {
+    BSA_HIP(c, hipMemcpyAsync(d8[7 + q], ff.reals[q], (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    a.st[q] = d8[7 + q];
+  }
+  double *dapalt = d8[7 + bsa::kFmsReals];
+  BSA_HIP(c, hipMemcpyAsync(dapalt, ap_alt, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+  a.tg[2] = dapalt;
+  const int32_t *h4[4] = {iactwp, rt_off, rt_n, count};
+  for (int q = 0; q < 4; ++q)
+    BSA_HIP(c, hipMemcpyAsync(d4[q], h4[q], (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  for (int q = 0; q < 4; ++q) {
+    BSA_HIP(c, hipMemcpyAsync(d1[q], ff.flags[q], (size_t)n, hipMemcpyHostToDevice, c->stream));
+    a.fl[q] = d1[q];
+  }
+  if (rb) BSA_HIP(c, hipMemcpyAsync(drows, route_rows, rb, hipMemcpyHostToDevice, c->stream));
+  a.iactwp = d4[0];
+  a.rt_off = d4[1];
+  a.rt_n = d4[2];
+  a.rows = drows;
+  hipLaunchKernelGGL(bsa::k_fms_recover, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, (int)n, a,
+                     (const int *)d4[3]);
+  BSA_HIP(c, hipGetLastError());
+  for (int q = 0; q < bsa::kFmsMutable; ++q)
+    BSA_HIP(c, hipMemcpyAsync(ff.reals[q], d8[7 + q], (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  BSA_HIP(c, hipMemcpyAsync(ap_alt, dapalt, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+  for (int q = 0; q < 2; ++q)
+    BSA_HIP(c, hipMemcpyAsync(ff.flags[q], d1[q], (size_t)n, hipMemcpyDeviceToHost, c->stream));
   BSA_HIP(c, hipMemcpyAsync(iactwp, d4[0], (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
   BSA_HIP(c, hipStreamSynchronize(c->stream));
   return 0;

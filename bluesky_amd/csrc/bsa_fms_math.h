@@ -214,5 +214,128 @@ __device__ __forceinline__ void tick(Lane &L, const double *rows, int off, int n
   L.swvnavvs = vv ? 1.0 : 0.0;
 }
 
+// ---- waypoint recovery after ResumeNav dropped a resopair (asas.py:459-465):
+// Route.findact (route.py:1043-1079) and Route.direct (route.py:635-688) on the
+// route table.
+
+// Route.findact: the aircraft's best active waypoint, -1 without a route.  The
+// search reads lat, lon of each of the aircraft's rows; argmin keeps numpy's
+// first minimum (a NaN is its minimum).  tan(bank) of 0 gives time_turn = inf,
+// or NaN (never > time_straight) when delhdg is 0 too, as numpy does.
+__device__ __forceinline__ int findact(const Lane &L, const double *route, int nwp) {
+  if (nwp <= 0) return -1;
+  if (nwp == 1) return 0;
+  const double coslat = cos(L.lat * kD2R);   // traf.coslat (traffic.py:482)
+  int near = 0;
+  double best = 0.;
+  for (int w = 0; w < nwp; ++w) {
+    const double2 r0 = *(const double2 *)(route + (size_t)w * kRouteCols);
+    const double dy = r0.x - L.lat;
+    const double dx = (r0.y - L.lon) * coslat;
+    const double d2 = dx * dx + dy * dy;
+    if (w == 0 || d2 < best || (d2 != d2 && best == best)) {
+      best = d2;
+      near = w;
+    }
+  }
+  int iw = near > L.iactwp ? near : L.iactwp;   // max(iactwp, argmin): never walks back
+  if (iw + 1 < nwp) {
+    const double2 r0 = *(const double2 *)(route + (size_t)iw * kRouteCols);
+    const double dy = r0.x - L.lat;
+    const double dx = (r0.y - L.lon) * coslat;
+    const double dist2 = dx * dx + dy * dy;
+    const double qdr = atan2(dx, dy) * kR2D;
+    const double delhdg = fabs(degto180(L.trk - qdr));
+    const double vt = L.tas > 0.01 ? L.tas : 0.01;   // max(0.01, tas)
+    const double time_turn = (vt * (delhdg * kD2R)) / (kin::kG0 * tan(L.bank));
+    const double time_straight = ((sqrt(dist2) * 60.) * kNM) / vt;
+    if (time_turn > time_straight) iw += 1;
+  }
+  return iw;
+}
+
+// wpdirfrom[i] of Route.calcfp (route.py:1005-1012) from the table: the leg
+// direction out of waypoint i, which is its row's nextqdr; the last waypoint
+// repeats the one before it, a one-waypoint route has 0.
+__device__ __forceinline__ double wpdirfrom(const double *route, int nwp, int i) {
+  if (i + 1 < nwp) return route[(size_t)i * kRouteCols + 7];
+  return nwp > 1 ? route[(size_t)(nwp - 2) * kRouteCols + 7] : 0.;
+}
+
+// Route.direct to waypoint wpidx, in the order it is written.  ComputeVNAV runs
+// BEFORE turndist is updated and is restated whole: Pilot.APorASAS of the same
+// step reads ap.alt, which only the next tick overwrites (next_qdr and, outside
+// ComputeVNAV, nextaltco stay as they were: direct does not set them).
+__device__ __forceinline__ void direct(Lane &L, const double *route, int nwp, int wpidx) {
+  L.iactwp = wpidx;
+  const double2 *row = (const double2 *)(route + (size_t)wpidx * kRouteCols);
+  const double2 r0 = row[0], r1 = row[1], r2 = row[2], r3 = row[3];
+  const double wpalt = r1.x, wpspd = r1.y, xtoalt = r2.x, toalt = r2.y;
+  L.wlat = r0.x;
+  L.wlon = r0.y;
+  L.flyby = r3.x;
+  // ---- ComputeVNAV(idx, wptoalt, wpxtoalt) (autopilot.py:207-304)
+  if (toalt < 0 || !L.swvnav) {
+    L.dist2vs = -999.;
+  } else if (L.alt > toalt + 10. * kFT) {
+    const double lim = toalt + xtoalt * kSteepness;
+    L.nextaltco = lim < L.alt ? lim : L.alt;
+    L.xtoalt = xtoalt;
+    L.dist2vs = L.turndist + fabs(L.alt - L.nextaltco) / kSteepness;
+    const double dy = L.wlat - L.lat;
+    const double dx = (L.wlon - L.lon) * cos(L.lat * kD2R);
+    const double legdist = (60. * kNM) * sqrt(dx * dx + dy * dy);
+    if (legdist < L.dist2vs) {   // the urgent descent
+      L.ap_alt = L.nextaltco;
+      const double num = legdist + xtoalt;
+      const double t2go = (num > 0.1 ? num : 0.1) / (L.gs > 0.01 ? L.gs : 0.01);
+      L.vs = (L.nextaltco - L.alt) / t2go;
+    } else {
+      L.vs = -kSteepness * (L.gs + (L.gs < 0.2 * L.tas ? 1. : 0.) * L.tas);
+    }
+  } else if (L.alt < toalt - 10. * kFT) {
+    L.nextaltco = toalt;
+    L.xtoalt = xtoalt;
+    L.ap_alt = L.nextaltco;
+    L.dist2vs = 99999. * kNM;
+    const double dy = L.wlat - L.lat;
+    const double dx = (L.wlon - L.lon) * cos(L.lat * kD2R);
+    const double legdist = (60. * kNM) * sqrt(dx * dx + dy * dy);
+    const double num = legdist + xtoalt;
+    const double t2go = (num > 0.1 ? num : 0.1) / (L.gs > 0.01 ? L.gs : 0.01);
+    L.vs = np_max(kSteepness * L.gs, (L.nextaltco - L.alt) / t2go);
+  } else {
+    L.dist2vs = -999.;
+  }
+  // ---- the speed of the next leg (route.py:651-674)
+  if (wpspd > 0.) {
+    const double cas = wpspd < 2.0 ? mach2cas(wpspd, wpalt < 0.0 ? L.alt : wpalt) : wpspd;
+    L.spd = cas;
+    if (L.swvnav) L.selspd = cas;
+  } else {
+    L.spd = -999.;
+  }
+  // ---- turndist [nm, as written] with the fixed 25 deg bank (route.py:677-684)
+  double qdr, dummy;
+  qdrdist(L.lat, L.lon, L.wlat, L.wlon, qdr, dummy);
+  const double turnrad = (((L.tas * L.tas) / tan(25. * kD2R)) / kin::kG0) / kNM;
+  const double dq = fabs(degto180(qdr - wpdirfrom(route, nwp, wpidx)));
+  L.turndist = ((L.flyby > 0.5 ? 1. : 0.) * turnrad) * fabs(tan(0.5 * ((dq > 5. ? dq : 5.) * kD2R)));
+  L.swlnav = true;
+}
+
+// ResumeNav's recovery of one ownship that lost `count` resopairs in one call:
+// findact + direct once per dropped pair, in sequence (the pair is not
+// idempotent).  route: this aircraft's rows.  Of the lane it reads lat lon alt
+// tas gs trk bank and reads or writes wlat wlon nextaltco xtoalt spd vs
+// turndist flyby dist2vs selspd ap_alt swlnav swvnav iactwp.
+__device__ __forceinline__ void fms_recover(Lane &L, const double *route, int nwp, int count) {
+  for (int q = 0; q < count; ++q) {
+    const int iw = findact(L, route, nwp);
+    if (iw < 0) return;   // no waypoints: nothing at all, swlnav included
+    direct(L, route, nwp, iw);
+  }
+}
+
 }  // namespace fms
 }  // namespace bsa

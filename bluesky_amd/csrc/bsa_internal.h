@@ -459,7 +459,9 @@ struct Ctx {
   int64_t fms_ticks = 0;
   // NORESO / RESOOFF membership (bsa_sim_set_reso_lists, u8 in home order) and
   // the rows whose ResumeNav dropped a pair in the last CD call (u8, home order)
-  DevBuf s_noreso, s_resooff, s_dropped;
+  // and how many pairs it dropped per row (int32: waypoint recovery runs once per pair)
+  DevBuf s_noreso, s_resooff, s_dropped, s_dropcnt;
+  bool sim_recovery = false;  // bsa_sim_set_recovery: k_sim_recover after k_bk_write
   DevBuf s_atm;          // traf.p / rho / Temp = vatmos(traf.alt) of the last step (3 x n), when on
   bool sim_atmos = false;
   bool sim_noreso = false, sim_resooff = false;
@@ -518,7 +520,7 @@ inline const SimArray kSimArrays[] = {
     {{&Ctx::s_fmass}, 8, 1, false, kSimForces},     {{&Ctx::s_fout}, 8, 6, false, kSimForces},
     {{&Ctx::s_fused}, 8, 1, false, kSimForces},     {{&Ctx::s_fpend}, 8, 1, false, kSimForces},
     {{&Ctx::s_fmsr}, 8, kFmsReals, false, kSimFms}, {{&Ctx::s_fmsf}, 1, kFmsFlags, false, kSimFms},
-    {{&Ctx::s_fmsi}, 4, kFmsInts, false, kSimFms},
+    {{&Ctx::s_fmsi}, 4, kFmsInts, false, kSimFms},   {{&Ctx::s_dropcnt}, 4, 1, false, kSimAlways},
 };
 // is the array part of the sim now (to be carried through a delete / create)?
 inline bool sim_array_on(Ctx *c, const SimArray &a) {
@@ -632,6 +634,8 @@ int fms_check_routes(Ctx *c, const char *who, int64_t n, int64_t nrows, const in
                      const int32_t *iactwp, const uint8_t *swlnav);
 int fms_sim_launch(Ctx *c, bool tick);
 int fms_sim_restore(Ctx *c);
+// waypoint recovery of the CD step just enqueued (after bk_apply, before K4'): k_sim_recover on this rank's rows
+int fms_sim_recover(Ctx *c);
 inline bool fms_ticks_at(double simt, double t0) { return t0 + 1.01 < simt || simt < t0 || simt < 1.01; }
 
 // ASAS bookkeeping of one CD call (bsa_asas.hip): bk_count before the gate
@@ -642,11 +646,18 @@ struct BkDev {
   const unsigned *h2id, *id2h;                // home <-> aircraft index
   uint8_t *active;
   uint8_t *dropped;             // per row: ResumeNav dropped one of its pairs (waypoint recovery)
+  int *dropcnt;                 // ... and how many (one findact + direct each)
   unsigned long long *gate;
   unsigned *sticky;
   unsigned long long *demand;   // resopairs overflow: pairs needed
   unsigned long long *kdemand;  // several ranks, key block overflow: words needed
 };
+#if defined(__HIPCC__)
+// the abort test of every kernel enqueued after the gate all-reduce of a CD step (the bookkeeping, k_sim_recover)
+__device__ __forceinline__ bool bk_aborted(const unsigned long long *gate, const unsigned *sticky) {
+  return sticky[0] != 0 || gate[0] >= kGateOverflow;
+}
+#endif
 int bk_count(Ctx *c, const BkDev &d);
 int bk_apply(Ctx *c, const BkDev &d);
 void bk_release(Ctx *c);

@@ -418,6 +418,7 @@ static int sim_cd(Ctx *c, bool in_step, bool keep_k2, CdOut *out) {
   bk.id2h = (const unsigned *)c->id2h.p;
   bk.active = (uint8_t *)c->s_active.p;
   bk.dropped = (uint8_t *)c->s_dropped.p;
+  bk.dropcnt = (int *)c->s_dropcnt.p;
   bk.gate = gate;
   bk.sticky = sticky;
   bk.demand = (unsigned long long *)((char *)c->sim_ctl.p + kSimCtlDemand);
@@ -713,6 +714,8 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
     c->hk_ok = false;  // (a detect may have been enqueued without its step's publication)
     return -1;
   }
+  // waypoint recovery of the pairs ResumeNav just dropped: on the pre-step state, before K4' reads ap.alt
+  if (c->sim_recovery && sp.cd && c->sim_fms && c->simp.resume_nav && fms_sim_recover(c)) return -1;
   PrepArgs pa{};
   if (sp.prep && step_prep_args(c, &pa)) return -1;
   if (step_launch(c, sp, cd, pa, step_hk_pub(c, cd.det))) return -1;
@@ -757,7 +760,7 @@ int bsa_sim_init(bsa_ctx *cc, int64_t n, const bsa_sim_state *s, const bsa_sim_p
   bsa::set_rank_rows(c);
   if (bsa::set_home_maps(c)) return -1;
   c->sim_noreso = c->sim_resooff = false;  // empty NORESO / RESOOFF lists
-  c->sim_atmos = c->sim_limits = c->sim_perf = c->sim_forces = c->sim_fms = false;
+  c->sim_atmos = c->sim_limits = c->sim_perf = c->sim_forces = c->sim_fms = c->sim_recovery = false;
   // every always-present array (kSimArrays); the all-gathered ones hold nranks
   // x rpr entries (in-place all-gather).  Zero unless a state field fills it:
   // asas.vs, asase / asasn, inactive, traf.ax, no ResumeNav drops
@@ -983,7 +986,7 @@ int bsa_sim_set_fms(bsa_ctx *cc, int64_t nrows, const double *route_rows, const 
   if (!c->sim_ready) return bsa::fail(c, "bsa_sim_set_fms before bsa_sim_init");
   BSA_HIP(c, hipSetDevice(c->device));
   if (!route_rows) {
-    c->sim_fms = false;
+    c->sim_fms = c->sim_recovery = false;
     return 0;
   }
   if (nrows < 0 || nrows > 0x7fffffff / 8) return bsa::fail(c, "bsa_sim_set_fms: bad route row count");
@@ -1020,6 +1023,25 @@ int bsa_sim_set_fms(bsa_ctx *cc, int64_t nrows, const double *route_rows, const 
   c->fms_ticks = 0;
   c->sim_fms = true;
   return 0;
+}
+
+int bsa_sim_set_recovery(bsa_ctx *cc, int on) {
+  Ctx *c = (Ctx *)cc;
+  if (!c) return -1;
+  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_set_recovery before bsa_sim_init");
+  if (on && !c->sim_fms) return bsa::fail(c, "waypoint recovery needs the FMS guidance (bsa_sim_set_fms)");
+  c->sim_recovery = on != 0;
+  return 0;
+}
+
+int bsa_sim_read_dropcount(bsa_ctx *cc, int32_t *count) {
+  Ctx *c = (Ctx *)cc;
+  if (!c || !count) return -1;
+  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_read_dropcount before bsa_sim_init");
+  BSA_HIP(c, hipSetDevice(c->device));
+  bsa::HomeBatch down(c, false, c->sim_rb, c->sim_re);
+  if (down.add(c->s_dropcnt.p, nullptr, count, 4)) return -1;
+  return down.run();
 }
 
 int bsa_sim_read_fms(bsa_ctx *cc, const bsa_fms_state *st, int32_t *iactwp, double *ap_trk, double *ap_tas,

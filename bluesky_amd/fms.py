@@ -129,11 +129,21 @@ def route_table(routes, swlnav=None):
     return rows, np.array(off, dtype=np.int32), np.array(cnt, dtype=np.int32), np.array(act, dtype=np.int32)
 
 
-def from_bluesky(traf):
+def from_bluesky(traf, unique_names=False):
     """``(rows, off, n, state)`` of a BlueSky ``Traffic`` object: its routes
     (``traf.ap.route``) as a table, and the state dict ``update`` takes --
     the traffic arrays, ``traf.actwp``, ``traf.ap`` and ``traf.swlnav / swvnav /
-    selspd / selvs / apvsdef / abco / belco / selalt``."""
+    selspd / selvs / apvsdef / abco / belco / selalt``.  ``unique_names``: raise
+    ValueError for a route that holds a waypoint name twice -- ``Route.direct``
+    looks its waypoint up by name and takes the first match, the device's
+    waypoint recovery (``recover``, ``ResidentSim.set_recovery``) goes to the
+    index ``findact`` found, and the two agree only for unique names."""
+    if unique_names:
+        for k, r in enumerate(traf.ap.route):
+            names = [str(x).upper().strip() for x in getattr(r, 'wpname', [])]
+            if len(set(names)) != len(names):
+                twice = sorted(set(x for x in names if names.count(x) > 1))
+                raise ValueError('route %d holds the waypoint name %s more than once' % (k, ', '.join(twice)))
     swlnav = np.asarray(traf.swlnav).astype(bool)
     rows, off, cnt, act = route_table(traf.ap.route, swlnav)
     w, ap = traf.actwp, traf.ap
@@ -214,3 +224,16 @@ def update(rows, off, n, state, ctx=None):
     call: dict of REALS, FLAGS, TARGETS and ``iactwp``; the inputs stay as they are."""
     ctx = ctx or _lib.default_context()
     return ctx.fms_update(rows, off, n, state)
+
+
+def recover(rows, off, n, state, count, ctx=None):
+    """Waypoint recovery on the device (bsa_fms_recover): what ``ASAS.ResumeNav``
+    does for an ownship whose resopair it drops (asas.py:459-465),
+    ``Route.findact`` + ``Route.direct``, applied ``count[k]`` times in sequence to
+    aircraft k (once per dropped pair).  ``state`` as ``update`` takes it (``ax``
+    and the targets other than ``ap_alt`` are not needed).  Returns the FMS state
+    after the call: dict of REALS, FLAGS, ``ap_alt`` and ``iactwp``; the inputs stay
+    as they are.  ``direct`` goes to the waypoint's index: the reference's lookup
+    by name for routes with unique names (``from_bluesky(unique_names=True)``)."""
+    ctx = ctx or _lib.default_context()
+    return ctx.fms_recover(rows, off, n, state, count)

@@ -136,6 +136,24 @@ class ResidentSim:
         None switches it off."""
         self.ctx.sim_set_fms(rows, off, n, state, simt, t0)
 
+    def set_recovery(self, on=True):
+        """Waypoint recovery after ResumeNav inside the step (bsa_sim_set_recovery):
+        with ``resume_nav`` on, every CD call sends each ownship whose resopair it
+        drops back to its route with ``Route.findact`` + ``Route.direct``
+        (asas.py:459-465), once per dropped pair, before the step's pilot reads
+        ``ap.alt``.  Needs ``set_fms`` (refused without it; ``set_fms(None)``
+        switches it off) and does nothing with ``resume_nav`` off.  Limit: the
+        reference's ``direct`` looks the waypoint up by NAME and takes the first
+        match; the device goes to the index ``findact`` found, which is the same
+        only for routes whose waypoint names are unique
+        (``fms.from_bluesky(traf, unique_names=True)`` checks that)."""
+        self.ctx.sim_set_recovery(on)
+
+    def read_dropcount(self):
+        """Resopairs ResumeNav dropped per ownship in the last CD call, this rank's
+        rows (bsa_sim_read_dropcount)."""
+        return self.ctx.sim_read_dropcount()
+
     def read_fms(self):
         """dict of the FMS state, ``iactwp``, the autopilot targets of this rank's
         rows, and ``simt``, ``t0``, ``ticks`` (bsa_sim_read_fms)."""

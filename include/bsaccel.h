@@ -513,6 +513,19 @@ int bsa_fms_update(bsa_ctx *ctx, int64_t n, int64_t nrows, const double *route_r
                    const double *tas, const double *gs, const double *trk, const double *ax, const double *bank,
                    const bsa_fms_state *st, double *ap_trk, double *ap_tas, double *ap_alt, double *ap_vs,
                    double *selalt);
+/* Waypoint recovery (asas.py:459-465): Route.findact (route.py:1043-1079) and
+ * Route.direct (route.py:635-688, with the whole of ComputeVNAV) applied
+ * count[k] >= 0 times in sequence to aircraft k -- once per resopair that
+ * ResumeNav dropped for it in one call.  Arrays and range checks as
+ * bsa_fms_update (traf.ax is not read).  In and out: iactwp, ap_alt and of *st
+ * actwp_lat / lon / nextaltco / xtoalt / spd / vs / turndist / flyby, dist2vs,
+ * selspd, swlnav; everything else is read only, and an aircraft with count 0
+ * or no route keeps every value.  direct goes to the waypoint's index, which
+ * is the reference's lookup by name for a route with unique names. */
+int bsa_fms_recover(bsa_ctx *ctx, int64_t n, int64_t nrows, const double *route_rows, const int32_t *rt_off,
+                    const int32_t *rt_n, int32_t *iactwp, const double *lat, const double *lon, const double *alt,
+                    const double *tas, const double *gs, const double *trk, const double *bank,
+                    const bsa_fms_state *st, double *ap_alt, const int32_t *count);
 /* The same inside the resident step, on the pre-step state (ap.update is the
  * first call of Traffic.update, traffic.py:395), in a launch of its own at the
  * start of every step, so that resident aircraft follow their routes with no
@@ -527,6 +540,16 @@ int bsa_fms_update(bsa_ctx *ctx, int64_t n, int64_t nrows, const double *route_r
  * several; bsa_sim_create is refused while it is on. */
 int bsa_sim_set_fms(bsa_ctx *ctx, int64_t nrows, const double *route_rows, const int32_t *rt_off, const int32_t *rt_n,
                     const int32_t *iactwp, const bsa_fms_state *st, double simt, double t0);
+/* Waypoint recovery inside the resident step (off by default): every CD step
+ * with resume_nav = 1 applies bsa_fms_recover's findact + direct to this rank's
+ * rows right after ResumeNav, once per resopair it dropped, on the pre-step
+ * state and before the step's Pilot.APorASAS reads ap.alt.  Refused while
+ * bsa_sim_set_fms is off; bsa_sim_set_fms(NULL) switches it off; inert with
+ * resume_nav = 0.  Exact through aborted and re-run batches. */
+int bsa_sim_set_recovery(bsa_ctx *ctx, int on);
+/* Resopairs ResumeNav dropped per ownship in the last CD call (resume_nav = 1),
+ * this rank's rows into a full-n host array: bsa_asas_out.dropped as a count. */
+int bsa_sim_read_dropcount(bsa_ctx *ctx, int32_t *count);
 /* This rank's rows (bsa_sim_row_ids) of the FMS state, iactwp and the
  * autopilot's targets into full-n host arrays, the clock and the number of
  * ticks since bsa_sim_set_fms; any pointer may be NULL. */
@@ -656,7 +679,9 @@ int bsa_sim_set_reso_lists(bsa_ctx *ctx, const uint8_t *noreso, const uint8_t *r
  * asas.trk / tas / vs / alt, asase / asasn (float32), asas.active, and
  * dropped = 1 for an ownship of which ResumeNav dropped a resopair in that call
  * (asas.py:454-468: the reference then starts waypoint recovery with
- * route.direct, which is autopilot state the host applies; resume_nav = 1). */
+ * route.findact + route.direct -- the ASAS drop-in applies it on the host from
+ * this flag, the resident step on the device with bsa_sim_set_recovery, once
+ * per dropped pair, bsa_sim_read_dropcount; resume_nav = 1). */
 typedef struct bsa_asas_out {
   double *trk, *tas, *vs, *alt;
   float *asase, *asasn;

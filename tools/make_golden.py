@@ -53,6 +53,13 @@ np.int = int
 np.float = float
 np.object = object
 np.str = str
+# ``from numpy import *`` (route.py:3): numpy 1.x kept max / min / abs / round out of
+# __all__, so the reference's Route.findact calls the builtins (max(iactwp, argmin(..))).
+# Process-wide: every reference module gets the star-import its numpy gave it.  The
+# other captures assert their oracle bitwise equal at capture, so a value that
+# this changed would stop the capture; none of their code paths calls these four
+# names on arrays with a numpy-only signature (axis=...).
+np.__all__ = [x for x in np.__all__ if x not in ('max', 'min', 'abs', 'round')]
 sys.dont_write_bytecode = True
 sys.path.insert(0, REF)
 sys.path.insert(0, REPO)
@@ -1014,6 +1021,427 @@ def run_fms_flight(name, n, seed, nsteps=2400, every=40, simdt=0.05):
           % (name, n, nsteps, nticks, len(sw_ac), ended.sum(), os.path.getsize(path)))
 
 
+def recover_case(n, seed):
+    """Inputs of the standalone waypoint recovery: fms_case's routes and FMS state,
+    every aircraft placed 100 m .. 25 km from a random waypoint of its own route
+    (before or after the active one) on a random track, counts 0 .. 3, and four
+    rows with bank 0 -- two of them tracking exactly at findact's waypoint."""
+    rng = np.random.default_rng(seed + 1000)
+    routes, st = fms_case(n, seed)
+    count = rng.choice([0, 1, 1, 2, 2, 3], n).astype(np.int32)
+    for k in range(n):
+        r = routes[k]
+        nwp = len(r['wplat'])
+        if nwp == 0:
+            continue
+        j = int(rng.integers(0, nwp))
+        dist = float(np.exp(rng.uniform(np.log(100.), np.log(25000.))))
+        side = float(rng.uniform(0., 360.))
+        lat = r['wplat'][j] + np.degrees(dist * np.cos(np.radians(side)) / 6371000.)
+        lon = r['wplon'][j] + np.degrees(dist * np.sin(np.radians(side)) / 6371000. / np.cos(np.radians(r['wplat'][j])))
+        st['lat'][k], st['lon'][k] = np.float32(lat), np.float32(lon)
+        st['trk'][k] = np.float32((side + 180. + float(rng.choice([0., 15., -60., 120., 180., -95.]))
+                                   + float(rng.uniform(-4., 4.))) % 360.)
+        st['bank'][k] = np.float32(np.radians(float(rng.choice([25., 25., 35.]))))
+    # bank 0: time_turn = inf, or NaN where the track points exactly at findact's waypoint
+    picked = [k for k in range(8, 257) if len(routes[k]['wplat']) >= 3 and routes[k]['iactwp'] == 0][:4]
+    assert len(picked) == 4
+    for q, k in enumerate(picked):
+        st['bank'][k] = 0.0
+        count[k] = max(count[k], 1)
+        if q < 2:
+            r = routes[k]
+            dy = np.array(r['wplat']) - st['lat'][k]
+            dx = (np.array(r['wplon']) - st['lon'][k]) * np.cos(np.deg2rad(st['lat'][k]))
+            iw = max(r['iactwp'], int(np.argmin(dx * dx + dy * dy)))
+            if iw + 1 < len(dy):
+                st['trk'][k] = np.degrees(np.arctan2(dx[iw], dy[iw]))
+    return routes, st, count
+
+
+def run_recover(name, n, seed):
+    """Route.findact + Route.direct of the reference's own Route / Autopilot /
+    ActiveWaypoint objects, applied count[k] times to aircraft k as ASAS.ResumeNav
+    does per dropped resopair (asas.py:459-465).  tests/recover_np.py is asserted
+    bitwise equal on every output and on wpdirfrom; every case the file must hold
+    is asserted present in the first 257 rows; the seed moves on until no
+    comparison lies within 1e-9 relative of equality."""
+    import bluesky as bs
+    from bluesky_amd import fms as bfms
+    from tests import fms_np, recover_np
+    for attempt in range(50):
+        routes, st, count = recover_case(n, seed + attempt)
+        ap, wp, traf = ref_autopilot(routes, st)
+        rows, off, cnt, act = bfms.route_table(ap.route, st['swlnav'])
+        with np.errstate(all='ignore'):
+            near = recover_np.near_threshold(st, rows, off, cnt, count)
+        if near.any():
+            continue
+        info = []
+        with np.errstate(all='ignore'):
+            mine = recover_np.recover(st, rows, off, cnt, count, info=info)
+        first = [r for r in info if r['i'] < 257]
+        by_row = {}
+        for r in first:
+            by_row.setdefault(r['i'], []).append(r)
+        h = slice(0, 257)
+        tgt = rows[np.minimum(off[h] + np.maximum(mine['iactwp'][h], 0), len(rows) - 1)]
+        went = (count[h] > 0) & (cnt[h] > 0)
+
+        def anyrec(f):
+            return any(f(r) for r in first)
+        cases = {
+            'no route': (cnt[h] == 0) & (count[h] > 0), 'one waypoint': (cnt[h] == 1) & (count[h] > 0),
+            'argmin < iactwp': anyrec(lambda r: 'argmin' in r and r['argmin'] < r['before']),
+            'argmin > iactwp': anyrec(lambda r: 'argmin' in r and r['argmin'] > r['before']),
+            'nearest is the last waypoint': anyrec(lambda r: r.get('turntest') == 0 and 'argmin' in r),
+            'turn test advances': anyrec(lambda r: r.get('turntest') == 2),
+            'turn test does not advance': anyrec(lambda r: r.get('turntest') == 1),
+            'bank 0: inf': anyrec(lambda r: st['bank'][r['i']] == 0 and np.isinf(r.get('time_turn', 0.))),
+            'bank 0 and delhdg 0: nan': anyrec(lambda r: st['bank'][r['i']] == 0 and np.isnan(r.get('time_turn', 0.))),
+            'count 2: the second advances again': any(len(v) >= 2 and v[1]['after'] > v[1]['before'] for v in by_row.values()),
+            'count 2: the second stays': any(len(v) >= 2 and v[1]['after'] == v[1]['before'] for v in by_row.values()),
+            'target is the last waypoint': went & (mine['iactwp'][h] == cnt[h] - 1) & (cnt[h] > 1),
+            'no speed': went & (tgt[:, 3] <= 0.), 'CAS': went & (tgt[:, 3] >= 2.0),
+            'Mach, wpalt < 0': went & (tgt[:, 3] > 0.) & (tgt[:, 3] < 2.0) & (tgt[:, 2] < 0.),
+            'Mach, wpalt >= 0': went & (tgt[:, 3] > 0.) & (tgt[:, 3] < 2.0) & (tgt[:, 2] >= 0.),
+            'speed with VNAV on': went & (tgt[:, 3] > 0.) & st['swvnav'][h],
+            'speed with VNAV off': went & (tgt[:, 3] > 0.) & ~st['swvnav'][h],
+            'fly-by': went & (tgt[:, 6] > 0.5), 'fly-over': went & (tgt[:, 6] < 0.5),
+            'LNAV switched on': went & ~st['swlnav'][h] & mine['swlnav'][h],
+        }
+        for code, what in ((1, 'toalt < 0'), (2, 'VNAV off'), (6, 'urgent descent'), (3, 'descent, not urgent'),
+                           (4, 'climb'), (5, 'level')):
+            cases['ComputeVNAV ' + what] = anyrec(lambda r, code=code: r['vnav'] == code)
+        missing = [w for w, m in cases.items() if not np.any(m)]
+        if missing:
+            print('recover seed %d: missing %s' % (seed + attempt, missing))
+            continue
+        break
+    else:
+        raise AssertionError('no seed holds every case clear of the thresholds')
+    for k, R in enumerate(ap.route):                  # wpdirfrom from the table against calcfp's own
+        for i in range(R.nwp):
+            assert np.array_equal(recover_np.wpdirfrom(rows[off[k]:off[k] + cnt[k]], i), R.wpdirfrom[i]), (k, i)
+    saved = getattr(bs, 'traf', None)
+    bs.traf = traf
+    try:
+        with np.errstate(all='ignore'):
+            for k in np.flatnonzero(count > 0):
+                for _ in range(count[k]):
+                    iw = ap.route[k].findact(k)
+                    if iw != -1:
+                        assert ap.route[k].direct(k, ap.route[k].wpname[iw]) is True
+    finally:
+        bs.traf = saved
+    ref = ref_fms_state(ap, wp, traf)
+    for k in recover_np.OUTPUTS + recover_np.UNTOUCHED:
+        if k in ref:
+            assert np.array_equal(np.asarray(mine[k], dtype=ref[k].dtype), ref[k], equal_nan=True), \
+                'helper != reference recovery %s' % k
+    out = {k: v for k, v in st.items()}
+    out.update(route_rows=rows, rt_off=off, rt_n=cnt, count=count, seed=seed + attempt,
+               numpy_version=np.array(np.__version__))
+    out.update({'out_' + k: ref[k] for k in recover_np.OUTPUTS})
+    path = os.path.join(OUT, 'fms_%s.npz' % name)
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) < 1000000, os.path.getsize(path)
+    changed = (ref['iactwp'] != st['iactwp']).sum()
+    print('fms_%-17s N=%5d seed %d applications %d, iactwp changed %d, %d bytes'
+          % (name, n, seed + attempt, len(info), changed, os.path.getsize(path)))
+
+
+def recover_flight_case(n, seed):
+    """n aircraft at 100-150 m/s on routes of 2-4 waypoints.  The first 18 are six
+    triples far from each other: an ownship and, crossing its track at 120 degrees
+    about 4 km ahead, two intruders 170 m above and below its level, one right
+    above the other -- ResumeNav's test is horizontal, so the ownship's two
+    resopairs are always decided alike and dropped together (a count of 2; the
+    intruders are more than the zone's height apart).  The rest fly at one of three levels
+    300 m apart across a box of 1 x 2 degrees.  With a 0.6 NM zone and 60 s of
+    lookahead, conflicts arise, are resolved and pass CPA within two minutes.
+    One aircraft in six starts with LNAV off."""
+    rng = np.random.default_rng(seed)
+    routes, st = fms_flight_case(n, seed)      # (for the key set and the constants; the geometry is replaced)
+    routes = []
+    for k in range(n):
+        tas = float(rng.uniform(100., 150.))
+        alt = 3000. + 300. * float(rng.integers(0, 3)) + float(rng.uniform(-40., 40.))
+        lat, lon = float(rng.uniform(51.5, 52.5)), float(rng.uniform(3.5, 5.5))
+        trk = float(np.degrees(np.arctan2((4.5 - lon) * np.cos(np.radians(52.25)), 52.25 - lat)) % 360.)
+        trk = (trk + float(rng.uniform(-40., 40.))) % 360.           # roughly across the middle of the box
+        if k < 18:
+            t, role = divmod(k, 3)
+            if role == 0:
+                base = float(rng.uniform(0., 360.))                  # the ownship's track
+                tas3 = float(rng.uniform(110., 140.))
+                alt3 = 3000. + float(rng.uniform(-40., 40.))
+            clat, clon = 53.5 + 0.4 * (t // 2), 4.0 + 0.8 * (t % 2)
+            trk = (base + (0., 120., 120.)[role]) % 360.
+            if role < 2:
+                d = 4000. + float(rng.uniform(-30., 30.))
+            lat = clat - np.degrees(d * np.cos(np.radians(trk)) / 6371000.)
+            lon = clon - np.degrees(d * np.sin(np.radians(trk)) / 6371000. / np.cos(np.radians(clat)))
+            tas, alt = tas3, alt3 + (0., 170., -170.)[role]
+        nwp = int(rng.choice([2, 3, 3, 4]))
+        la, lo, brg = lat, lon, trk
+        wplat, wplon = [], []
+        for i in range(nwp):
+            leg = float(rng.uniform(1500., 4000.) if i == 0 else rng.uniform(3000., 7000.))
+            turn = float(rng.choice([0., 15., -30., 50., -75.])) if i else 0.0
+            brg = (brg + turn + float(rng.uniform(-3., 3.))) % 360.
+            la = la + np.degrees(leg * np.cos(np.radians(brg)) / 6371000.)
+            lo = lo + np.degrees(leg * np.sin(np.radians(brg)) / 6371000. / np.cos(np.radians(la)))
+            wplat.append(float(np.float32(la)))
+            wplon.append(float(np.float32(lo)))
+        wpalt = [float(rng.choice([-999., -999., alt, alt - 250., alt + 200.])) for _ in range(nwp)]
+        wpspd = [float(rng.choice([-999., -999., 110., 140., 0.45])) for _ in range(nwp)]
+        routes.append(dict(wplat=wplat, wplon=wplon, wpalt=wpalt, wpspd=wpspd,
+                           wpflyby=[bool(i == 0 or rng.random() < 0.8) for i in range(nwp)], wptype=[0] * nwp,
+                           iactwp=0))
+        st['lat'][k], st['lon'][k], st['alt'][k], st['tas'][k], st['trk'][k] = lat, lon, alt, tas, trk
+        st['actwp_lat'][k], st['actwp_lon'][k] = wplat[0], wplon[0]
+        st['actwp_flyby'][k] = float(routes[-1]['wpflyby'][0])
+        st['actwp_next_qdr'][k] = float(refgeo.qdrdist(wplat[0], wplon[0], wplat[1], wplon[1])[0])
+        st['swvnav'][k] = rng.random() < 0.75
+        st['swlnav'][k] = rng.random() < 5. / 6.
+    st['gs'] = st['tas'].copy()
+    st['actwp_nextaltco'] = st['alt'].copy()
+    st['selspd'] = np.asarray(st['tas'] * 0.85)
+    st['ap_trk'], st['ap_tas'], st['ap_alt'] = st['trk'].copy(), st['tas'].copy(), st['alt'].copy()
+    st['selalt'] = st['alt'].copy()
+    st['swvnav'] &= st['swlnav']
+    return routes, st
+
+
+def detect_margins(st, rpz, hpz, tla, rel):
+    """Is a comparison of StateBasedCD.detect (StateBasedCD.py:46-99: dcpa2 < R2,
+    tinconf <= toutconf, toutconf > 0, tinconf < tlookahead, dist < R, |dalt| <
+    dh) or MVP's dabsH <= 10 (MVP.py:165) within ``rel`` relative of equality
+    for an off-diagonal pair?  Restated from oracle/statebased.detect_rows."""
+    n = len(st['lat'])
+    qdr, dist = ocd.qdrdist_rows(st['lat'], st['lon'], st['lat'], st['lon'], np.arange(n))
+    dist = np.array(dist) * nm
+    q = np.radians(np.array(qdr))
+    dx, dy = dist * np.sin(q), dist * np.cos(q)
+    u = (st['gs'] * np.sin(np.radians(st['trk']))).reshape((1, n))
+    v = (st['gs'] * np.cos(np.radians(st['trk']))).reshape((1, n))
+    du, dv = u - u.T, v - v.T
+    dv2 = du * du + dv * dv
+    dv2 = np.where(np.abs(dv2) < 1e-6, 1e-6, dv2)
+    vrel = np.sqrt(dv2)
+    tcpa = -(du * dx + dv * dy) / dv2
+    dcpa2 = dist * dist - tcpa * tcpa * dv2
+    R2 = rpz * rpz
+    hor = dcpa2 < R2
+    dt = np.sqrt(np.maximum(0., R2 - dcpa2)) / vrel
+    tinhor, touthor = np.where(hor, tcpa - dt, 1e8), np.where(hor, tcpa + dt, -1e8)
+    dalt = st['alt'].reshape((1, n)) - st['alt'].reshape((1, n)).T
+    dvs = st['vs'].reshape((1, n)) - st['vs'].reshape((1, n)).T
+    dvs = np.where(np.abs(dvs) < 1e-6, 1e-6, dvs)
+    hi, lo = (dalt + hpz) / -dvs, (dalt - hpz) / -dvs
+    tin, tout = np.maximum(np.minimum(hi, lo), tinhor), np.minimum(np.maximum(hi, lo), touthor)
+    off = ~np.eye(n, dtype=bool)
+
+    def near(a, b):
+        a, b = np.broadcast_arrays(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64))
+        return (np.abs(a - b) <= rel * np.maximum(np.abs(a), np.abs(b))) & ~((a == 0) & (b == 0)) & off
+    hit = near(dcpa2, R2) | (near(tin, tout) & hor) | (near(tin, tla) & hor) | near(dist, rpz) | near(np.abs(dalt), hpz)
+    hit |= near(dcpa2, 100.) & hor
+    return bool(hit.any())
+
+
+def resumenav_margins(pairs, st, R, Rm, rel):
+    """ResumeNav's comparisons (asas.py:437-450) for the given resopairs."""
+    for i, j in pairs:
+        d = 6371000. * np.array([np.radians(st['lon'][j] - st['lon'][i]) * np.cos(0.5 * np.radians(st['lat'][j] + st['lat'][i])),
+                                 np.radians(st['lat'][j] - st['lat'][i])])
+        vrel = np.array([st['gseast'][j] - st['gseast'][i], st['gsnorth'][j] - st['gsnorth'][i]])
+        dot, h = np.dot(d, vrel), np.linalg.norm(d)
+        scale = np.linalg.norm(vrel) * h
+        if abs(dot) <= rel * scale or abs(h - R) <= rel * R or abs(h - Rm) <= rel * Rm:
+            return True
+        if h < Rm * (1. + rel) and abs(abs(st['trk'][i] - st['trk'][j]) - 30.0) <= rel * 30.0:
+            return True
+    return False
+
+
+class Reseed(Exception):
+    pass
+
+
+def run_recover_flight(name, n, seed, nsteps=1920, every=40, simdt=0.0625, cd_every=64, rpz=0.6 * nm, tla=60.0):
+    """Closed loop of the reference with ASAS: real Autopilot.update -> real
+    ASAS.update (StateBasedCD.detect + MVP.resolve, resopairs bookkeeping,
+    ResumeNav with its route.findact / route.direct) -> Pilot.APorASAS ->
+    UpdateAirSpeed / UpdateGroundSpeed / UpdatePosition, no wind, acceleration()
+    = 0.5, simt accumulated as simulation.py:119 does (simdt = 1/16 s, exact in
+    binary, so ASAS.update's ``simt < tasas`` with dtasas = 4 s fires every 64th step exactly).
+    tests/fms_np.py + oracle/step.py + oracle/asas.py + tests/recover_np.py
+    (tests/recover_cases.recover_step) run alongside and are asserted bitwise
+    equal to the reference after every step -- FMS state, traffic, asas.trk /
+    tas / vs / alt and asas.active, so no aircraft's active depended on set
+    order in this run.  Stored: the initial state, the full state every
+    ``every`` steps, every recovery event (CD call, aircraft, count, iactwp
+    after, its step, whether ComputeVNAV took the urgent descent), every waypoint switch's step.  The seed moves on until no decision
+    (tick, detect, MVP's dabsH floor, ResumeNav, recovery) lies within 1e-6
+    relative of equality and the required events all occur."""
+    for attempt in range(3 if '--probe' in sys.argv else 40):
+        try:
+            out = _recover_flight(n, seed + attempt, nsteps, every, simdt, cd_every, rpz, tla)
+            break
+        except Reseed as e:
+            print('recover_flight seed %d: %s' % (seed + attempt, e))
+    else:
+        raise AssertionError('no seed meets the conditions')
+    path = os.path.join(OUT, 'fms_%s.npz' % name)
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) < 1000000, os.path.getsize(path)
+    print('fms_%-17s N=%5d seed %d steps %d CD calls %d recoveries %d (aircraft %d) switches %d, %d bytes'
+          % (name, n, out['seed'], nsteps, out['ncd'], len(out['ev_ac']), len(np.unique(out['ev_ac'])),
+             len(out['sw_ac']), os.path.getsize(path)))
+
+
+def _recover_flight(n, seed, nsteps, every, simdt, cd_every, rpz, tla):
+    import bluesky as bs
+    from bluesky.traffic.asas.asas import ASAS
+    from bluesky.traffic.pilot import Pilot
+    from bluesky_amd import fms as bfms
+    from oracle import asas as oasas
+    from tests import fms_np, recover_np, recover_cases
+    REL = 1e-6
+    routes, st = recover_flight_case(n, seed)
+    ap, wp, traf = ref_autopilot(routes, st)
+    rows, off, cnt, _ = bfms.route_table(ap.route, st['swlnav'])
+    ids = ['AC%03d' % k for k in range(n)]
+    idmap = {k: i for i, k in enumerate(ids)}
+    traf.id = ids
+    traf.id2idx = lambda x: [idmap.get(a, -1) for a in x]
+    traf.hdg, traf.vs = st['trk'].copy(), np.zeros(n)
+    traf.gseast = st['tas'] * np.sin(np.radians(st['trk']))
+    traf.gsnorth = st['tas'] * np.cos(np.radians(st['trk']))
+    traf.eps = np.full(n, 0.01)
+    traf.pilot = Pilot.__new__(Pilot)
+    mar = 1.05
+    asas = types.SimpleNamespace(
+        swasas=True, tasas=0.0, dtasas=cd_every * simdt, R=rpz, dh=HPZ, mar=mar, Rm=rpz * mar, dhm=HPZ * mar,
+        dtlookahead=tla, vmin=200.0 * nm / 3600., vmax=500.0 * nm / 3600., vsmin=-3000. / 60. * ft,
+        vsmax=3000. / 60. * ft, swresohoriz=True, swresospd=False, swresohdg=False, swresovert=False,
+        swprio=False, priocode='FF1', swnoreso=False, noresolst=[], swresooff=False, resoofflst=[],
+        asaseval=False, resopairs=set(), confpairs_unique=set(), lospairs_unique=set(), confpairs_all=[],
+        lospairs_all=[], active=np.zeros(n, dtype=bool), trk=st['trk'].copy(), tas=st['tas'].copy(),
+        alt=st['alt'].copy(), vs=np.zeros(n), asasn=np.zeros(n, dtype=np.float32), asase=np.zeros(n, dtype=np.float32))
+    asas.cd = types.SimpleNamespace(detect=StateBasedCD.detect)
+    asas.cr = types.SimpleNamespace(resolve=MVP.resolve)
+    asas.ResumeNav = lambda: ASAS.ResumeNav(asas)
+    traf.asas = asas
+    traf.wind = WindSim()
+    acc = np.full(n, 0.5)
+    traf.perf = types.SimpleNamespace(acceleration=lambda: acc)
+    me = {k: np.array(v) for k, v in st.items()}
+    me.update(hdg=st['trk'].copy(), vs=np.zeros(n), gseast=traf.gseast.copy(), gsnorth=traf.gsnorth.copy(),
+              eps=np.full(n, 0.01), accel=acc.copy(), asas_trk=st['trk'].copy(), asas_tas=st['tas'].copy(),
+              asas_vs=np.zeros(n), asas_alt=st['alt'].copy(), active=np.zeros(n, dtype=bool))
+    op = dict(simdt=simdt, rpz=rpz, hpz=HPZ, tla=tla, reso=True, wind=None,
+              mvp=omvp.params_from_settings(rpz, HPZ, tla, mar))
+    bk = oasas.Bookkeeping(n)
+    init = {k: np.array(v) for k, v in me.items()}
+    keys = FLIGHT_TRAFFIC + fms_np.OUTPUTS + ('asas_trk', 'asas_tas', 'asas_vs', 'asas_alt', 'active')
+    samples = {k: [] for k in keys + ('simt', 't0')}
+    sw_ac, sw_step, ev = [], [], []
+    lnav_on = 0
+    nticks = ncd = 0
+    simt, t0 = 0.0, -999.
+
+    def sample():
+        for k in keys:
+            samples[k].append(np.array(me[k]))
+        samples['simt'].append(simt)
+        samples['t0'].append(t0)
+
+    saved = getattr(bs, 'traf', None)
+    bs.traf = traf
+    try:
+        with np.errstate(all='ignore'):
+            for step in range(nsteps):
+                if step % every == 0:
+                    sample()
+                tick = fms_np.ticks(simt, t0)
+                do_cd = step % cd_every == 0
+                if tick:
+                    if fms_np.near_threshold(me, rows, off, cnt, rel=REL).any():
+                        raise Reseed('step %d: a tick decision within 1e-6' % step)
+                    t0 = simt
+                    nticks += 1
+                if do_cd:
+                    if detect_margins(me, rpz, HPZ, tla, REL):
+                        raise Reseed('step %d: a detect decision within 1e-6' % step)
+                before = me['iactwp'].copy()
+                ticked = fms_np.update(me, rows, off, cnt, tick=tick)
+                new, count = recover_cases.recover_step(me, rows, off, cnt, op, bk, tick, do_cd)
+                if do_cd:
+                    if resumenav_margins(list(bk.last_keep), me, rpz, rpz * mar, REL):
+                        raise Reseed('step %d: a ResumeNav decision within 1e-6' % step)
+                    after_tick = dict(me, **{k: ticked[k] for k in fms_np.OUTPUTS})
+                    if recover_np.near_threshold(after_tick, rows, off, cnt, count, rel=REL).any():
+                        raise Reseed('step %d: a recovery decision within 1e-6' % step)
+                    info = []
+                    recover_np.recover(after_tick, rows, off, cnt, count, info=info)
+                    for k in np.flatnonzero(count):
+                        urgent = any(r['i'] == k and r['vnav'] == 6 for r in info)     # legdist < dist2vs: ap.alt dialled in
+                        ev.append((ncd, int(k), int(count[k]), int(new['iactwp'][k]), step, int(ticked['iactwp'][k]),
+                                   int(urgent)))
+                        lnav_on += int(new['swlnav'][k] and not ticked['swlnav'][k])
+                    ncd += 1
+                me = new
+                for k in np.flatnonzero(me['iactwp'] != before):
+                    sw_ac.append(k)
+                    sw_step.append(step)
+                # ---- the reference
+                tasas = asas.tasas
+                ap.update(simt)
+                assert ap.t0 == t0
+                ASAS.update(asas, simt)
+                assert (asas.tasas != tasas) == do_cd, 'step %d: ASAS.update and cd_every disagree' % step
+                Pilot.APorASAS(traf.pilot)
+                RefTraffic.UpdateAirSpeed(traf, simdt, simt)
+                RefTraffic.UpdateGroundSpeed(traf, simdt)
+                RefTraffic.UpdatePosition(traf, simdt)
+                simt += simdt
+                if do_cd and bk.ambiguous(bk.last_keep):       # (an aircraft with a kept AND a dropped pair)
+                    raise Reseed('step %d: an asas.active depends on the set order (aircraft %s)' % (step, bk.ambiguous(bk.last_keep)))
+                assert np.array_equal(me['active'], asas.active), 'step %d: oracle active != reference' % step
+                ref = ref_fms_state(ap, wp, traf)
+                for k in fms_np.OUTPUTS:
+                    assert np.array_equal(np.asarray(me[k], dtype=ref[k].dtype), ref[k], equal_nan=True), \
+                        'step %d: helper != reference %s' % (step, k)
+                for k in FLIGHT_TRAFFIC + ('gs', 'trk', 'gseast', 'gsnorth'):
+                    assert np.array_equal(me[k], getattr(traf, k)), 'step %d: oracle step != reference %s' % (step, k)
+                for k in ('trk', 'tas', 'vs', 'alt'):
+                    assert np.array_equal(me['asas_' + k], getattr(asas, k), equal_nan=True), \
+                        'step %d: oracle asas.%s != reference' % (step, k)
+                assert sorted((idmap[a], idmap[b]) for a, b in asas.resopairs) == sorted(bk.resopairs)
+            sample()
+    finally:
+        bs.traf = saved
+    ev = np.array(ev, dtype=np.int32).reshape(-1, 7)
+    conds = {'at least 8 aircraft recover': len(np.unique(ev[:, 1])) >= 8, 'a count >= 2': (ev[:, 2] >= 2).any(),
+             'a recovery changes iactwp': (ev[:, 3] != ev[:, 5]).any(), 'a recovery leaves iactwp': (ev[:, 3] == ev[:, 5]).any(),
+             'a recovery switches LNAV on': lnav_on > 0,
+             'a recovery takes the urgent descent and writes ap.alt': (ev[:, 6] > 0).any()}
+    missing = [w for w, ok in conds.items() if not ok]
+    if missing:
+        raise Reseed('missing: %s' % missing)
+    out = {'init_' + k: v for k, v in init.items()}
+    out.update({'s_' + k: np.array(v) for k, v in samples.items()})
+    out.update(route_rows=rows, rt_off=off, rt_n=cnt, sw_ac=np.array(sw_ac, dtype=np.int32),
+               sw_step=np.array(sw_step, dtype=np.int32), ev_cd=ev[:, 0], ev_ac=ev[:, 1], ev_count=ev[:, 2],
+               ev_iactwp=ev[:, 3], ev_step=ev[:, 4], ev_urgent=ev[:, 6], nticks=nticks, ncd=ncd, simdt=simdt, every=every, nsteps=nsteps,
+               cd_every=cd_every, rpz=rpz, hpz=HPZ, tla=tla, mar=mar, margin_rel=REL, seed=seed,
+               numpy_version=np.array(np.__version__))
+    return out
+
+
 def run_asas(name, traf, ncalls=4, dt=20.0):
     """Reference ASAS.update (asas.py:473-504) incl. ResumeNav on a stand-in
     bs.traf; state advanced along straight tracks between CD calls."""
@@ -1156,6 +1584,13 @@ def main():
     if '--forces-only' in sys.argv:
         run_forces('forces3000', 3000, 75)
         return
+    if '--recover-only' in sys.argv:
+        run_recover('recover2000', 2000, 81)
+        run_recover_flight('recover_flight', 48, 83)
+        return
+    if '--recover-flight-only' in sys.argv:
+        run_recover_flight('recover_flight', 48, 83)
+        return
     if '--fms-only' in sys.argv:
         run_fms('update2000', 2000, 77)
         run_fms_flight('flight64', 64, 79)
@@ -1191,6 +1626,8 @@ def main():
     run_forces('forces3000', 3000, 75)
     run_fms('update2000', 2000, 77)
     run_fms_flight('flight64', 64, 79)
+    run_recover('recover2000', 2000, 81)
+    run_recover_flight('recover_flight', 48, 83)
     for case in geo_cases():
         run_geo(*case)
 

@@ -6,10 +6,13 @@ steps (one host synchronisation at its end, no stage events) after SETTLE
 untimed ones (the device at steady clocks, as bench.py's --settle).  Collectives
 (box all-gather, halo send / recv, gate all-reduce) are excluded: they need
 the 8-GPU node.  Prints every rank's ms per step and the slowest.
-Usage: python tools/probe_step.py [WORKLOAD [R [STEPS [RANK [SETTLE]]]]] [--perf | --forces] [--fms]  (RANK:
+Usage: python tools/probe_step.py [WORKLOAD [R [STEPS [RANK [SETTLE]]]]] [--perf | --forces] [--fms]
+[--resume-nav] [--recover]  (RANK:
 that rank of R only, -1 all; SETTLE default 200; --perf: OpenAP phase / envelope in the step,
 --forces: also its drag / thrust / fuel-flow launch; --fms: Autopilot.update in the
-step, every aircraft on a generated 4-waypoint route)"""
+step, every aircraft on a generated 4-waypoint route; --resume-nav: ASAS.update's
+bookkeeping and ResumeNav in the CD step; --recover: waypoint recovery after ResumeNav, DESIGN.md 3.23
+-- implies --fms and --resume-nav, its cost is --recover against --fms --resume-nav)"""
 import json
 import os
 import sys
@@ -40,7 +43,10 @@ def main():
     forces = '--forces' in sys.argv
     with_perf = forces or '--perf' in sys.argv
     with_fms = '--fms' in sys.argv           # Autopilot.update in the step (bsa_sim_set_fms): its cost is --fms against none
-    sys.argv = [a for a in sys.argv if a not in ('--forces', '--perf', '--fms')]
+    recover = '--recover' in sys.argv        # waypoint recovery after ResumeNav (bsa_sim_set_recovery)
+    with_fms = with_fms or recover
+    resume_nav = recover or '--resume-nav' in sys.argv
+    sys.argv = [a for a in sys.argv if a not in ('--forces', '--perf', '--fms', '--recover', '--resume-nav')]
     name = sys.argv[1] if len(sys.argv) > 1 else 'global1m'
     R = int(sys.argv[2]) if len(sys.argv) > 2 else 8
     steps = int(sys.argv[3]) if len(sys.argv) > 3 else 40
@@ -50,16 +56,18 @@ def main():
     ctx = _lib.Context(0)
     ctx.set_timing_sample(0)
     init = resident.initial_state(t)
-    sim = resident.ResidentSim(init, resident.params(cd_every=1), ctx=ctx)
+    sim = resident.ResidentSim(init, resident.params(cd_every=1, resume_nav=resume_nav), ctx=ctx)
     if with_fms:
         from bluesky_amd import fms
         sim.set_fms(*fms.synthetic_routes(init, seed=5, nwp=4))
+        if recover:
+            sim.set_recovery()
     if with_perf:
         table, tidx, ftable, mass = openap_tables(t.ntraf)
         sim.set_perf(table, tidx)
         if forces:
             sim.set_forces(ftable, mass)
-    out = dict(perf=with_perf, forces=forces, fms=with_fms)
+    out = dict(perf=with_perf, forces=forces, fms=with_fms, resume_nav=resume_nav, recover=recover)
     for ranks in sorted({1, R}) if only is None else [R]:
         per = []
         for r in range(ranks) if only is None else [only]:
@@ -81,6 +89,8 @@ def main():
         f = sim.read_fms()
         out['fms_ticks'] = f['ticks']
         out['fms_switched'] = int((f['iactwp'] > 0).sum())
+    if resume_nav:
+        out['dropped_pairs_last_cd'] = int(sim.read_dropcount().sum())
     ctx.sim_probe_rank(0, 1)
     print(json.dumps(dict(workload=name, steps=steps, settle=settle, **out)), flush=True)
 
