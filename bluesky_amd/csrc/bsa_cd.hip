@@ -2681,7 +2681,7 @@ struct DetectPlan {
   // BSA_STAGE1_T0 environment variable selects t = 0 for A/B measurements
   int mid;
   // the resident step's K4' already wrote this detect's column records and
-  // boxes from the state it computed (Ctx::sim_prepped; any detect consumes or
+  // boxes from the state it computed (Ctx::prep; any detect consumes or
   // invalidates them: it rewrites the same buffers)
   bool prepped;
   // tile-pair list reuse: the resident step's detects of a
@@ -2811,25 +2811,24 @@ struct DetectRun {
 // HK (see DetectPlan::hk): the host's rebuild decision for this detect
 static int decide_hk(Ctx *c, DetectPlan &p, bool host_decides) {
   if (p.tpr && host_decides && c->hk_on && !c->simp.resume_nav && c->hk_hdev) {
-    if (c->hk_cool > 0) {  // after a stale abort: device-decided for a while
-      c->hk_cool--;
-      c->hk_ok = false;
+    if (c->hk.cool > 0) {  // after a stale abort: device-decided for a while
+      c->hk.cool--;
+      c->hk.drop();
     } else {
       p.hk = true;
-      p.hm = c->hk_m++;
+      p.hm = c->hk.m++;
       const int64_t hm = p.hm;
       const int nf = (c->simp.winddim == 0 && c->sim_gs_derivable) ? 6 : 8;  // (halo_mid's field count)
-      bool build = !p.tvalid || !c->hk_ok || (c->halo_mode == 1 && nf != c->halo_fields);
+      bool build = !p.tvalid || !c->hk.matches() || (c->halo_mode == 1 && nf != c->halo_fields);
       // a build one or two detects ago: its snapshot is fresh enough (the
       // prediction covers two steps of drift); else the prediction made from
       // the records of detect hm - 2, published by that step's K4'
-      if (!build && !c->hk_built[(hm + 3) & 3] && !c->hk_built[(hm + 2) & 3]) {
+      if (!build && !c->hk.built_lately(hm)) {
         unsigned long long v = 0;
         if (hk_wait(c, hm - 2, &v)) return -1;
         build = (v & 3ull) != 0;  // predicted, or that step aborted (its retry rebuilds anyway)
       }
-      c->hk_built[hm & 3] = build;
-      c->hk_ok = true;
+      c->hk.keep(hm, build);
       p.hkeep = !build;
       (build ? c->hk_builds : c->hk_keeps)++;
       if (detect_env().hk_trace)
@@ -2837,7 +2836,7 @@ static int decide_hk(Ctx *c, DetectPlan &p, bool host_decides) {
                 build ? "build" : "keep", p.tvalid ? 1 : 0, (long long)c->sim_steps);
     }
   } else if (p.tpr) {
-    c->hk_ok = false;  // a device-decided detect: the build history is no longer the host's
+    c->hk.drop();  // a device-decided detect: the build history is no longer the host's
   }
   return 0;
 }
@@ -2847,9 +2846,8 @@ static int decide_launch(Ctx *c, DetectPlan &p) {
   const DetectEnv &env = detect_env();
   const int64_t n = p.n, nrows = p.nrows;
   p.kf = p.mid ? 0.5 * (p.tla > 0.0 ? p.tla : 0.0) / 6371000.0 : 0.0;
-  p.resort = !p.home && (!c->perm_valid || c->perm_n != n || c->perm_rb != p.rb || c->perm_re != p.re ||
-                         c->perm_shared != p.shared || c->perm_distinct != p.distinct || c->perm_f != p.kf ||
-                         (p.flags & BSA_FLAG_RESORT) || c->perm_age >= (p.reuse ? kResortEveryReuse : kResortEvery));
+  p.resort = !p.home && (!c->order.matches({n, p.rb, p.re, p.shared, p.distinct, p.kf}) || (p.flags & BSA_FLAG_RESORT) ||
+                         c->order.age >= (p.reuse ? kResortEveryReuse : kResortEvery));
   if (c->cand_cap == 0)
     // 8 x max(128 k, 4 rows) candidates in all (at 100k rows ~12x the demand), whole shards
     c->cand_cap = (unsigned long long)kCandShards *
@@ -2862,14 +2860,9 @@ static int decide_launch(Ctx *c, DetectPlan &p) {
         !ensure(c, c->reuse_use, (size_t)((n + 63) / 64) * 8, "reuse budget use") ||
         !ensure(c, c->reuse_ctl, 16, "reuse control"))
       return -1;
-    const double key[4] = {p.rpz, p.hpz, p.tla, (double)p.flags};
-    p.rvalid = c->reuse_valid && !p.resort && c->reuse_n == n && c->reuse_cap == p.cap &&
-               c->reuse_candp == c->cand.p && memcmp(key, c->reuse_key, sizeof key) == 0;
-    c->reuse_valid = true;  // optimistic: an overflow invalidates it (detect_finish / sim retry)
-    memcpy(c->reuse_key, key, sizeof key);
-    c->reuse_n = n;
-    c->reuse_cap = p.cap;
-    c->reuse_candp = c->cand.p;
+    const KeptCands::Key key{p.rpz, p.hpz, p.tla, (double)p.flags, n, p.cap, c->cand.p};
+    p.rvalid = !p.resort && c->cands.matches(key);
+    c->cands.keep(key);  // optimistic: an overflow invalidates it (detect_finish / sim retry)
   }
   p.na = p.halo ? p.a1 - p.a0 : 0;
   p.ovl = p.halo && p.hkeep && !p.noprune && p.na > 0 && (c->ov_mode == 2 || (c->ov_mode == 1 && c->halo_mode == 1));
@@ -2961,30 +2954,26 @@ static int detect_decide(Ctx *c, const DetectRequest &q, DetectPlan *plan) {
   p.shared = p.home || (!p.distinct && rb == 0 && re == n);
   p.roff = p.home ? rb : 0;
   p.reuse = c->reuse_on && p.shared && rb == 0 && re == n && !p.noprune && !p.kwik && n > 0 && !p.halo;
-  if (!p.reuse) c->reuse_valid = false;
+  if (!p.reuse) c->cands.drop();
   p.mid = stage1_mid(flags, p.reuse, p.kwik);
-  p.prepped = c->sim_prepped && p.home && !p.halo && !p.reuse && rb == 0 && re == n && flags == 0 &&
-              c->sim_prep_key[0] == rpz && c->sim_prep_key[1] == hpz && c->sim_prep_key[2] == tla &&
-              c->sim_prep_key[3] == (double)p.mid && c->sim_prep_n == n;
-  c->sim_prepped = false;
+  p.prepped = p.home && !p.halo && !p.reuse && rb == 0 && re == n && flags == 0 &&
+              c->prep.matches({rpz, hpz, tla, (double)p.mid, n});
+  c->prep.drop();
   if (!nonfin_word(c)) return -1;
   p.nf_epoch = p.prepped ? c->nf_prep_epoch : (q.nf_epoch ? q.nf_epoch : ++c->nf_counter);
   p.tp_list = p.halo && !env.tp_halo_all && !env.tp_super;
   p.tpr = env.tpr && c->tpr_on && p.home && !p.reuse && flags == 0 && !env.tp_super &&
           ((!p.halo && p.prepped && (n + kTile - 1) / kTile <= kTPDirectMax) || p.tp_list);
-  const double tkey[6] = {rpz, hpz, tla, (double)p.mid, (double)rb, (double)re};
-  p.tvalid = p.tpr && c->tpr_valid && c->tpr_n == n && memcmp(tkey, c->tpr_key, sizeof tkey) == 0;
+  const KeptTilePairs::Key tkey{rpz, hpz, tla, (double)p.mid, (double)rb, (double)re, n};
+  p.tvalid = p.tpr && c->tiles.matches(tkey);
   if (decide_hk(c, p, q.host_decides)) return -1;
-  if (p.tpr) {  // (every rank, also one without rows: the kept state stays collective)
-    c->tpr_valid = true;  // (an aborted step or any state change clears it)
-    memcpy(c->tpr_key, tkey, sizeof tkey);
-    c->tpr_n = n;
-  } else {
-    c->tpr_valid = false;
-  }
+  if (p.tpr)  // (every rank, also one without rows: the kept state stays collective)
+    c->tiles.keep(tkey);
+  else
+    c->tiles.drop();
   p.nozero = ((p.prepped && (n + kTile - 1) / kTile <= kTPDirectMax) || (p.hkeep && p.halo)) && !env.k0z &&
-             !env.tp_super && c->k2_bucket > 0 && c->zeroed_rows == nrows;
-  c->zeroed_rows = -1;
+             !env.tp_super && c->k2_bucket > 0 && c->zero.matches({nrows});
+  c->zero.drop();
   if (p.nozero) {
     std::swap(c->counters, c->counters2);
     std::swap(c->workq, c->workq2);
@@ -3052,16 +3041,9 @@ static int detect_order(DetectRun &R) {
     if (!p.shared && spatial_order(c, (int)p.nrows, (int)p.rb, R.own.lat, R.own.lon, R.intr.trk, R.intr.gs, p.kf,
                                    c->key_r, c->idx_r, c->key_r2, c->perm_r))
       return -1;
-    c->perm_f = p.kf;
-    c->perm_valid = true;
-    c->perm_n = p.n;
-    c->perm_rb = p.rb;
-    c->perm_re = p.re;
-    c->perm_shared = p.shared;
-    c->perm_distinct = p.distinct;
-    c->perm_age = 0;
+    c->order.keep({p.n, p.rb, p.re, p.shared, p.distinct, p.kf});
   }
-  if (!p.home) c->perm_age++;
+  if (!p.home) c->order.age++;
   R.perm_c = (const unsigned *)(p.home ? c->h2id.p : c->perm_c.p);
   R.perm_r = p.home ? nullptr : (const unsigned *)(p.shared ? c->perm_c.p : c->perm_r.p);
   return 0;
@@ -3440,7 +3422,7 @@ static int detect_rank(DetectRun &R) {
     } else {
       rank_launch(c, rl, false, K24Args{});
     }
-    c->zeroed_rows = p.nrows;
+    c->zero.keep({p.nrows});
   } else {
     hipLaunchKernelGGL(k_rank, dim3(256 * 4), dim3(256), 0, c->stream, nrows, R.dcnt, cap,
                        (const unsigned *)c->rowoff.p, (const unsigned long long *)c->ckey2.p,
@@ -3465,7 +3447,7 @@ int detect_enqueue(Ctx *c, const DetectRequest &q, DetectResult *res) {
   DetectRun R{c, p, q, *res, soa(c->own), soa(p.distinct ? c->intr : c->own), (Counters *)c->counters.p,
               NfArgs{(unsigned long long *)c->nonfin.p, p.nf_epoch, nullptr}};
   if (R.mark(0)) {
-    c->reuse_valid = false;  // (detect_decide's optimistic mark: nothing of this detect is enqueued)
+    invalidate(c, Change::DetectNotEnqueued);  // (detect_decide's optimistic mark: nothing of this detect is enqueued)
     return -1;
   }
   if (p.empty) return detect_empty(R);
@@ -3523,7 +3505,7 @@ int detect_finish(Ctx *c, bool *retry) {
     c->have_pairs = true;
     return 0;
   }
-  c->zeroed_rows = -1;  // (a retry zeroes everything again; so does any host-side recovery)
+  invalidate(c, Change::DetectDone);  // (a retry zeroes everything again; so does any host-side recovery)
   // every cause of a retry is fixed before the one retry (not one per retry)
   if (h.fuse_ovf) {  // a wave flushed more blocks than the fused K1b records: K1b as its own launch
     c->fuse_skip = true;
@@ -3539,7 +3521,7 @@ int detect_finish(Ctx *c, bool *retry) {
   const unsigned long long total = h.cand;  // (the list is dense: K2 summed the shard counts)
   if (worst > c->cand_cap / kCandShards) {
     c->cand_cap = (unsigned long long)kCandShards * (worst + worst / 4 + 1024);
-    c->reuse_valid = false;
+    invalidate(c, Change::DetectOverflow);
     *retry = true;
   }
   if (*retry) return 0;

@@ -541,9 +541,8 @@ int bsa_set_state(bsa_ctx *c, int64_t n, const double *lat, const double *lon, c
   if (n < 0) return bsa::fail(c, "negative n");
   BSA_HIP(c, hipSetDevice(c->device));
   c->sim_ready = false;  // a new state replaces any resident sim
-  c->sim_prepped = false;
-  c->tpr_valid = false;  // (tile-pair list / halo plan reuse: rebuilt at the next detect)
   c->home = false;       // ... and its home order: aircraft-index order again
+  bsa::invalidate(c, bsa::Change::NewState);
   const double *src[6] = {lat, lon, trk, gs, alt, vs};
   if (n == 0) {
     c->n = 0;
@@ -704,7 +703,7 @@ int bsa_set_candidate_reuse(bsa_ctx *c, int on, double sigma_h, double sigma_v) 
     c->reuse_sh = sigma_h;
     c->reuse_sv = sigma_v;
   }
-  c->reuse_valid = false;  // the next detect builds
+  bsa::invalidate(c, bsa::Change::SetCandReuse);  // the next detect builds
   return 0;
 }
 
@@ -726,7 +725,7 @@ int bsa_set_tile_reuse(bsa_ctx *c, int on, double sigma_h, double sigma_v) {
     c->tpr_ds = (float)(sigma_h / 6.3e6 / 20);  // reach: |V| T/2 changes with the speed, slowly
     c->tpr_dv = (float)sigma_v;
   }
-  c->tpr_valid = false;  // the next detect builds
+  bsa::invalidate(c, bsa::Change::SetTileReuse);  // the next detect builds
   return 0;
 }
 
@@ -748,7 +747,7 @@ int bsa_set_hk(bsa_ctx *c, int on, double f) {
   if (!(f > 0.0 && f <= 4.0)) return bsa::fail(c, "HK prediction fraction must be in (0, 4]");
   c->hk_on = on != 0;
   c->hk_f = (float)f;
-  c->hk_ok = false;  // (the next host-decided detect builds)
+  bsa::invalidate(c, bsa::Change::SetHk);  // (the next host-decided detect builds)
   return 0;
 }
 
@@ -771,7 +770,7 @@ int bsa_hk_stats(bsa_ctx *c, int64_t *out6) {
   out6[1] = c->hk_builds;
   out6[2] = c->hk_waits;
   out6[3] = c->hk_stale;
-  out6[4] = c->hk_cool;
+  out6[4] = c->hk.cool;
   out6[5] = c->hk_on ? 1 : 0;
   return 0;
 }
@@ -792,9 +791,10 @@ int bsa_reuse_stats(bsa_ctx *c, int64_t *builds, int64_t *detects) {
 int bsa_reuse_budget_use(bsa_ctx *c, double *use2) {
   if (!c || !use2) return -1;
   use2[0] = use2[1] = 0.0;
-  if (!c->reuse_use.p || c->reuse_n <= 0) return 0;
+  const int64_t n = c->cands.key.n;  // (of the last detect that could reuse)
+  if (!c->reuse_use.p || n <= 0) return 0;
   BSA_HIP(c, hipSetDevice(c->device));
-  std::vector<float> u((size_t)((c->reuse_n + 63) / 64) * 2);
+  std::vector<float> u((size_t)((n + 63) / 64) * 2);
   BSA_HIP(c, hipMemcpyAsync(u.data(), c->reuse_use.p, u.size() * 4, hipMemcpyDeviceToHost, c->stream));
   BSA_HIP(c, hipStreamSynchronize(c->stream));
   for (size_t k = 0; k < u.size(); k += 2) {

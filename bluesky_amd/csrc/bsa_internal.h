@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/bsaccel.h"
+#include "bsa_kept.h"
 
 namespace bsa {
 
@@ -216,16 +217,17 @@ struct Ctx {
   bool scan_ready = false;
   unsigned long long scan_tickets = 0;
   unsigned scan_epoch = 0;
-  // reusable spatial order (any permutation gives identical results)
-  bool perm_valid = false, perm_shared = false, perm_distinct = false;
-  double perm_f = 0.0;  // midpoint factor the spatial order was computed with (k_keys)
-  int64_t perm_n = 0, perm_rb = 0, perm_re = 0, perm_age = 0;
+  // what a detect keeps from earlier calls (bsa_kept.h); dropped through invalidate() below
+  KeptOrder order;
+  KeptCands cands;
+  KeptTilePairs tiles;
+  KeptPrep prep;
+  KeptZero zero;
+  HkHistory hk;
 
   // detect buffers
   DevBuf counters;           // Counters
-  DevBuf counters2, workq2;  // the next detect's counters / dequeue words (double-buffered, zeroed by K2)
-  int64_t zeroed_rows = -1;  // rows of the last detect whose K2 zeroed counters2 / workq2 / rowcnt, or -1
-                             // (state: the next detect of that many rows skips its K0z)
+  DevBuf counters2, workq2;  // the next detect's counters / dequeue words (double-buffered, zeroed by K2: Ctx::zero)
   DevBuf cand;               // uint2 (i, j)
   DevBuf cflag;              // per candidate: bit0 conflict, bit1 LoS
   unsigned long long cand_cap = 0;
@@ -249,11 +251,6 @@ struct Ctx {
   // candidate-list reuse across detects (shared own == intruder only)
   bool reuse_on = false;
   double reuse_sh = 800.0, reuse_sv = 60.0;   // horizontal budget, default / max vertical budget [m]
-  bool reuse_valid = false;                   // a list + snapshot exist for the current perm / params
-  double reuse_key[4] = {0, 0, 0, 0};         // rpz hpz tla flags of the list
-  int64_t reuse_n = -1;
-  unsigned long long reuse_cap = 0;
-  void *reuse_candp = nullptr;
   DevBuf snap_build, snap_cur, reuse_ctl, reuse_use;  // ctl: [0] build flag, [1] detects since build
 
   // tile-pair list reuse: K0d's item list, built on boxes
@@ -262,9 +259,6 @@ struct Ctx {
   // the build (checked by whoever prepares the records: K4' / K0b); a record
   // outside raises tpr_ctl[0] and the next detect rebuilds on the device
   bool tpr_on = true;                  // resident home-order detects of all rows (BSA_TPR=0: off)
-  bool tpr_valid = false;              // a list + snapshot exist for tpr_key / tpr_n
-  double tpr_key[6] = {0, 0, 0, 0, 0, 0};  // rpz hpz tla mid row_begin row_end of the list
-  int64_t tpr_n = -1;
   float tpr_dx = 3.2e-4f, tpr_ds = 1.6e-5f, tpr_dv = 300.f;  // ~2 km, ~100 m of reach, 300 m
   DevBuf tpr_snap;                     // PFRec per aircraft at the last build
   DevBuf tpr_ctl;                      // u64: [0] build flag, [1] near items, [2] far items, [3] builds, [4] detects,
@@ -280,13 +274,8 @@ struct Ctx {
   // checks every record against the full budgets: one outside aborts the step
   // (Counters::tpr_stale) and it re-runs with a build.
   bool hk_on = true;                   // BSA_HK=0: the device decides (round-5 behaviour)
-  // (state: the decisions of one host-decided detect are read by the next ones)
-  bool hk_ok = false;                  // the build history below is this sim's
-  bool hk_built[4] = {false, false, false, false};  // build decisions of detects m & 3
-  int64_t hk_m = 0;                    // index of the next host-decided detect
-  int64_t hk_cool = 0;                 // after a stale abort: device-decided detects left
-  int64_t hk_cool_len = 32;            // ... the next such stretch (doubles per stale abort, <= 4096):
-                                       // a workload whose lists go stale often ends up device-decided
+  int64_t hk_cool_len = 32;            // device-decided detects after the next stale abort (doubles per
+                                       // abort, <= 4096): a workload whose lists go stale often ends up device-decided
   int64_t hk_keeps = 0, hk_builds = 0, hk_stale = 0, hk_waits = 0;  // statistics
   float hk_f = 0.75f;                  // prediction fraction of the budgets (BSA_HK_F)
   unsigned long long *hk_host = nullptr, *hk_hdev = nullptr;  // pinned ring (host / device view)
@@ -365,10 +354,6 @@ struct Ctx {
   int64_t sim_last_conf = 0, sim_last_los = 0;
   bool sim_gathered = true;  // replicas consistent with every rank's rows
   bool sim_gs_derivable = false;  // gseast / gsnorth of every row follow from gs / trk (K4' without wind ran)
-  // (state: written by a step's K4', consumed or invalidated by whichever detect comes next)
-  bool sim_prepped = false;       // the last K4' wrote the next detect's column records / boxes (one rank)
-  double sim_prep_key[4] = {0, 0, 0, 0};  // ... for rpz, hpz, tla, stage-1 mode
-  int64_t sim_prep_n = 0;
   DevBuf s_tas, s_hdg, s_gse, s_gsn;                        // traffic state besides own[]
   DevBuf s_aptrk, s_aptas, s_apalt, s_apvs, s_selalt, s_bank, s_eps, s_accel;  // frozen
   DevBuf s_atrk, s_atas, s_avs, s_aalt, s_ase, s_asn, s_active;  // ASAS (full n)
@@ -472,6 +457,17 @@ struct Ctx {
   bool feed_pending = false;
   int64_t feed_steps = 0, feed_rb = 0, feed_re = 0;
 };
+
+// the one place outside a detect that drops kept detect state (kDrops, bsa_kept.h)
+inline void invalidate(Ctx *c, Change what) {
+  const Drops &d = kDrops[(int)what];
+  if (d.order) c->order.drop();
+  if (d.cands) c->cands.drop();
+  if (d.tiles) c->tiles.drop();
+  if (d.prep) c->prep.drop();
+  if (d.zero) c->zero.drop();
+  if (d.hk) c->hk.drop();
+}
 
 // ---- the resident sim's per-aircraft arrays, described once
 struct BufRef {  // a DevBuf of the context: c->*m, or c->own[own] when m is NULL

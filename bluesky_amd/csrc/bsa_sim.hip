@@ -43,7 +43,7 @@ namespace bsa {
 // (bsa_prep.h: k_prep_cols' expressions, bitwise its records), and each wave
 // reduces its group's sub-group and group boxes; that detect then skips its
 // K0b launch, its K0z unites the group boxes into tile boxes
-// (detect_enqueue, Ctx::sim_prepped).
+// (detect_enqueue, Ctx::prep).
 template <bool FUSE, bool PREP>
 __global__ __launch_bounds__(256) void k_sim_pilot_kin(int rb, int re, double simdt, int winddim, double vwn,
                                                          double vwe, WindField wf, SimDev d, MvpIn mv,
@@ -502,11 +502,10 @@ static int batch_end(Ctx *c, unsigned long long ctl[5]) {
 // same step; each rank grows only what overflowed on IT (another rank's
 // overflow re-runs the step here with unchanged buffers) and all ranks re-run it
 static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long long *ctl) {
-  c->reuse_valid = false;  // the re-run rebuilds any reused candidate list
-  c->tpr_valid = false;    // ... and any kept tile-pair list / halo plan (every rank aborted alike)
-  c->zeroed_rows = -1;     // ... and zeroes every per-detect buffer (an aborted K2 wrote no inconf / tcpamax)
-  c->sim_prepped = false;  // (an aborted K4' prepared nothing)
-  c->hk_ok = false;        // (HK: the decisions of the aborted steps never took effect)
+  // the re-run rebuilds the candidate list and the tile-pair list / halo plan (every rank aborted alike) and zeroes
+  // every per-detect buffer (an aborted K2 wrote no inconf / tcpamax); an aborted K4' prepared nothing, and the HK
+  // decisions of the aborted steps never took effect
+  invalidate(c, Change::BatchAborted);
   const int64_t done = (int64_t)ctl[1];
   c->sim_steps = base.steps + done;
   c->sim_gs_derivable = done > 0 ? c->simp.winddim == 0 : base.gs_derivable;  // K4' ran for the completed steps only
@@ -544,7 +543,7 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long lon
   const double kdem = agree[0];
   if (agree[1] > 0.0) {  // an HK-kept list no longer covered some rank's records: device-decided for a while
     c->hk_stale++;
-    c->hk_cool = c->hk_cool_len;
+    c->hk.cool = c->hk_cool_len;
     c->hk_cool_len = std::min<int64_t>(2 * c->hk_cool_len, 4096);
   }
   if (kdem > 0)
@@ -622,8 +621,8 @@ static int step_fms(Ctx *c, const StepPlan &sp) {
 
 // K4' as the preparer of the next detect's column records and boxes
 // (StepPlan::prep): their buffers, a fresh non-finite epoch and, with a kept
-// tile-pair list, its budgets.  After the step's CD call: Ctx::tpr_valid and
-// Ctx::hk_m are that detect's
+// tile-pair list, its budgets.  After the step's CD call: Ctx::tiles and
+// Ctx::hk.m are that detect's
 static int step_prep_args(Ctx *c, PrepArgs *out) {
   PrepArgs &pa = *out;
   const int64_t n = c->n;
@@ -640,14 +639,14 @@ static int step_prep_args(Ctx *c, PrepArgs *out) {
   if (!nonfin_word(c)) return -1;
   pa.nf = (unsigned long long *)c->nonfin.p;  // the next detect's records: a fresh epoch
   pa.nfe = c->nf_prep_epoch = ++c->nf_counter;
-  if (c->tpr_valid && c->tpr_snap.p && c->tpr_ctl.p && c->tpr_n == n) {  // the kept list's budgets
+  if (c->tiles.kept_for(n) && c->tpr_snap.p && c->tpr_ctl.p) {  // the kept list's budgets
     pa.snap = (const PFRec *)c->tpr_snap.p;
     pa.tpr_ctl = (unsigned long long *)c->tpr_ctl.p;
     pa.dx = c->tpr_dx;
     pa.ds = c->tpr_ds;
     pa.dv = c->tpr_dv;
-    // HK: the prediction word of the next detect (index hk_m, if it is host-decided)
-    pa.pred = (unsigned long long *)c->tpr_ctl.p + 6 + (c->hk_m & 1);
+    // HK: the prediction word of the next detect (index hk.m, if it is host-decided)
+    pa.pred = (unsigned long long *)c->tpr_ctl.p + 6 + (c->hk.m & 1);
     pa.pf = c->hk_f;
   }
   return 0;
@@ -711,7 +710,7 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
   if (c->sim_fms && step_fms(c, sp)) return -1;
   CdOut cd;
   if (sp.cd && sim_cd(c, true, sp.k24, &cd)) {
-    c->hk_ok = false;  // (a detect may have been enqueued without its step's publication)
+    invalidate(c, Change::StepNotEnqueued);  // (a detect may have been enqueued without its step's publication)
     return -1;
   }
   // waypoint recovery of the pairs ResumeNav just dropped: on the pre-step state, before K4' reads ap.alt
@@ -719,14 +718,10 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
   PrepArgs pa{};
   if (sp.prep && step_prep_args(c, &pa)) return -1;
   if (step_launch(c, sp, cd, pa, step_hk_pub(c, cd.det))) return -1;
-  c->sim_prepped = sp.prep;
-  if (sp.prep) {
-    c->sim_prep_key[0] = pa.rpz;
-    c->sim_prep_key[1] = pa.hpz;
-    c->sim_prep_key[2] = pa.tla;
-    c->sim_prep_key[3] = (double)pa.mid;
-    c->sim_prep_n = c->n;
-  }
+  if (sp.prep)
+    c->prep.keep({pa.rpz, pa.hpz, pa.tla, (double)pa.mid, c->n});
+  else
+    c->prep.drop();
   // every rank's rows now hold K4's gs / trk / gse / gsn: gse / gsn follow
   // from gs / trk bitwise only without wind (with wind gs / trk derive from
   // them, traffic.py:463-466, not the other way round)
@@ -791,10 +786,8 @@ int bsa_sim_init(bsa_ctx *cc, int64_t n, const bsa_sim_state *s, const bsa_sim_p
   if (bsa::halo_init_caps(c)) return -1;
   c->sim_steps = c->sim_cd_calls = c->sim_last_conf = c->sim_last_los = 0;
   c->sim_gathered = true;
-  c->sim_prepped = false;
-  c->tpr_valid = false;  // (tile-pair list / halo plan reuse: rebuilt at the next detect)
-  c->hk_ok = false;      // (HK: no build history yet)
-  c->hk_cool = 0;
+  bsa::invalidate(c, bsa::Change::NewSim);
+  c->hk.cool = 0;
   c->hk_cool_len = 32;
   if (!c->hk_host) {     // HK: the pinned ring the steps' K4' publish their predictions into
     void *hp = nullptr;
@@ -1092,8 +1085,7 @@ int bsa_sim_update(bsa_ctx *cc, const bsa_sim_state *s) {
     if (hb.add(bsa::buf_at(c, f.buf).p, src, nullptr, 8)) return -1;
   }
   if (hb.run()) return -1;
-  c->sim_prepped = false;  // prepared records are of the old state
-  c->tpr_valid = false;  // (tile-pair list / halo plan reuse: rebuilt at the next detect)
+  bsa::invalidate(c, any_cd ? bsa::Change::EditedCdInput : bsa::Change::EditedArrays);
   if (any_cd) {
     // every rank passed the same full arrays: the replicas are consistent only
     // if ALL replicated arrays were passed; otherwise the next all-gather
@@ -1101,7 +1093,6 @@ int bsa_sim_update(bsa_ctx *cc, const bsa_sim_state *s) {
     // own rows are right either way)
     if (all_rep) c->sim_gathered = true;
     c->sim_gs_derivable = false;  // (gseast / gsnorth may be the host's)
-    c->reuse_valid = false;       // a state jump rebuilds any reused candidate list
   }
   return 0;
 }
@@ -1179,8 +1170,7 @@ int bsa_sim_probe_rank(bsa_ctx *cc, int rank, int nranks) {
   if (nranks < 1 || rank < 0 || rank >= nranks) return bsa::fail(c, "bad probe rank %d of %d", rank, nranks);
   BSA_HIP(c, hipSetDevice(c->device));
   const int64_t n = c->n;
-  c->tpr_valid = false;  // (its tile-pair list / plan are rebuilt for the new rows)
-  c->sim_prepped = false;
+  bsa::invalidate(c, bsa::Change::OtherRows);
   if (nranks == 1) {  // back to the whole sim
     c->sim_rb = 0;
     c->sim_re = n;
@@ -1327,8 +1317,7 @@ int bsa_sim_set_params(bsa_ctx *cc, const bsa_sim_params *p) {
   if (bsa::check_params(c, p)) return -1;
   if (p->resume_nav && !c->simp.resume_nav) c->bk_ready = false;  // the bookkeeping starts empty
   c->simp = *p;
-  c->sim_prepped = false;
-  c->tpr_valid = false;  // (tile-pair list / halo plan reuse: rebuilt at the next detect)
+  bsa::invalidate(c, bsa::Change::SimParams);
   return 0;
 }
 

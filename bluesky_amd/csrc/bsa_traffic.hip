@@ -324,11 +324,8 @@ static void set_n(Ctx *c, int64_t n) {
   c->last_rb = c->sim_rb;
   c->last_re = c->sim_re;
   c->have_pairs = false;
-  c->perm_valid = false;   // the spatial order is over the old indices
-  c->reuse_valid = false;  // so is any reusable candidate list
   c->sim_gathered = true;  // every replica is complete after the change
-  c->sim_prepped = false;  // prepared records are of the old traffic
-  c->tpr_valid = false;  // (tile-pair list / halo plan reuse: rebuilt at the next detect)
+  invalidate(c, Change::Traffic);  // the spatial order, the lists and the prepared records are over the old indices
 }
 
 // length of each full-n per-aircraft buffer for n aircraft (several ranks: the

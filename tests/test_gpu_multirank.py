@@ -906,3 +906,41 @@ def test_reads_on_a_rank_without_rows(ctx):
     for _, _, st in res:
         for k, v in exp_st.items():
             assert np.array_equal(st[k], v), k
+
+
+def test_sharded_update_keeps_the_kept_state_collective(ctx):
+    """bsa_sim_update of lat on every rank of two, then 6 steps:
+    bitwise the one-rank run given the same update, and both ranks take the same
+    build decisions -- host-known builds and keeps, list builds on the device --
+    since what the update drops, it drops on every rank."""
+    from tests.util import same
+    t = synth.box(5000, 150.0, seed=131)
+    init = resident.initial_state(t)
+    p = resident.params(swresohoriz=False)
+
+    def run(sim, c, pairs):
+        out = []
+        sim.step(4)
+        out.append((sim.read(), pairs(sim)))
+        lat = out[0][0]['lat'].copy()
+        lat[7] += 40.0 / 111.19   # one aircraft 40 km further north
+        sim.update(lat=lat)
+        h0, t0 = c.hk_stats(), c.tile_reuse_stats()
+        for k in (2, 4):
+            sim.step(k)
+            out.append((sim.read(), pairs(sim)))
+        h, t = c.hk_stats(), c.tile_reuse_stats()
+        return out, (h['builds'] - h0['builds'], h['keeps'] - h0['keeps'], t['builds'] - t0['builds'])
+
+    def one(sim):
+        st = sim.stats()
+        return ctx.fetch_pairs(st['n_conf'], st['n_los'])
+
+    exp, _ = run(resident.ResidentSim(init, p, ctx=ctx), ctx, one)
+    assert sum(len(x[1]['ci']) for x in exp) > 0
+    res = run_ranks(2, lambda r, c, g: run(resident.ResidentSim(init, p, ctx=c, rank=r, world=2, group=g), c,
+                                           lambda sim: sim.gather_pairs(root=0)))
+    same(res[0][0], exp)                                      # (the pair lists are gathered on rank 0)
+    same([(s, e[1]) for (s, _), e in zip(res[1][0], exp)], exp)
+    print('builds / keeps / list builds per rank', res[0][1], res[1][1])
+    assert res[0][1] == res[1][1] and res[0][1][2] >= 1, (res[0][1], res[1][1])

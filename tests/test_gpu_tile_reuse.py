@@ -6,10 +6,10 @@ detects rebuild the coarse cull -- every pair is still tested and evaluated --
 so the sim with it is BITWISE the sim without it: state arrays and pair lists
 after every step, with MVP manoeuvres, large steps that force rebuilds, budgets
 tiny enough to rebuild every step, and cd_every > 1."""
-import numpy as np
 import pytest
 
 from bluesky_amd import _lib, resident, synth
+from tests.util import same
 
 pytestmark = pytest.mark.gpu
 
@@ -29,15 +29,6 @@ def run(ctx, init, p, steps, tile):
         return out, ctx.tile_reuse_stats()
     finally:
         ctx.set_tile_reuse(True)
-
-
-def same(a, b):
-    for k, (sa, pa) in enumerate(a):
-        sb, pb = b[k]
-        for f in sa:
-            assert np.array_equal(sa[f], sb[f]), 'step %d %s' % (k, f)
-        for f in ('ci', 'cj', 'qdr', 'dist', 'tcpa', 'tinconf', 'li', 'lj', 'inconf', 'tcpamax'):
-            assert np.array_equal(pa[f], pb[f]), 'step %d %s' % (k, f)
 
 
 @pytest.mark.parametrize('simdt, tile, cd_every', [

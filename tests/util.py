@@ -62,6 +62,16 @@ def assert_detect_equal(got, exp, rpz, tla, rows=None):
         assert ok, '%s: %s' % (k, msg)
 
 
+def same(a, b):
+    """Two runs' [(state read, fetched pairs)] per step or batch: bitwise equal."""
+    for k, (sa, pa) in enumerate(a):
+        sb, pb = b[k]
+        for f in sa:
+            assert np.array_equal(sa[f], sb[f]), 'step %d %s' % (k, f)
+        for f in ('ci', 'cj', 'qdr', 'dist', 'tcpa', 'tinconf', 'li', 'lj', 'inconf', 'tcpamax'):
+            assert np.array_equal(pa[f], pb[f]), 'step %d %s' % (k, f)
+
+
 TRACE_PAIRS = {'ci': 'ci', 'cj': 'ci', 'qdr': 'ci', 'dist': 'ci', 'tcpa': 'ci', 'tLOS': 'ci',
                'li': 'li', 'lj': 'li', 'reso_i': 'reso_i', 'reso_j': 'reso_i',
                'reso_in_i': 'reso_in_i', 'reso_in_j': 'reso_in_i'}
