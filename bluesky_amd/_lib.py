@@ -198,6 +198,8 @@ SIGNATURES.update({
     'bsa_sim_probe_rank': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
     'bsa_set_exact_fusion': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
     'bsa_exact_fusion_stats': (ctypes.c_int, [_vp, _c_i64p]),
+    'bsa_set_symmetric_sweep': (ctypes.c_int, [_vp, ctypes.c_int]),
+    'bsa_symmetric_sweep_stats': (ctypes.c_int, [_vp, _c_i64p]),
     'bsa_sim_comm_stats': (ctypes.c_int, [_vp, _c_i64p]),
     'bsa_sim_set_atmos': (ctypes.c_int, [_vp, ctypes.c_int]),
     'bsa_sim_read_atmos': (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp]),
@@ -983,6 +985,17 @@ class Context:
         v = np.zeros(3, np.int64)
         self.check(self.lib.bsa_exact_fusion_stats(self.h, ptr(v, _c_i64p)), 'bsa_exact_fusion_stats')
         return dict(fused=int(v[0]), retries=int(v[1]), last=bool(v[2]))
+
+    def set_symmetric_sweep(self, on=True):
+        """bsa_set_symmetric_sweep: each unordered tile pair swept once, refined both ways
+        (default on where rows and columns are the same aircraft; results never depend on it)."""
+        self.check(self.lib.bsa_set_symmetric_sweep(self.h, int(bool(on))), 'bsa_set_symmetric_sweep')
+
+    def symmetric_sweep_stats(self):
+        """bsa_symmetric_sweep_stats: detects planned symmetric, whether the last one was."""
+        v = np.zeros(2, np.int64)
+        self.check(self.lib.bsa_symmetric_sweep_stats(self.h, ptr(v, _c_i64p)), 'bsa_symmetric_sweep_stats')
+        return dict(detects=int(v[0]), last=bool(v[1]))
 
     def sim_probe_rank(self, rank, nranks):
         """bsa_sim_probe_rank (measurement aid): the one-rank sim's steps play rank `rank` of `nranks`."""

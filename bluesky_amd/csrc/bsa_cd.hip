@@ -475,6 +475,7 @@ constexpr int kTPThreads = 1024;
 constexpr int kSuper = 8;  // tiles per super tile (each side)
 constexpr int kSlicesPerTile = kTile / kGroup;  // 64-row slices (work items) per row tile
 static_assert(kSlicesPerTile == 8, "8 slices per tile (item bit layout, slice boxes = group boxes)");
+constexpr unsigned kItemMirror = 1u << 31;  // item word 0: row tile (22 bits) | slice << 22 | mirrored
 // present (halo mode, nullable): column tiles whose data this rank holds --
 // its own [p0, p1) and the halo tiles it received.  A kept pair with any
 // other column tile means the halo plan disagreed with this test (it cannot:
@@ -485,8 +486,11 @@ static_assert(kSlicesPerTile == 8, "8 slices per tile (item bit layout, slice bo
 // 64-row slices whose boxes may reach the column tile (sg: the slice boxes)
 __device__ __forceinline__ unsigned tp_classify(const TileBox &a, const TileBox *sg, const TileBox &b, int rt, int ct,
                                                 int nrows, int noprune, const uint8_t *__restrict__ present, int p0,
-                                                int p1, Counters *__restrict__ cnt, bool &kn, bool &kf) {
+                                                int p1, Counters *__restrict__ cnt, bool &kn, bool &kf, int sym) {
   unsigned sm = 0;
+  // symmetric sweep (DetectPlan::sym; row tile t is column tile t): the pair
+  // (ct, rt) covers this one, its items refined in both orientations
+  if (sym && ct < rt) return 0u;
   if ((noprune || boxes_may_interact(a, b)) && present && !(ct >= p0 && ct < p1) && !present[ct]) {
     cnt->halo_miss = 1;
   } else if (noprune || boxes_may_interact(a, b)) {
@@ -509,7 +513,7 @@ template <int NT>
 __device__ __forceinline__ void tp_emit(bool kn, bool kf, unsigned sm, int rt, int ct, uint2 *__restrict__ out,
                                         unsigned long long cap, Counters *__restrict__ cnt,
                                         unsigned long long *__restrict__ icnt, unsigned (*wpre)[NT / 64],
-                                        unsigned long long *bbase) {
+                                        unsigned long long *bbase, int sym) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const unsigned ni = (unsigned)__popc(sm);
   const unsigned xn = wave_incl_scan(kn ? ni : 0u), xf = wave_incl_scan(kf ? ni : 0u);
@@ -535,10 +539,13 @@ __device__ __forceinline__ void tp_emit(bool kn, bool kf, unsigned sm, int rt, i
     }
   }
   __syncthreads();
-  if (ni) {  // item = (row tile | slice << 22, column tile); near ones from the front
+  if (ni) {  // item = (row tile | slice << 22 | mirrored << 31, column tile); near ones from the front
+    // mirrored (kItemMirror): an off-diagonal pair of a symmetric list -- the
+    // sweep refines its stage-1 survivors as (row, column) and as (column, row)
+    const unsigned mir = sym && rt != ct ? kItemMirror : 0u;
     unsigned long long k = (kn ? bbase[0] + wpre[0][w] + xn : bbase[1] + wpre[1][w] + xf) - ni;
     for (unsigned m = sm; m; m &= m - 1u, ++k) {
-      const uint2 v = make_uint2((unsigned)rt | (unsigned)__builtin_ctz(m) << 22, (unsigned)ct);
+      const uint2 v = make_uint2((unsigned)rt | (unsigned)__builtin_ctz(m) << 22 | mir, (unsigned)ct);
       out[kn ? k : cap - 1 - k] = v;
     }
   }
@@ -551,7 +558,8 @@ __global__ __launch_bounds__(kTPThreads) void k_tilepairs(int nrt, int nct, int 
                                                           Counters *__restrict__ cnt,
                                                           unsigned long long *__restrict__ icnt,
                                                           const unsigned *__restrict__ build,
-                                                          const uint8_t *__restrict__ present, int p0, int p1) {
+                                                          const uint8_t *__restrict__ present, int p0, int p1,
+                                                          int sym) {
   if (build && !build[0]) return;
   __shared__ TileBox srt[kSuper];                    // this super row's tile boxes
   __shared__ TileBox sgb[kSuper * kSlicesPerTile];   // ... and its 64-row slices' boxes
@@ -575,7 +583,7 @@ __global__ __launch_bounds__(kTPThreads) void k_tilepairs(int nrt, int nct, int 
       const int ct0 = sc * kSuper, nc = min(kSuper, nct - ct0);
       TileBox u = cb[ct0];
       for (int j = 1; j < nc; ++j) u = box_union(u, cb[ct0 + j]);
-      kp = noprune || boxes_may_interact(sr, u);
+      kp = (noprune || boxes_may_interact(sr, u)) && !(sym && ct0 + nc <= rt0);  // (sym: no tile pair with rt <= ct in it)
     }
     const unsigned x = wave_incl_scan(kp ? 1u : 0u);
     if (lane == 63) wpre[2][w] = x;
@@ -600,9 +608,9 @@ __global__ __launch_bounds__(kTPThreads) void k_tilepairs(int nrt, int nct, int 
         rt = rt0 + i;
         ct = (int)sc2 * kSuper + (int)(r % kSuper);
         if (i < nr && ct < nct) sm = tp_classify(srt[i], &sgb[i * kSlicesPerTile], cb[ct], rt, ct, nrows, noprune,
-                                                 present, p0, p1, cnt, kn, kf);
+                                                 present, p0, p1, cnt, kn, kf, sym);
       }
-      tp_emit<kTPThreads>(kn, kf, sm, rt, ct, out, cap, cnt, icnt, wpre, bbase);
+      tp_emit<kTPThreads>(kn, kf, sm, rt, ct, out, cap, cnt, icnt, wpre, bbase, sym);
       __syncthreads();  // wpre / bbase are rewritten by the next round
     }
   }
@@ -643,7 +651,7 @@ __global__ __launch_bounds__(kTPDirectThreads) __attribute__((amdgpu_waves_per_e
     const TileBox *__restrict__ cb, int noprune, uint2 *__restrict__ out, unsigned long long cap,
     Counters *__restrict__ cnt, unsigned long long *__restrict__ icnt, const unsigned *__restrict__ build,
     const uint8_t *__restrict__ present, int p0, int p1, const TileBox *__restrict__ gbc,
-    const int *__restrict__ hl, int nhl, const unsigned *__restrict__ nhl_dev, TprArgs tp) {
+    const int *__restrict__ hl, int nhl, const unsigned *__restrict__ nhl_dev, TprArgs tp, int sym) {
   if (tp.myflag && blockIdx.x == 0 && threadIdx.x == 0) *tp.myflag = 0u;  // (k_halo_plan's blocks all read it)
   if (build && !build[0]) return;
   // tile-pair list reuse: no build this detect -> the kept
@@ -704,8 +712,8 @@ __global__ __launch_bounds__(kTPDirectThreads) __attribute__((amdgpu_waves_per_e
     }
     bool kn = false, kf = false;
     unsigned sm = 0;
-    if (ct >= 0) sm = tp_classify(a, sgb, bc, rt, ct, nrows, noprune, present, p0, p1, cnt, kn, kf);
-    tp_emit<kTPDirectThreads>(kn, kf, sm, rt, ct, out, cap, cnt, icnt, wpre, bbase);
+    if (ct >= 0) sm = tp_classify(a, sgb, bc, rt, ct, nrows, noprune, present, p0, p1, cnt, kn, kf, sym);
+    tp_emit<kTPDirectThreads>(kn, kf, sm, rt, ct, out, cap, cnt, icnt, wpre, bbase, sym);
     __syncthreads();  // wpre / bbase are rewritten by the next round
   }
   if (hl) {  // the tiles this rank does not hold: none may be reachable (no appends, no barriers;
@@ -1087,6 +1095,7 @@ __global__ __launch_bounds__(PF_BLOCK) PF_OCC void k_prefilter(
   __shared__ float4 clh[PF_WAVES][32];      //                      lo lo' hi hi' (stage 1)
   __shared__ float4 csx[PF_WAVES][64];      // staged columns:      x y z -       (refine)
   __shared__ float4 csv[PF_WAVES][64];      //                      u v vs alt    (refine)
+  __shared__ float2 cbs[PF_WAVES][64];      //                      1/rho rho     (mirrored refine basis)
   __shared__ unsigned cix[PF_WAVES][64];    //                      sorted column index
   __shared__ float4 rsv[PF_WAVES][PF_WROWS];  // staged rows:       u v vs alt    (refine)
   __shared__ float4 rsp[PF_WAVES][PF_WROWS];  //                    x y z sigma   (refine)
@@ -1272,7 +1281,11 @@ __global__ __launch_bounds__(PF_BLOCK) PF_OCC void k_prefilter(
     if (skip) break;
     // the item: (row tile | slice << 22, column tile)
     const uint2 rc = make_uint2(it.x & 0x3fffffu, it.y);
-    const unsigned slice = it.x >> 22;
+    const unsigned slice = (it.x >> 22) & (unsigned)(kSlicesPerTile - 1);
+    // a mirrored item (K0d, a symmetric list: rows = columns, row tile < column
+    // tile): the tile pair (column tile, row tile) is not listed -- the drain
+    // refines every stage-1 survivor in both orientations (wave-uniform)
+    const bool mir = !NOPRUNE && __builtin_amdgcn_readfirstlane(it.x & kItemMirror) != 0u;
     // column sub-groups of this tile that may interact with the wave's row box:
     // the stage-1 test on box gaps (one sub-group box per lane), evaluated as
     // the item starts
@@ -1391,12 +1404,20 @@ __global__ __launch_bounds__(PF_BLOCK) PF_OCC void k_prefilter(
         const unsigned k = b0 + lane;
         const unsigned e = q1[k < n1 ? k : b0];
         const unsigned rl = e >> 6, cl = e & 63u;
-        bool keep = false;
+        bool keep = false, keepm = false;
         unsigned gi = 0, gj = 0;
         if (k < n1) {
           gi = (unsigned)rbase + rl;
           gj = sci[cl];
           keep = NOPRUNE ? true : pf_refine(rsp[w][rl], rv[rl], rbs[w][rl], sx[cl], sv[cl], prm);
+          // mirrored item: the same routine with the roles swapped -- the
+          // column as the row (its basis staged with the batch), the row as
+          // the column; the staged row and column values have one layout
+          if (mir) {
+            const float4 cp = sx[cl];
+            const float2 cb = cbs[w][cl];
+            keepm = pf_refine(cp, sv[cl], make_float4(cp.x * cb.x, cp.y * cb.x, cb.y, 0.f), rsp[w][rl], rv[rl], prm);
+          }
           // an aircraft against itself (rows = the columns [diag, diag + nrows)):
           // never a pair (StateBasedCD.py's +1e9 I sentinel), ~40 % of the
           // refine survivors at the 100k box otherwise
@@ -1412,6 +1433,10 @@ __global__ __launch_bounds__(PF_BLOCK) PF_OCC void k_prefilter(
         const unsigned long long mk = __ballot(keep);
         if (mk) {
           emit(mk, keep, make_uint2(gi, gj));
+        }
+        if (mir) {  // candidate (row gj, column gi): rows are the columns from 0 on (diag == 0)
+          const unsigned long long mm = __ballot(keepm);
+          if (mm) emit(mm, keepm, make_uint2(gj, gi));
         }
       }
       n1 = 0;
@@ -1480,6 +1505,12 @@ __global__ __launch_bounds__(PF_BLOCK) PF_OCC void k_prefilter(
         sx[lane] = make_float4(np.x, np.y, np.z, nx.pad);
         sv[lane] = make_float4(nv.flags ? qnan : nv.u * kInvRS, nv.v * kInvRS, nv.vs, nx.alt);
         sci[lane] = (unsigned)jn;
+        if (mir) {  // the column's refine basis as a row's (rbs above: x/rho, y/rho, rho), once per
+                    // staged column; 1/rho and rho only -- 8 B per column keep the workgroup within 40 KB
+          const float rho2 = np.x * np.x + np.y * np.y;
+          const float irho = __builtin_amdgcn_rsqf(rho2);
+          cbs[w][lane] = make_float2(irho, rho2 * irho);
+        }
         colmask = __ballot(jn >= 0);
       }
 #ifdef BSA_PF_STAMPS
@@ -2486,6 +2517,7 @@ const DetectEnv &detect_env() {
                      num("BSA_FUSE_EXACT", -1),
                      num("BSA_OV_GRID_A", 2),
                      num("BSA_K1B_GRID", 0),
+                     num("BSA_PF_SYM", 1) != 0,
                      num("BSA_K24", 1) != 0,
                      (k4b == 64 || k4b == 128 || k4b == 256) ? k4b : 64,
                      num("BSA_SIM_PREP", 1) != 0};
@@ -2680,6 +2712,13 @@ struct DetectPlan {
   // the reuse budgets (whose drift checks assume t = 0 points); the
   // BSA_STAGE1_T0 environment variable selects t = 0 for A/B measurements
   int mid;
+  // symmetric sweep: rows and columns are the same records
+  // and every row is detected, so K0d lists each unordered tile pair once
+  // (row tile <= column tile) and the sweep refines the stage-1 survivors of
+  // an off-diagonal item in both orientations.  One rank, midpoint stage 1,
+  // no KWIK / NOPRUNE / candidate reuse; bsa_set_symmetric_sweep and
+  // BSA_PF_SYM=0 switch it off (A/B).  Part of the kept tile-pair list's key.
+  bool sym;
   // the resident step's K4' already wrote this detect's column records and
   // boxes from the state it computed (Ctx::prep; any detect consumes or
   // invalidates them: it rewrites the same buffers)
@@ -2964,7 +3003,11 @@ static int detect_decide(Ctx *c, const DetectRequest &q, DetectPlan *plan) {
   p.tp_list = p.halo && !env.tp_halo_all && !env.tp_super;
   p.tpr = env.tpr && c->tpr_on && p.home && !p.reuse && flags == 0 && !env.tp_super &&
           ((!p.halo && p.prepped && (n + kTile - 1) / kTile <= kTPDirectMax) || p.tp_list);
-  const KeptTilePairs::Key tkey{rpz, hpz, tla, (double)p.mid, (double)rb, (double)re, n};
+  p.sym = env.pf_sym && c->sym_on && p.shared && rb == 0 && re == n && !p.halo && c->nranks == 1 && p.mid &&
+          !p.noprune && !p.kwik && !p.reuse;
+  c->last_sym = p.sym;
+  if (p.sym) c->sym_count++;
+  const KeptTilePairs::Key tkey{rpz, hpz, tla, (double)p.mid, (double)rb, (double)re, p.sym ? 1.0 : 0.0, n};
   p.tvalid = p.tpr && c->tiles.matches(tkey);
   if (decide_hk(c, p, q.host_decides)) return -1;
   if (p.tpr)  // (every rank, also one without rows: the kept state stays collective)
@@ -3224,12 +3267,12 @@ static int detect_tilepairs(DetectRun &R) {
                        p.halo ? halo_present(c) : nullptr, p.a0, p.a1,
                        p.nozero ? (const TileBox *)c->gbox_c.p : (const TileBox *)nullptr,
                        p.tp_list ? (const int *)c->h_hl.p : (const int *)nullptr, (int)c->halo_hl,
-                       p.tp_list ? halo_list_count(c) : (const unsigned *)nullptr, R.tp);
+                       p.tp_list ? halo_list_count(c) : (const unsigned *)nullptr, R.tp, p.sym ? 1 : 0);
   else
     hipLaunchKernelGGL(k_tilepairs, dim3((unsigned)((p.nrt + kSuper - 1) / kSuper)), dim3(kTPThreads), 0, c->stream,
                        p.nrt, p.nct, (int)p.nrows, R.tbox_r, R.gbox_r, (const TileBox *)c->tbox_c.p, p.noprune,
                        (uint2 *)c->tilepairs.p, p.icap, R.dcnt, (unsigned long long *)c->workq.p, R.build,
-                       p.halo ? halo_present(c) : nullptr, p.a0, p.a1);
+                       p.halo ? halo_present(c) : nullptr, p.a0, p.a1, p.sym ? 1 : 0);
   BSA_HIP(c, hipGetLastError());
   return 0;
 }

@@ -694,6 +694,20 @@ int bsa_exact_fusion_stats(bsa_ctx *c, int64_t *out3) {
   return 0;
 }
 
+int bsa_set_symmetric_sweep(bsa_ctx *c, int on) {
+  if (!c) return -1;
+  c->sym_on = on != 0;
+  bsa::invalidate(c, bsa::Change::SetSymSweep);  // (a kept tile-pair list is the other kind: the next detect builds)
+  return 0;
+}
+
+int bsa_symmetric_sweep_stats(bsa_ctx *c, int64_t *out2) {
+  if (!c || !out2) return -1;
+  out2[0] = c->sym_count;
+  out2[1] = c->last_sym ? 1 : 0;
+  return 0;
+}
+
 int bsa_set_candidate_reuse(bsa_ctx *c, int on, double sigma_h, double sigma_v) {
   if (!c) return -1;
   if (on && !(sigma_h > 0.0 && sigma_h < 1e6 && sigma_v > 0.0 && sigma_v < 1e5))

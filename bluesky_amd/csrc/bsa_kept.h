@@ -61,14 +61,17 @@ struct KeptCands {
 };
 
 // K0d's tile-pair list with its record snapshot and, in halo mode, the halo
-// plan kept with it.  The six parameters are compared as bytes
+// plan kept with it.  The seven parameters are compared as
+// bytes.  sym: the list holds each unordered tile pair once, its off-diagonal
+// items flagged mirrored (DetectPlan::sym) -- a list is only
+// ever swept by a detect whose plan took the same choice
 struct KeptTilePairs {
   struct Key {
-    double rpz, hpz, tla, mid, rb, re;
+    double rpz, hpz, tla, mid, rb, re, sym;
     int64_t n;
   };
   bool valid = false;
-  Key key{0, 0, 0, 0, 0, 0, -1};
+  Key key{0, 0, 0, 0, 0, 0, 0, -1};
   bool matches(const Key &k) const { return valid && key.n == k.n && memcmp(&key, &k, offsetof(Key, n)) == 0; }
   bool kept_for(int64_t n) const { return valid && key.n == n; }  // K4' checks its records against this list's budgets
   void keep(const Key &k) {
@@ -148,6 +151,7 @@ enum class Change {
   SetCandReuse,       // bsa_set_candidate_reuse
   SetTileReuse,       // bsa_set_tile_reuse
   SetHk,              // bsa_set_hk
+  SetSymSweep,        // bsa_set_symmetric_sweep
   Count
 };
 struct Drops {
@@ -182,6 +186,7 @@ constexpr Drops kDrops[(int)Change::Count] = {
     /* SetCandReuse      */ {stays, drop, stays, stays, stays, stays},  // p . s s s s
     /* SetTileReuse      */ {stays, stays, drop, stays, stays, stays},  // p s . s s b
     /* SetHk             */ {stays, stays, stays, stays, stays, drop},  // p s s s s .
+    /* SetSymSweep       */ {stays, stays, drop, stays, stays, stays},  // p i . i i b
 };
 
 }  // namespace bsa

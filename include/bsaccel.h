@@ -146,6 +146,17 @@ int bsa_set_exact_fusion(bsa_ctx *ctx, int on, int max_records);
 /* [0] detects enqueued with K1b fused, [1] of them retried unfused (a wave ran
  * out of flush records), [2] whether the last detect fused (0 / 1). */
 int bsa_exact_fusion_stats(bsa_ctx *ctx, int64_t *out3);
+/* Symmetric prefilter sweep (on by default): when the rows
+ * and the columns of a detect are the same aircraft (own == intruder, every
+ * row, one rank; midpoint stage 1, not KWIK / NOPRUNE / candidate reuse) each
+ * unordered pair of 512-aircraft tiles is listed and stage-1-tested once, and
+ * its survivors are refined in both orientations.  Results never depend on
+ * it; off sweeps both orders (A/B; the BSA_PF_SYM=0 environment variable does
+ * the same for every context). */
+int bsa_set_symmetric_sweep(bsa_ctx *ctx, int on);
+/* [0] detects enqueued with the symmetric sweep, [1] whether the last detect
+ * used it (0 / 1). */
+int bsa_symmetric_sweep_stats(bsa_ctx *ctx, int64_t *out2);
 /* Candidate-list reuse across detects (own == intruder, whole row range, not
  * KWIK / NOPRUNE).  A detect that builds the list inflates
  * every aircraft's reach by a horizontal budget sigma_h [m] and a vertical
