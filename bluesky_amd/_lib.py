@@ -13,7 +13,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('BSACCEL_LIB', os.path.join(_HERE, 'libbsaccel.so'))
 
-ABI_VERSION = 1
+ABI_VERSION = 2
 PF_BLOCK_PAIRS = 512   # BSA_PF_BLOCK_PAIRS: stage-1 pair tests per swept prefilter block
 FLAG_WITH_DCPA = 1
 FLAG_NOPRUNE = 2
@@ -173,6 +173,9 @@ SIGNATURES.update({
     'bsa_geo_last_ms': (ctypes.c_int, [_vp, _c_dp]),
     'bsa_sim_acdata_request': (ctypes.c_int, [_vp]),
     'bsa_set_windfield': (ctypes.c_int, [_vp, ctypes.c_int64, _c_dp, _c_dp, _c_dp, _c_dp]),
+    'bsa_set_windfield3d': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_double,
+                                           _c_dp, _c_dp, _c_dp, _c_dp]),
+    'bsa_wind_getdata': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     'bsa_sim_set_limits': (ctypes.c_int, [_vp] + [_c_dp] * 6),
     'bsa_sim_set_perf': (ctypes.c_int, [_vp, ctypes.c_int64, _c_dp, _c_i32p]),
     'bsa_sim_read_perf': (ctypes.c_int, [_vp, _c_u8p, _c_dp]),
@@ -434,6 +437,41 @@ class Context:
             raise ValueError('wind field arrays differ in length')
         self.check(self.lib.bsa_set_windfield(self.h, len(arrs[0]), *[ptr(a) for a in arrs]),
                    'bsa_set_windfield')
+
+    def set_windfield3d(self, lat=None, lon=None, vnorth=None, veast=None, altstep=None):
+        """3-D wind field for winddim 3 (bsa_set_windfield3d): Windfield.lat / lon of
+        the nvec points, Windfield.vnorth / veast (nalt x nvec) and Windfield.altstep [m];
+        no arguments clears it."""
+        if lat is None:
+            self.check(self.lib.bsa_set_windfield3d(self.h, 0, 0, 0.0, None, None, None, None),
+                       'bsa_set_windfield3d')
+            return
+        pts = [f64(x).ravel() for x in (lat, lon)]
+        tabs = [np.ascontiguousarray(x, dtype=np.float64) for x in (vnorth, veast)]
+        nvec = len(pts[0])
+        if len(pts[1]) != nvec or tabs[0].ndim != 2 or tabs[0].shape != tabs[1].shape or tabs[0].shape[1] != nvec:
+            raise ValueError('3-D wind field: lat / lon of nvec points, vnorth / veast of shape (nalt, nvec)')
+        if altstep is None:
+            raise ValueError('3-D wind field: altstep [m] is required')
+        self.check(self.lib.bsa_set_windfield3d(self.h, nvec, tabs[0].shape[0], float(altstep),
+                                                *[ptr(a) for a in pts + tabs]), 'bsa_set_windfield3d')
+
+    def wind_getdata(self, winddim, lat, lon, alt=None):
+        """Windfield.getdata at the given positions (bsa_wind_getdata): winddim 1 / 2 from
+        the 2-D field, 3 from the 3-D field at ``alt`` [m].  Returns (vnorth, veast)."""
+        lat, lon = f64(lat).ravel(), f64(lon).ravel()
+        n = len(lat)
+        if len(lon) != n:
+            raise ValueError('lat and lon differ in length')
+        if alt is not None:
+            alt = f64(alt).ravel()
+            if len(alt) != n:
+                raise ValueError('alt and lat differ in length')
+        vn, ve = np.empty(n), np.empty(n)
+        self.check(self.lib.bsa_wind_getdata(self.h, int(winddim), n, ptr(lat), ptr(lon),
+                                             None if alt is None else ptr(alt), ptr(vn), ptr(ve)),
+                   'bsa_wind_getdata')
+        return vn, ve
 
     # ---------------------------------------------------------------- ACDATA feed
     def sim_acdata_request(self):

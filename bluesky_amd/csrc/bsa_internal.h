@@ -411,6 +411,13 @@ struct Ctx {
   // 2-D wind field (bsa_set_windfield): lat lon vnorth veast of wf_nvec points
   DevBuf wfield;
   int64_t wf_nvec = 0;
+  // 3-D wind field (bsa_set_windfield3d, bsa_wind.hip): lat lon of wf3_nvec points, then
+  // {vnorth, veast}[level * nvec + point] on wf3_nalt levels wf3_altstep [m] apart.
+  // wind_pa: the wind per aircraft k_wind3d wrote last (vnorth, then veast at + wind_pa_n);
+  // wind_stage: bsa_wind_getdata's positions
+  DevBuf wfield3, wind_pa, wind_stage;
+  int64_t wf3_nvec = 0, wf3_nalt = 0, wind_pa_n = 0;
+  double wf3_altstep = 0.0;
 
   // standalone geo matrices (bsa_geo.hip)
   DevBuf geo_in, geo_pts, geo_out;
@@ -616,6 +623,10 @@ struct KinDev {
 int kin_device(Ctx *c, int64_t n, double simdt, int winddim, double vn, double ve, const KinDev &d);
 struct WindField;
 WindField wind_field(const Ctx *c);  // device view of the context's 2-D field (bsa_kin.hip)
+// winddim 3 (bsa_wind.hip): k_wind3d on rows [rb, re) of n, enqueued in front of the kernel that reads
+// wind_field_pa(c), the per-aircraft wind it writes
+int wind3d_launch(Ctx *c, int64_t rb, int64_t re, int64_t n, const double *lat, const double *lon, const double *alt);
+WindField wind_field_pa(const Ctx *c);
 
 // OpenAP drag / thrust / fuel flow (bsa_perf.hip).  forces_consts: Ctx::f_const
 // filled (once).  forces_sim_launch: k_sim_forces of the step about to be

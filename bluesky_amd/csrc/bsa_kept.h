@@ -152,6 +152,7 @@ enum class Change {
   SetTileReuse,       // bsa_set_tile_reuse
   SetHk,              // bsa_set_hk
   SetSymSweep,        // bsa_set_symmetric_sweep
+  WindField,          // bsa_set_windfield3d
   Count
 };
 struct Drops {
@@ -168,6 +169,8 @@ constexpr bool drop = true, stays = false;
 //  (b) a detect without a matching list builds whatever the history says
 //  (c) the detect consumed or re-armed it before it was enqueued
 //  (s) only the dropped state reads that setting
+//  (w) the wind moves aircraft only through K4'; every kept state bounds drift by the records K4' or the
+//      next detect actually writes, against its snapshot, whatever wind produced them -- no state reads the field
 //  (?) unexplained
 constexpr Drops kDrops[(int)Change::Count] = {
     //                      order  cands  tiles  prep   zero   hk
@@ -187,6 +190,7 @@ constexpr Drops kDrops[(int)Change::Count] = {
     /* SetTileReuse      */ {stays, stays, drop, stays, stays, stays},  // p s . s s b
     /* SetHk             */ {stays, stays, stays, stays, stays, drop},  // p s s s s .
     /* SetSymSweep       */ {stays, stays, drop, stays, stays, stays},  // p i . i i b
+    /* WindField         */ {stays, stays, stays, stays, stays, stays}, // w w w w w w
 };
 
 }  // namespace bsa

@@ -15,6 +15,10 @@ __global__ __launch_bounds__(256) void k_kinematics(int n, double simdt, int win
   if (winddim == 2) {  // traffic.py:463: getdata at the pre-step position
     kin::windfield_2d(wf, d.lat[k], d.lon[k], wn, we);
     winddim = 1;
+  } else if (winddim == 3) {  // the 3-D field at the pre-step state, per aircraft (k_wind3d)
+    wn = wf.vn[k];
+    we = wf.ve[k];
+    winddim = 1;
   }
   kin::In s;
   s.tas = d.tas[k];
@@ -64,10 +68,15 @@ WindField wind_field(const Ctx *c) {
 
 int kin_device(Ctx *c, int64_t n, double simdt, int winddim, double vn, double ve, const KinDev &d) {
   if (n <= 0) return 0;
-  if (winddim < 0 || winddim > 2) return fail(c, "winddim %d not supported (0, 1 or 2)", winddim);
+  if (winddim < 0 || winddim > 3) return fail(c, "winddim %d not supported (0, 1, 2 or 3)", winddim);
   if (winddim == 2 && c->wf_nvec < 1) return fail(c, "winddim 2 needs a wind field (bsa_set_windfield)");
+  WindField wf = wind_field(c);
+  if (winddim == 3) {  // traffic.py:463 with a 3-D field: per aircraft at the pre-step state, a kernel of its own
+    if (wind3d_launch(c, 0, n, n, d.lat, d.lon, d.alt)) return -1;
+    wf = wind_field_pa(c);
+  }
   hipLaunchKernelGGL(k_kinematics, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (int)n,
-                     simdt, winddim, vn, ve, wind_field(c), d);
+                     simdt, winddim, vn, ve, wf, d);
   BSA_HIP(c, hipGetLastError());
   return 0;
 }

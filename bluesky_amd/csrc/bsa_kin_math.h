@@ -4,6 +4,7 @@
 // Traffic.UpdateAirSpeed    bluesky/traffic/traffic.py:425-454
 // Traffic.UpdateGroundSpeed bluesky/traffic/traffic.py:456-476 (winddim 0/1/2)
 // Windfield.getdata, 2-D    bluesky/traffic/windfield.py:158-179 (winddim 2)
+// Windfield.getdata, 3-D    bluesky/traffic/windfield.py:158-202 (winddim 3)
 // Traffic.UpdatePosition    bluesky/traffic/traffic.py:478-483
 // aero.vatmos / vtas2cas / vtas2mach  bluesky/tools/aero.py:62-147
 // Every expression keeps numpy's evaluation order (compile with
@@ -16,9 +17,24 @@ namespace bsa {
 
 // 2-D wind field (winddim 2): nvec definition points with their wind
 // (Windfield.lat / lon / vnorth[0, :] / veast[0, :]), device pointers.
+// winddim 3, as the kinematic kernels see it: vn / ve hold the wind per
+// aircraft (indexed like the state arrays), written by k_wind3d (bsa_wind.hip)
+// from the pre-step state before the kernel runs; lat / lon / nvec are unused.
 struct WindField {
   const double *lat, *lon, *vn, *ve;
   int nvec;
+};
+
+// 3-D wind field (winddim 3, bsa_set_windfield3d): nvec definition points and
+// Windfield.vnorth / veast on nalt levels altstep [m] apart, interleaved as
+// tab[level * nvec + point] = {vnorth, veast} -- the lanes of a wave hold
+// different levels and the same point, so a point of one level is one 16-byte
+// read and the level above it one more
+struct WindField3D {
+  const double *lat, *lon;
+  const double2 *tab;
+  int nvec, nalt;
+  double altstep;
 };
 
 namespace kin {
@@ -47,6 +63,74 @@ __device__ __forceinline__ void windfield_2d(const WindField &w, double lat, dou
     vn += w.vn[k] * horfact;
     ve += w.ve[k] * horfact;
   }
+}
+
+// Windfield.getdata's altitude index (windfield.py:185-189) on an axis of nalt
+// levels, altstep apart: the lower level and the weight of the upper one.
+// Build-defined: ialt is clamped into [0, nalt - 2] before any
+// table read -- alt >= the top level gives falt = 1 (the top level's value,
+// where the reference raises IndexError), a NaN altitude level 0 and falt = NaN.
+__device__ __forceinline__ void wind3d_level(double alt, int nalt, double altstep, int &ialt, double &falt) {
+  const double top = (nalt - 1) * altstep;
+  const double a = (top - 1e-20 <= alt || top != top) ? top - 1e-20 : alt;  // np.minimum(top - eps, alt)
+  const double q = a / altstep;
+  const double idxalt = (0. >= q) ? 0. : q;                                 // np.maximum(0., .): a NaN stays
+  const double fl = floor(idxalt);
+  ialt = fl >= 0. ? (fl <= (double)(nalt - 2) ? (int)fl : nalt - 2) : 0;    // (NaN: 0)
+  falt = idxalt - (double)ialt;
+}
+
+// no cache of the weights between windfield_3d's two passes: the second
+// recomputes them (same expressions, same bits)
+struct WindNoCache {
+  static constexpr int kMax = 0;
+  __device__ __forceinline__ void put(int, double) const {}
+  __device__ __forceinline__ double get(int) const { return 0.0; }
+};
+
+// Windfield.getdata for a 3-D field at one position (windfield.py:158-202):
+// windfield_2d's weights, then each of the two levels around alt summed over
+// the points in point order, each term T * (invd2 / sum), and the two blended.
+// tab: {vnorth, veast}[level * nvec + point].  cache: the weights of up to
+// Cache::kMax points kept from the first pass (a field of more recomputes).
+template <class Cache>
+__device__ __forceinline__ void windfield_3d(const WindField3D &w, double lat, double lon, double alt,
+                                             const Cache &cache, double &vn, double &ve) {
+  const double eps = 1e-20;
+  const bool cached = w.nvec <= Cache::kMax;
+  double sum = 0.0;
+  for (int k = 0; k < w.nvec; ++k) {
+    const double cavelat = cos((0.5 * (lat + w.lat[k])) * kD2R);
+    const double dy = lat - w.lat[k];
+    const double dx = cavelat * (lon - w.lon[k]);
+    const double invd2 = 1. / (eps + dx * dx + dy * dy);
+    if (cached) cache.put(k, invd2);
+    sum += invd2;
+  }
+  int ialt;
+  double falt;
+  wind3d_level(alt, w.nalt, w.altstep, ialt, falt);
+  const double2 *lo = w.tab + (size_t)ialt * w.nvec, *hi = lo + w.nvec;
+  double vn0 = 0.0, vn1 = 0.0, ve0 = 0.0, ve1 = 0.0;
+  for (int k = 0; k < w.nvec; ++k) {
+    double invd2;
+    if (cached) {
+      invd2 = cache.get(k);
+    } else {
+      const double cavelat = cos((0.5 * (lat + w.lat[k])) * kD2R);
+      const double dy = lat - w.lat[k];
+      const double dx = cavelat * (lon - w.lon[k]);
+      invd2 = 1. / (eps + dx * dx + dy * dy);
+    }
+    const double horfact = invd2 / sum;
+    const double2 a = lo[k], b = hi[k];
+    vn0 += a.x * horfact;
+    ve0 += a.y * horfact;
+    vn1 += b.x * horfact;
+    ve1 += b.y * horfact;
+  }
+  vn = (1. - falt) * vn0 + falt * vn1;
+  ve = (1. - falt) * ve0 + falt * ve1;
 }
 
 constexpr double kG0 = 9.80665;        // aero.py:18

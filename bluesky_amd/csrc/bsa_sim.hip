@@ -568,7 +568,7 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long lon
 static int check_params(Ctx *c, const bsa_sim_params *p) {
   if (p->cd_every < 1) return fail(c, "cd_every must be >= 1");
   if (p->resume_nav != 0 && p->resume_nav != 1) return fail(c, "resume_nav must be 0 or 1");
-  if (p->winddim < 0 || p->winddim > 2) return fail(c, "winddim must be 0, 1 or 2");
+  if (p->winddim < 0 || p->winddim > 3) return fail(c, "winddim must be 0, 1, 2 or 3");
   if (p->reso != 0 && p->reso != 1) return fail(c, "reso must be 0 or 1");
   return 0;
 }
@@ -674,6 +674,12 @@ static HkPub step_hk_pub(const Ctx *c, const DetectResult &det) {
 static int step_launch(Ctx *c, const StepPlan &sp, const CdOut &cd, const PrepArgs &pa, const HkPub &pub) {
   const bsa_sim_params &p = c->simp;
   const int64_t rb = c->sim_rb, re = c->sim_re, n = c->n;
+  WindField wf = wind_field(c);
+  if (p.winddim == 3) {  // the 3-D field at the pre-step state of the own rows: K4' (either form) reads it per aircraft
+    const SimDev d0 = sim_dev(c);
+    if (wind3d_launch(c, rb, re, n, d0.lat, d0.lon, d0.alt)) return -1;
+    wf = wind_field_pa(c);
+  }
   if (cd.det.k2_kept) {
     if (!cd.mvp_deferred) return fail(c, "internal: fused K2 + K4' without the deferred MVP rows");
     if (!ensure(c, c->nx_alt, n * 8, "next altitudes") || !ensure(c, c->nx_vs, n * 8, "next vs") ||
@@ -684,7 +690,7 @@ static int step_launch(Ctx *c, const StepPlan &sp, const CdOut &cd, const PrepAr
     d.vs_w = (double *)c->nx_vs.p;
     d.gse_w = (double *)c->nx_gse.p;
     d.gsn_w = (double *)c->nx_gsn.p;
-    const K24Args ka{d, cd.mv, p.mvp, pa, wind_field(c), p.simdt, p.windnorth, p.windeast, p.winddim,
+    const K24Args ka{d, cd.mv, p.mvp, pa, wf, p.simdt, p.windnorth, p.windeast, p.winddim,
                      sp.prep ? 1 : 0, pub};
     if (k24_launch(c, cd.det.k2, cd.det.k2_ev, ka)) return -1;
     std::swap(c->own[4], c->nx_alt);
@@ -697,7 +703,7 @@ static int step_launch(Ctx *c, const StepPlan &sp, const CdOut &cd, const PrepAr
     const auto K4 = cd.mvp_deferred ? (sp.prep ? k_sim_pilot_kin<true, true> : k_sim_pilot_kin<true, false>)
                                     : (sp.prep ? k_sim_pilot_kin<false, true> : k_sim_pilot_kin<false, false>);
     hipLaunchKernelGGL(K4, dim3((unsigned)nb), dim3(blk), 0, c->stream, (int)rb, (int)re, p.simdt, p.winddim,
-                       p.windnorth, p.windeast, wind_field(c), sim_dev(c), cd.mv, p.mvp, pa, pub);
+                       p.windnorth, p.windeast, wf, sim_dev(c), cd.mv, p.mvp, pa, pub);
   }
   BSA_HIP(c, hipGetLastError());
   return 0;
@@ -814,6 +820,8 @@ int bsa_sim_step(bsa_ctx *cc, int nsteps) {
   if (!c->sim_ready) return bsa::fail(c, "bsa_sim_step before bsa_sim_init");
   if (c->simp.winddim == 2 && c->wf_nvec < 1)
     return bsa::fail(c, "winddim 2 needs a wind field (bsa_set_windfield)");
+  if (c->simp.winddim == 3 && c->wf3_nvec < 1)
+    return bsa::fail(c, "winddim 3 needs a 3-D wind field (bsa_set_windfield3d)");
   if (nsteps < 0) return bsa::fail(c, "negative step count");
   BSA_HIP(c, hipSetDevice(c->device));
   const int64_t target = c->sim_steps + nsteps;

@@ -85,6 +85,10 @@ __device__ __forceinline__ PFRec pilot_kin_row(int rb, int k, double simdt, int 
   if (winddim == 2) {  // pilot.py:32 and traffic.py:463 read the field at the same pre-step position
     kin::windfield_2d(wf, s.lat, s.lon, vwn, vwe);
     winddim = 1;
+  } else if (winddim == 3) {  // the 3-D field at the same pre-step state, evaluated by k_wind3d before this kernel
+    vwn = wf.vn[k];
+    vwe = wf.ve[k];
+    winddim = 1;
   }
   const double ptrk = act ? atrk : aptrk;             // pilot.py:41
   double asastas = atas;                              // pilot.py:37-38: no wind, GS = TAS

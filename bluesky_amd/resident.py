@@ -45,10 +45,11 @@ def initial_state(traf):
 
 def params(simdt=0.05, rpz=5.0 * NM, hpz=1000.0 * FT, tla=300.0, cd_every=1, reso=True, mar=1.05,
            swresohoriz=True, swresospd=False, swresohdg=False, swresovert=False, swprio=False,
-           priocode='FF1', wind=None, resume_nav=False, windfield=False):
+           priocode='FF1', wind=None, resume_nav=False, windfield=False, windfield3d=False):
     """bsa_sim_params; ASAS defaults of asas.py:81-112 with asas_mar from data/default.cfg.
     ``wind=(vnorth, veast)`` [m/s]: constant wind (winddim 1); ``windfield=True``: the
-    2-D field handed to ``ResidentSim(windfield=...)`` (winddim 2).  ``resume_nav``: ASAS.update's
+    2-D field handed to ``ResidentSim(windfield=...)`` (winddim 2); ``windfield3d=True``: the
+    3-D field handed to ``ResidentSim(windfield3d=...)`` (winddim 3).  ``resume_nav``: ASAS.update's
     resopairs bookkeeping and ResumeNav's asas.active (asas.py:409-504) instead of
     ``active = inconf``."""
     mvp = _lib.MvpParams(Rm=rpz * mar, dhm=hpz * mar, dtlookahead=tla, vmin=200.0 * NM / 3600.,
@@ -59,7 +60,7 @@ def params(simdt=0.05, rpz=5.0 * NM, hpz=1000.0 * FT, tla=300.0, cd_every=1, res
     wn, we = (0.0, 0.0) if wind is None else (float(wind[0]), float(wind[1]))
     return _lib.SimParams(simdt=simdt, rpz=rpz, hpz=hpz, tla=tla, cd_every=int(cd_every),
                           reso=int(bool(reso)), mvp=mvp,
-                          winddim=2 if windfield else (0 if wind is None else 1),
+                          winddim=3 if windfield3d else (2 if windfield else (0 if wind is None else 1)),
                           resume_nav=int(bool(resume_nav)),
                           windnorth=wn, windeast=we)
 
@@ -67,9 +68,14 @@ def params(simdt=0.05, rpz=5.0 * NM, hpz=1000.0 * FT, tla=300.0, cd_every=1, res
 class ResidentSim:
     """Device-resident traffic; ``rank``/``world`` > 1 shards the rows over GPUs."""
 
-    def __init__(self, state, p, ctx=None, rank=0, world=1, windfield=None, limits=None, group=None):
+    def __init__(self, state, p, ctx=None, rank=0, world=1, windfield=None, limits=None, group=None,
+                 windfield3d=None):
         """``windfield``: dict(lat, lon, vnorth, veast) of the 2-D field's points
         (Windfield.lat / lon / vnorth[0, :] / veast[0, :]) for ``winddim`` 2.
+        ``windfield3d``: dict(lat, lon, vnorth, veast, altstep) of the 3-D field
+        (Windfield.lat / lon, vnorth / veast of shape (nalt, nvec), altstep [m])
+        for ``winddim`` 3: Windfield.getdata's altitude branch (windfield.py:181-202)
+        per aircraft; every rank uploads it on its own context.
         ``limits``: per-aircraft OpenAP envelope dict(hmax, vmin, vmax, vsmin,
         vsmax, axmax) for Pilot.applylimits (pilot.py:65-68), or None.
         ``group``: an in-process ``_lib.Group`` to join as ``rank`` instead of
@@ -84,6 +90,8 @@ class ResidentSim:
         if windfield is not None:
             self.ctx.set_windfield(windfield['lat'], windfield['lon'], windfield['vnorth'],
                                    windfield['veast'])
+        if windfield3d is not None:
+            self.set_windfield3d(**windfield3d)
         self.ctx.sim_init(state, p)
         if limits is not None:
             self.ctx.sim_set_limits(limits)
@@ -96,6 +104,12 @@ class ResidentSim:
         """New parameters for the running sim (bsa_sim_set_params; e.g. ZONER / DTLOOK)."""
         self.ctx.sim_set_params(p)
         self.params = p
+
+    def set_windfield3d(self, lat=None, lon=None, vnorth=None, veast=None, altstep=None):
+        """Replace the 3-D wind field between steps (a weather reload; bsa_set_windfield3d).
+        The steps that follow read the new field; no kept detect state is dropped (the
+        field is no detect input).  Sharded: every rank calls it."""
+        self.ctx.set_windfield3d(lat, lon, vnorth, veast, altstep)
 
     def halo_stats(self):
         """Halo exchange of the sharded step (bsa_sim_halo_stats): rx / tx bytes per CD

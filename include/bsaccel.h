@@ -18,6 +18,8 @@
  *       bluesky/tools/aero.py:62-147                 vatmos / vtas2cas / vtas2mach (inlined)
  *   bsa_set_windfield (winddim 2)
  *       bluesky/traffic/windfield.py:158-179         Windfield.getdata, 2-D field
+ *   bsa_set_windfield3d (winddim 3), bsa_wind_getdata
+ *       bluesky/traffic/windfield.py:158-202         Windfield.getdata, 3-D field (per position)
  *   bsa_qdrdist
  *       bluesky/tools/geo.py:110-162,347-363         qdrdist_matrix / kwikqdrdist_matrix, materialised
  *   bsa_sim_set_limits
@@ -40,7 +42,7 @@
 extern "C" {
 #endif
 
-#define BSA_ABI_VERSION 1
+#define BSA_ABI_VERSION 2
 
 typedef struct bsa_ctx bsa_ctx;
 
@@ -273,7 +275,8 @@ int bsa_mvp(bsa_ctx *ctx, const bsa_mvp_params *p,
  * (bluesky/traffic/traffic.py:425-483) for n aircraft, one fused kernel.
  * winddim 0 = no wind, 1 = constant wind (windnorth/windeast m/s,
  * windfield.py:150-152), 2 = the context's 2-D wind field (bsa_set_windfield;
- * windnorth/windeast ignored).  Host arrays of length n; state arrays are updated
+ * windnorth/windeast ignored), 3 = the context's 3-D wind field
+ * (bsa_set_windfield3d; windnorth/windeast ignored).  Host arrays of length n; state arrays are updated
  * in place; output pointers may be NULL. */
 typedef struct bsa_kin_io {
   /* inputs */
@@ -295,11 +298,41 @@ int bsa_kinematics(bsa_ctx *ctx, int64_t n, double simdt, int winddim,
  * lat/lon [deg] with wind vnorth/veast [m/s] (Windfield.vnorth[0, :] /
  * veast[0, :], as WindSim.addpoint stores them).  Evaluated per aircraft at
  * its pre-step position, for both Pilot.APorASAS (pilot.py:31-35) and
- * UpdateGroundSpeed (traffic.py:463).  Altitude profiles (winddim 3) are not
- * supported: the reference's 3-D branch raises for arrays (windfield.py:177).
- * nvec = 0 clears the field.  Host arrays are copied. */
+ * UpdateGroundSpeed (traffic.py:463).  Altitude profiles are the 3-D field
+ * below.  nvec = 0 clears the field.  Host arrays are copied. */
 int bsa_set_windfield(bsa_ctx *ctx, int64_t nvec, const double *lat, const double *lon,
                       const double *vnorth, const double *veast);
+
+/* 3-D wind field for winddim 3 (bsa_kinematics, the resident sim,
+ * bsa_wind_getdata): Windfield.getdata with altitude profiles
+ * (bluesky/traffic/windfield.py:158-202).  The reference's getdata raises for
+ * array arguments longer than one (windfield.py:177 takes the truth value of
+ * an array comparison) but evaluates one position at a time; the pin is that
+ * per-aircraft result.  The 2-D field's horizontal weights, then
+ *   idxalt = max(0, min((nalt-1)*altstep - 1e-20, alt) / altstep),
+ *   ialt = floor(idxalt), falt = idxalt - ialt,
+ *   vn = (1-falt) * sum_k vnorth[ialt,k] horfact_k + falt * sum_k vnorth[ialt+1,k] horfact_k
+ * (veast alike), at each aircraft's pre-step position and altitude.
+ * vnorth / veast: Windfield.vnorth / veast as WindSim.addpoint leaves them,
+ * nalt x nvec doubles, row-major (Windfield: nalt = 451, altstep = 100 ft).
+ * Build-defined: ialt is clamped into [0, nalt-2] before any table read, so
+ * alt >= (nalt-1)*altstep (where the reference raises IndexError) gives the
+ * top level's wind and a NaN altitude a NaN wind; nothing outside the table is
+ * ever read.  nvec >= 1, nalt >= 2, altstep > 0; nvec = 0 clears the field.
+ * Stored apart from the 2-D field; winddim selects which one is read.  Host
+ * arrays are copied.  May be called between steps of a resident sim (a
+ * weather reload); no kept detect state depends on the field. */
+int bsa_set_windfield3d(bsa_ctx *ctx, int64_t nvec, int64_t nalt, double altstep,
+                        const double *lat, const double *lon,
+                        const double *vnorth, const double *veast);
+
+/* Windfield.getdata at n host-given positions -- the array form the reference
+ * lacks for 3-D fields (its callers: traffic.py:280,355, autopilot.py:336).
+ * winddim 1: the 2-D field's first point everywhere (windfield.py:150-152),
+ * 2: the 2-D field, 3: the 3-D field (alt [m]; ignored and may be NULL
+ * otherwise).  vn_out / ve_out: n doubles [m/s]. */
+int bsa_wind_getdata(bsa_ctx *ctx, int winddim, int64_t n, const double *lat, const double *lon,
+                     const double *alt, double *vn_out, double *ve_out);
 
 /* ---------------------------------------------------------------- geo matrices
  * Standalone materialised producers of
@@ -407,7 +440,7 @@ typedef struct bsa_sim_params {
                        Either way asas.active = inconf, or ResumeNav's with resume_nav = 1 */
   bsa_mvp_params mvp;
   int32_t winddim;  /* 0 = no wind, 1 = constant wind (windfield.py:150-152), 2 = 2-D field
-                       (bsa_set_windfield): the wind branches of Pilot.APorASAS
+                       (bsa_set_windfield), 3 = 3-D field (bsa_set_windfield3d): the wind branches of Pilot.APorASAS
                        (pilot.py:31-36,51-61) and UpdateGroundSpeed */
   int32_t resume_nav; /* 1: ASAS.update bookkeeping on the device: resopairs, ResumeNav's
                          asas.active (asas.py:409-471) and the unique / cumulative pair

@@ -10,7 +10,13 @@ and outputs as small ``.npz`` files under ``tests/golden/``:
 * ``mvp_<case>.npz``  -- ``MVP.resolve`` (MVP.py:14-143) for several switch sets
 * ``kin_<case>.npz``  -- ``Traffic.UpdateAirSpeed/GroundSpeed/Position``
                          (traffic.py:425-483)
-* ``asas_<case>.npz``  -- ``ASAS.update``'s bookkeeping + ``ResumeNav``
+* ``wind3d_<case>.npz`` -- ``Windfield.getdata`` of a field with altitude profiles
+                         (windfield.py:158-202), one call per position, and
+                         ``kin3d_wind1500.npz``, the kinematics over such a field
+                         (not ``kin_*``: the tests over that pattern hand a
+                         fixture's wind on as two scalars)
+                         (``--wind3d-only`` writes only these)
+* ``asas_<case>.npz``  --``ASAS.update``'s bookkeeping + ``ResumeNav``
                          (asas.py:409-504) over a few CD calls, run by the
                          reference's own ``ASAS.update`` on a stand-in ``bs.traf``
 * ``geo_<case>.npz``   -- standalone ``geo.qdrdist_matrix`` / ``geo.kwikqdrdist_matrix``
@@ -407,6 +413,127 @@ def run_kin(name, n, seed, dt, wind=None):
     out.update({'out_' + k: v for k, v in ref.items()})
     np.savez_compressed(os.path.join(OUT, 'kin_%s.npz' % name), **out)
     print('kin_%-17s N=%5d dt=%g wind=%s' % (name, n, dt, wind))
+
+
+# ---------------------------------------------------------------- 3-D wind field
+# Windfield.getdata's altitude branch (windfield.py:181-202).  The reference
+# raises for array arguments longer than one (windfield.py:177) and runs for
+# one position at a time: the pin is one call per aircraft with one-element arrays.
+def wind3d_fields():
+    """name -> list of (lat, lon, winddir, windspd[, windalt]) for WindSim.addpoint."""
+    rng = np.random.default_rng(91)
+    prof = lambda k: ([float(a) for a in np.sort(rng.uniform(0.0, 13000.0, k))],          # noqa: E731
+                      [float(d) for d in rng.uniform(0.0, 360.0, k)],
+                      [float(v) for v in rng.uniform(2.0, 60.0, k)])
+    n5 = []
+    for (la, lo, k) in ((52.0, 4.0, 4), (52.8, 3.1, 3), (51.4, 5.2, 6)):                  # 3 profile points
+        alts, dirs, spds = prof(k)
+        n5.append((la, lo, dirs, spds, alts))
+    n5 += [(52.4, 5.6, 250.0, 18.0), (51.0, 3.5, 40.0, 7.5)]                              # 2 plain points
+    alts, dirs, spds = prof(5)
+    n1 = [(52.0, 4.0, dirs, spds, alts)]
+    n67 = []
+    for q in range(67):                                                                   # an irregular grid
+        la = 50.0 + 0.45 * (q // 9) + float(rng.uniform(-0.15, 0.15))
+        lo = 2.0 + 0.55 * (q % 9) + float(rng.uniform(-0.2, 0.2))
+        if q % 8 == 3:
+            alts, dirs, spds = prof(4)
+            n67.append((la, lo, dirs, spds, alts))
+        else:
+            n67.append((la, lo, float(rng.uniform(0, 360)), float(rng.uniform(2, 40))))
+    return dict(n1=n1, n5=n5, n67=n67)
+
+
+def make_wind3d(points):
+    w = WindSim()
+    for pt in points:
+        w.addpoint(*pt)
+    assert w.winddim == 3
+    return w
+
+
+def ref_getdata_each(w, lat, lon, alt):
+    """The reference's getdata, one call per aircraft with one-element arrays."""
+    vn, ve = np.empty(len(lat)), np.empty(len(lat))
+    for i in range(len(lat)):
+        a, b = w.getdata(np.array([lat[i]]), np.array([lon[i]]), np.array([alt[i]]))
+        vn[i], ve[i] = a[0], b[0]
+    return vn, ve
+
+
+def wind3d_positions(w, npos, seed):
+    """Random positions over the field plus the edge positions the reference accepts."""
+    rng = np.random.default_rng(seed)
+    lat = rng.uniform(49.5, 54.5, npos)
+    lon = rng.uniform(1.5, 7.5, npos)
+    alt = rng.uniform(0.0, 13700.0, npos)
+    st = float(w.altstep)
+    edge_alt = [-10.0, 0.0, 7 * st, 13715.9, 49.0 * ft, 51.0 * ft, 50.0 * ft]
+    alt[:len(edge_alt)] = edge_alt
+    lat[8], lon[8] = float(w.lat[0]), float(w.lon[0])          # exactly on a definition point
+    alt[8] = 3 * st + 11.0
+    lat[9:12] = [-52.0, -0.5, -89.0]                           # latitudes of the opposite sign
+    return lat, lon, alt
+
+
+def run_wind3d(name, points, npos, seed):
+    from tests import wind3d_np
+    w = make_wind3d(points)
+    lat, lon, alt = wind3d_positions(w, npos, seed)
+    vn, ve = ref_getdata_each(w, lat, lon, alt)
+    field = dict(wlat=np.array(w.lat, dtype=np.float64), wlon=np.array(w.lon, dtype=np.float64),
+                 wvnorth=np.array(w.vnorth), wveast=np.array(w.veast), altstep=float(w.altstep))
+    assert field['wvnorth'].shape == (w.nalt, len(points))
+    hn, he = wind3d_np.getdata(lat, lon, alt, **field)
+    assert np.array_equal(hn, vn) and np.array_equal(he, ve), 'helper != reference wind3d %s' % name
+    np.savez_compressed(os.path.join(OUT, 'wind3d_%s.npz' % name), lat=lat, lon=lon, alt=alt,
+                        vnorth=vn, veast=ve, **field)
+    print('wind3d_%-14s nvec=%3d npos=%5d' % (name, len(points), npos))
+
+
+def run_kin_wind3d(name, n, seed, dt, points):
+    """Update* on a fake traf whose wind.getdata makes the per-aircraft calls."""
+    from tests import wind3d_np
+    s = kin_state(n, seed)
+    s['alt'][:4] = [-10.0, 0.0, 49.0 * ft, 51.0 * ft]
+    w = make_wind3d(points)
+    fake = types.SimpleNamespace()
+    fake.pilot = types.SimpleNamespace(tas=s['ptas'].copy(), hdg=s['phdg'].copy(),
+                                       alt=s['palt'].copy(), vs=s['pvs'].copy())
+    fake.tas, fake.hdg, fake.alt, fake.vs = (s['tas'].copy(), s['hdg'].copy(),
+                                             s['alt'].copy(), s['vs'].copy())
+    fake.lat, fake.lon = s['lat'].copy(), s['lon'].copy()
+    fake.bank, fake.eps = s['bank'].copy(), s['eps'].copy()
+    acc = s['accel'].copy()
+    fake.perf = types.SimpleNamespace(acceleration=lambda: acc)
+    fake.wind = types.SimpleNamespace(winddim=3, getdata=lambda la, lo, al: ref_getdata_each(w, la, lo, al))
+    RefTraffic.UpdateAirSpeed(fake, dt, 0.0)
+    RefTraffic.UpdateGroundSpeed(fake, dt)
+    RefTraffic.UpdatePosition(fake, dt)
+    keys = ('ax', 'delspd', 'tas', 'cas', 'M', 'hdg', 'swhdgsel', 'swaltsel', 'az', 'vs',
+            'gsnorth', 'gseast', 'gs', 'trk', 'alt', 'lat', 'lon', 'coslat')
+    ref = {k: np.asarray(getattr(fake, k)) for k in keys}
+    field = dict(wlat=np.array(w.lat, dtype=np.float64), wlon=np.array(w.lon, dtype=np.float64),
+                 wvnorth=np.array(w.vnorth), wveast=np.array(w.veast), altstep=float(w.altstep))
+    vn, ve = ref_getdata_each(w, s['lat'], s['lon'], s['alt'])
+    hn, he = wind3d_np.getdata(s['lat'], s['lon'], s['alt'], **field)
+    assert np.array_equal(hn, vn) and np.array_equal(he, ve), 'helper != reference wind3d (kin)'
+    o = okin.step(s, dt, winddim=1, windnorth=hn, windeast=he)
+    for k in keys:
+        assert np.array_equal(o[k], ref[k], equal_nan=True), 'oracle != reference kin %s/%s' % (name, k)
+    out = dict(dt=dt, winddim=3, windnorth=vn, windeast=ve, **s)
+    out.update(field)
+    out.update({'out_' + k: v for k, v in ref.items()})
+    np.savez_compressed(os.path.join(OUT, 'kin3d_%s.npz' % name), **out)
+    print('kin3d_%-15s N=%5d dt=%g 3-D field of %d points' % (name, n, dt, len(points)))
+
+
+def run_wind3d_all():
+    f = wind3d_fields()
+    run_wind3d('n1', f['n1'], 200, 92)
+    run_wind3d('n5', f['n5'], 2000, 93)
+    run_wind3d('n67', f['n67'], 500, 94)
+    run_kin_wind3d('wind1500', 1500, 95, 0.05, f['n5'])
 
 
 def run_limits(name, n, seed):
@@ -1598,6 +1725,9 @@ def main():
     if '--windfield-only' in sys.argv:
         run_kin('windfield1500', 1500, 34, 0.05, wind=WIND_FIELD)
         return
+    if '--wind3d-only' in sys.argv:
+        run_wind3d_all()
+        return
     if '--geo-only' in sys.argv:
         for case in geo_cases():
             run_geo(*case)
@@ -1621,6 +1751,7 @@ def main():
     run_kin('nowind_dt1', 500, 32, 1.0)
     run_kin('wind1000', 1000, 33, 0.05, wind=(270.0, 25.0 * kts))
     run_kin('windfield1500', 1500, 34, 0.05, wind=WIND_FIELD)
+    run_wind3d_all()
     run_limits('openap2000', 2000, 71)
     run_perf('openap3000', 3000, 73)
     run_forces('forces3000', 3000, 75)
