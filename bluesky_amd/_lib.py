@@ -28,6 +28,7 @@ _c_fp = ctypes.POINTER(ctypes.c_float)
 _c_i32p = ctypes.POINTER(ctypes.c_int32)
 _c_u8p = ctypes.POINTER(ctypes.c_uint8)
 _c_i64p = ctypes.POINTER(ctypes.c_int64)
+_c_u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
 
 
@@ -238,6 +239,12 @@ SIGNATURES.update({
                         [_c_dp] * 7 + [ctypes.POINTER(FmsState), _c_dp, _c_i32p]),
     'bsa_sim_set_recovery': (ctypes.c_int, [_vp, ctypes.c_int]),
     'bsa_sim_read_dropcount': (ctypes.c_int, [_vp, _c_i32p]),
+    'bsa_turb_draws': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                      _c_u64p, _c_dp]),
+    'bsa_turb_apply': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_double] + [_c_dp] * 4 +
+                       [ctypes.c_uint64, ctypes.c_uint64] + [_c_dp] * 5),
+    'bsa_sim_set_turbulence': (ctypes.c_int, [_vp, ctypes.c_int, _c_dp, ctypes.c_uint64]),
+    'bsa_sim_turb_call': (ctypes.c_int, [_vp, _c_i64p, _c_i64p]),
 })
 
 UNIQUE_ID_BYTES = 128
@@ -809,6 +816,49 @@ class Context:
     def sim_set_recovery(self, on=True):
         """bsa_sim_set_recovery: waypoint recovery after ResumeNav in the resident step."""
         self.check(self.lib.bsa_sim_set_recovery(self.h, 1 if on else 0), 'bsa_sim_set_recovery')
+
+    # ---------------------------------------------------------------- turbulence
+    def turb_draws(self, n, seed=0, call=0, first_index=0, raw=True):
+        """bsa_turb_draws: (raw Philox words (n, 4) uint64 or None, unit normals (n, 3)) of the
+        aircraft indices ``first_index .. first_index + n - 1`` of call number ``call``."""
+        n = int(n)
+        words = np.empty((n, 4), dtype=np.uint64) if raw else None
+        z = np.empty((n, 3))
+        self.check(self.lib.bsa_turb_draws(self.h, n, int(seed), int(call), int(first_index),
+                                           ptr(words, _c_u64p), ptr(z)), 'bsa_turb_draws')
+        return words, z
+
+    def turb_apply(self, dt, sd, trk, coslat, lat, lon, alt, draws=None, seed=0, call=0):
+        """bsa_turb_apply: one Turbulence.Woosh; ``draws``: the unit normals (hf, hw, alt) to
+        apply, or None for the draws of (seed, call, index).  Returns the new (lat, lon, alt)."""
+        sd = f64(sd).ravel()
+        if len(sd) != 3:
+            raise ValueError('sd: three standard deviations (flight direction, wing direction, vertical)')
+        trk, coslat = f64(trk).ravel(), f64(coslat).ravel()
+        out = [f64(x).ravel().copy() for x in (lat, lon, alt)]
+        n = len(trk)
+        z = [None] * 3 if draws is None else [f64(x).ravel() for x in draws]
+        if any(len(x) != n for x in [coslat] + out + [x for x in z if x is not None]) or len(z) != 3:
+            raise ValueError('turbulence arrays differ in length')
+        self.check(self.lib.bsa_turb_apply(self.h, n, float(dt), ptr(sd), ptr(z[0]), ptr(z[1]), ptr(z[2]),
+                                           int(seed), int(call), ptr(trk), ptr(coslat), *[ptr(x) for x in out]),
+                   'bsa_turb_apply')
+        return tuple(out)
+
+    def sim_set_turbulence(self, on=True, sd=(0, 0.1, 0.1), seed=0):
+        """bsa_sim_set_turbulence: Turbulence.Woosh as the last stage of every resident step."""
+        sd = f64(sd).ravel()
+        if len(sd) != 3:
+            raise ValueError('sd: three standard deviations (flight direction, wing direction, vertical)')
+        self.check(self.lib.bsa_sim_set_turbulence(self.h, 1 if on else 0, ptr(sd), int(seed)),
+                   'bsa_sim_set_turbulence')
+
+    def sim_turb_call(self, set_to=None):
+        """bsa_sim_turb_call: the call number of the next step's draws (after setting it, if given)."""
+        out = ctypes.c_int64(0)
+        new = None if set_to is None else ctypes.byref(ctypes.c_int64(int(set_to)))
+        self.check(self.lib.bsa_sim_turb_call(self.h, ctypes.byref(out), new), 'bsa_sim_turb_call')
+        return out.value
 
     def sim_read_dropcount(self):
         """bsa_sim_read_dropcount: resopairs ResumeNav dropped per ownship in the last CD

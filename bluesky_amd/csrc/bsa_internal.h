@@ -419,6 +419,15 @@ struct Ctx {
   int64_t wf3_nvec = 0, wf3_nalt = 0, wind_pa_n = 0;
   double wf3_altstep = 0.0;
 
+  // Turbulence.Woosh in the resident step (bsa_sim_set_turbulence, bsa_turb.hip): sd as given
+  // (clamped where the scale is made), the seed, and the call number of the next step's draws -- the host's,
+  // advanced per enqueued step while on and replayed after an abort.  turb_stage: bsa_turb_draws / _apply's arrays
+  DevBuf turb_stage;
+  bool sim_turb = false;
+  double turb_sd[3] = {0.0, 0.0, 0.0};
+  unsigned long long turb_seed = 0;
+  int64_t turb_call = 0;
+
   // standalone geo matrices (bsa_geo.hip)
   DevBuf geo_in, geo_pts, geo_out;
   hipEvent_t geo_ev[2] = {nullptr, nullptr};
@@ -627,6 +636,10 @@ WindField wind_field(const Ctx *c);  // device view of the context's 2-D field (
 // wind_field_pa(c), the per-aircraft wind it writes
 int wind3d_launch(Ctx *c, int64_t rb, int64_t re, int64_t n, const double *lat, const double *lon, const double *alt);
 WindField wind_field_pa(const Ctx *c);
+// Turbulence.Woosh of the step (bsa_turb.hip): k_sim_turb on home rows [rb, re), call number Ctx::turb_call,
+// enqueued after the step's K4' on the arrays it wrote
+int turb_sim_launch(Ctx *c, int64_t rb, int64_t re, const unsigned *sticky, const double *trk, double *lat,
+                    double *lon, double *alt);
 
 // OpenAP drag / thrust / fuel flow (bsa_perf.hip).  forces_consts: Ctx::f_const
 // filled (once).  forces_sim_launch: k_sim_forces of the step about to be

@@ -153,6 +153,7 @@ enum class Change {
   SetHk,              // bsa_set_hk
   SetSymSweep,        // bsa_set_symmetric_sweep
   WindField,          // bsa_set_windfield3d
+  Turbulence,         // bsa_sim_set_turbulence: on / off, sd, seed
   Count
 };
 struct Drops {
@@ -171,6 +172,11 @@ constexpr bool drop = true, stays = false;
 //  (s) only the dropped state reads that setting
 //  (w) the wind moves aircraft only through K4'; every kept state bounds drift by the records K4' or the
 //      next detect actually writes, against its snapshot, whatever wind produced them -- no state reads the field
+//  (t) turbulence moves aircraft after K4', so K4' prepares no records while it is on (StepPlan::prep) and every
+//      detect makes its own from the perturbed state with K0b: on one rank no list is kept then (a kept list needs
+//      prepared records), on several the own-tile K0b checks every record against the list's snapshot.  Switching
+//      it on, off or to other sd / seed drops what was made under the other setting's drift: the prepared
+//      records' budget check and HK's predictions assumed it
 //  (?) unexplained
 constexpr Drops kDrops[(int)Change::Count] = {
     //                      order  cands  tiles  prep   zero   hk
@@ -191,6 +197,7 @@ constexpr Drops kDrops[(int)Change::Count] = {
     /* SetHk             */ {stays, stays, stays, stays, stays, drop},  // p s s s s .
     /* SetSymSweep       */ {stays, stays, drop, stays, stays, stays},  // p i . i i b
     /* WindField         */ {stays, stays, stays, stays, stays, stays}, // w w w w w w
+    /* Turbulence        */ {stays, drop, drop, drop, stays, drop},     // p t t t z t
 };
 
 }  // namespace bsa

@@ -483,9 +483,11 @@ struct BatchBase {
   bool gs_derivable;
   double fms_simt, fms_t0;  // the FMS clock
   int64_t fms_ticks;
+  int64_t turb_call;  // the draws' call number
 };
 static int batch_begin(Ctx *c, bool kin, BatchBase *b) {
-  *b = BatchBase{kin, c->sim_steps, c->sim_cd_calls, c->sim_gs_derivable, c->fms_simt, c->fms_t0, c->fms_ticks};
+  *b = BatchBase{kin, c->sim_steps, c->sim_cd_calls, c->sim_gs_derivable, c->fms_simt, c->fms_t0, c->fms_ticks,
+                 c->turb_call};
   BSA_HIP(c, hipMemsetAsync((char *)c->sim_ctl.p + kSimCtlSticky, 0, 40, c->stream));  // sticky, steps_done, demands, stale
   return 0;
 }
@@ -523,6 +525,9 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long lon
     for (int64_t k = 0; k < done; ++k) fms_clock_step(c);
     if (fms_ticks_at(c->fms_simt, c->fms_t0) && fms_sim_restore(c)) return -1;
   }
+  // the draws are a pure function of (seed, call, index): the completed steps took one call number each, the
+  // aborted step's k_sim_turb returned behind the sticky word -- nothing to undo
+  if (base.kin && c->sim_turb) c->turb_call = base.turb_call + done;
   // the last detect's counters: every detect after the abort ran on the same, unchanged state
   Counters h;
   BSA_HIP(c, hipMemcpy(&h, c->counters.p, sizeof(h), hipMemcpyDeviceToHost));
@@ -607,7 +612,8 @@ static StepPlan step_decide(const Ctx *c, bool rerun_first) {
   sp.k24 = sp.cd && env.k24 && c->nranks == 1 && c->halo_mode == 0 && !c->simp.resume_nav && re > rb &&
            c->k2_bucket > 0;
   sp.prep = env.sim_prep && c->nranks == 1 && c->home && !c->reuse_on && c->halo_mode == 0 && rb == 0 &&
-            re == c->n && (c->sim_steps + 1) % c->simp.cd_every == 0;
+            re == c->n && (c->sim_steps + 1) % c->simp.cd_every == 0 &&
+            !c->sim_turb;  // turbulence moves the aircraft after K4': the next detect makes its own records (K0b)
   sp.k4_block = env.k4_block;  // (PREP: whole waves = whole groups, rb = 0)
   return sp;
 }
@@ -724,6 +730,11 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
   PrepArgs pa{};
   if (sp.prep && step_prep_args(c, &pa)) return -1;
   if (step_launch(c, sp, cd, pa, step_hk_pub(c, cd.det))) return -1;
+  if (c->sim_turb) {  // Turbulence.Woosh, the last statement of Traffic.update (traffic.py:416), on what K4' wrote
+    const SimDev d = sim_dev(c);
+    if (turb_sim_launch(c, c->sim_rb, c->sim_re, d.sticky, d.trk, d.lat, d.lon, d.alt)) return -1;
+    c->turb_call++;
+  }
   if (sp.prep)
     c->prep.keep({pa.rpz, pa.hpz, pa.tla, (double)pa.mid, c->n});
   else
@@ -761,7 +772,8 @@ int bsa_sim_init(bsa_ctx *cc, int64_t n, const bsa_sim_state *s, const bsa_sim_p
   bsa::set_rank_rows(c);
   if (bsa::set_home_maps(c)) return -1;
   c->sim_noreso = c->sim_resooff = false;  // empty NORESO / RESOOFF lists
-  c->sim_atmos = c->sim_limits = c->sim_perf = c->sim_forces = c->sim_fms = c->sim_recovery = false;
+  c->sim_atmos = c->sim_limits = c->sim_perf = c->sim_forces = c->sim_fms = c->sim_recovery = c->sim_turb = false;
+  c->turb_call = 0;
   // every always-present array (kSimArrays); the all-gathered ones hold nranks
   // x rpr entries (in-place all-gather).  Zero unless a state field fills it:
   // asas.vs, asase / asasn, inactive, traf.ax, no ResumeNav drops

@@ -45,24 +45,29 @@ def initial_state(traf):
 
 def params(simdt=0.05, rpz=5.0 * NM, hpz=1000.0 * FT, tla=300.0, cd_every=1, reso=True, mar=1.05,
            swresohoriz=True, swresospd=False, swresohdg=False, swresovert=False, swprio=False,
-           priocode='FF1', wind=None, resume_nav=False, windfield=False, windfield3d=False):
+           priocode='FF1', wind=None, resume_nav=False, windfield=False, windfield3d=False, turbulence=None):
     """bsa_sim_params; ASAS defaults of asas.py:81-112 with asas_mar from data/default.cfg.
     ``wind=(vnorth, veast)`` [m/s]: constant wind (winddim 1); ``windfield=True``: the
     2-D field handed to ``ResidentSim(windfield=...)`` (winddim 2); ``windfield3d=True``: the
     3-D field handed to ``ResidentSim(windfield3d=...)`` (winddim 3).  ``resume_nav``: ASAS.update's
     resopairs bookkeeping and ResumeNav's asas.active (asas.py:409-504) instead of
-    ``active = inconf``."""
+    ``active = inconf``.  ``turbulence``: dict(on, sd, seed) for ``ResidentSim.set_turbulence``, which
+    ``ResidentSim`` applies right after its init (kept beside the C struct, not in it)."""
     mvp = _lib.MvpParams(Rm=rpz * mar, dhm=hpz * mar, dtlookahead=tla, vmin=200.0 * NM / 3600.,
                          vmax=500.0 * NM / 3600., vsmin=-3000. / 60. * FT, vsmax=3000. / 60. * FT,
                          swresohoriz=int(swresohoriz), swresospd=int(swresospd),
                          swresohdg=int(swresohdg), swresovert=int(swresovert), swprio=int(swprio),
                          priocode=_lib.PRIO_CODES.get(priocode, 0), swnoreso=0, swresooff=0)
     wn, we = (0.0, 0.0) if wind is None else (float(wind[0]), float(wind[1]))
-    return _lib.SimParams(simdt=simdt, rpz=rpz, hpz=hpz, tla=tla, cd_every=int(cd_every),
+    if turbulence is not None and not set(turbulence) <= {'on', 'sd', 'seed'}:
+        raise ValueError('turbulence: dict(on=, sd=, seed=)')
+    p = _lib.SimParams(simdt=simdt, rpz=rpz, hpz=hpz, tla=tla, cd_every=int(cd_every),
                           reso=int(bool(reso)), mvp=mvp,
                           winddim=3 if windfield3d else (2 if windfield else (0 if wind is None else 1)),
                           resume_nav=int(bool(resume_nav)),
                           windnorth=wn, windeast=we)
+    p.turbulence = None if turbulence is None else dict(turbulence)
+    return p
 
 
 class ResidentSim:
@@ -96,6 +101,8 @@ class ResidentSim:
         if limits is not None:
             self.ctx.sim_set_limits(limits)
         self.params = p
+        if getattr(p, 'turbulence', None) is not None:
+            self.set_turbulence(**p.turbulence)
 
     def step(self, nsteps=1):
         self.ctx.sim_step(nsteps)
@@ -110,6 +117,23 @@ class ResidentSim:
         The steps that follow read the new field; no kept detect state is dropped (the
         field is no detect input).  Sharded: every rank calls it."""
         self.ctx.set_windfield3d(lat, lon, vnorth, veast, altstep)
+
+    def set_turbulence(self, on=True, sd=(0, 0.1, 0.1), seed=0):
+        """Turbulence.Woosh (turbulence.py:24-46) as the last stage of every step
+        (bsa_sim_set_turbulence): position noise with standard deviations ``sd`` [m/s] along
+        the flight direction, the wing direction and the vertical, scaled by sqrt(simdt);
+        ``sd`` is clamped like ``SetStandards`` (at least 1e-6).  The draws are build-defined
+        (``bluesky_amd.turbulence.draws``): a function of ``seed``, the call number
+        (``turb_call``) and the aircraft's current index only, so a run repeats bitwise
+        whatever the batching or the rank count.  While on, every detect makes its records
+        from the perturbed state.  ``on=False`` keeps ``sd`` / ``seed`` but
+        runs nothing.  Sharded: every rank calls it alike."""
+        self.ctx.sim_set_turbulence(on, sd, seed)
+
+    def turb_call(self, set_to=None):
+        """The call number of the next step's draws (0 at init, + 1 per step while
+        turbulence is on); ``set_to`` continues another sim's stream."""
+        return self.ctx.sim_turb_call(set_to)
 
     def halo_stats(self):
         """Halo exchange of the sharded step (bsa_sim_halo_stats): rx / tx bytes per CD

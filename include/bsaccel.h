@@ -20,6 +20,8 @@
  *       bluesky/traffic/windfield.py:158-179         Windfield.getdata, 2-D field
  *   bsa_set_windfield3d (winddim 3), bsa_wind_getdata
  *       bluesky/traffic/windfield.py:158-202         Windfield.getdata, 3-D field (per position)
+ *   bsa_turb_draws, bsa_turb_apply, bsa_sim_set_turbulence
+ *       bluesky/traffic/turbulence.py:24-46          Turbulence.Woosh (build-defined draws)
  *   bsa_qdrdist
  *       bluesky/tools/geo.py:110-162,347-363         qdrdist_matrix / kwikqdrdist_matrix, materialised
  *   bsa_sim_set_limits
@@ -594,6 +596,47 @@ int bsa_sim_set_recovery(bsa_ctx *ctx, int on);
 /* Resopairs ResumeNav dropped per ownship in the last CD call (resume_nav = 1),
  * this rank's rows into a full-n host array: bsa_asas_out.dropped as a count. */
 int bsa_sim_read_dropcount(bsa_ctx *ctx, int32_t *count);
+/* ---------------------------------------------------------------- turbulence
+ * Turbulence.Woosh (bluesky/traffic/turbulence.py:24-46): position noise along
+ * the flight direction, the wing direction and the vertical.  The reference
+ * draws from numpy's global Mersenne state; here the draws are build-defined:
+ * aircraft `index` of call number `call` owns one Philox4x64-10 block,
+ *   counter = {index, call, 0, 0}, key = {seed, 0}      -> words w0..w3
+ *   u_i = ((w_i >> 11) + 0.5) * 2^-53                    (never 0)
+ *   z0 = sqrt(-2 log u0) cos(2 pi u1), z1 = sqrt(-2 log u0) sin(2 pi u1),
+ *   z2 = sqrt(-2 log u2) cos(2 pi u3)
+ * and turbhf, turbhw, turbalt = (sd[k] * sqrt(dt)) * z_k.  A pure function of
+ * (seed, call, index): no state, any order, any partition.  sd: three finite
+ * values >= 0, clamped like Turbulence.SetStandards (sd > 1e-6 ? sd : 1e-6).
+ *
+ * bsa_turb_draws: indices first_index .. first_index + n - 1 of one call.
+ * raw4n (4 n words, index-major; may be NULL) and z3n (3 n unit normals,
+ * index-major: z0 z1 z2 per index). */
+int bsa_turb_draws(bsa_ctx *ctx, int64_t n, uint64_t seed, uint64_t call, uint64_t first_index,
+                   uint64_t *raw4n, double *z3n);
+/* One Woosh over host arrays of length n: alt += turbalt, lat +=
+ * degrees(turblat / Rearth), lon += degrees(turblon / Rearth / coslat) with
+ * turblat / turblon the draws rotated by trk [deg]; coslat as traf.coslat
+ * (traffic.py:482).  hf / hw / valt: the unit normals to apply (all three), or
+ * all NULL: aircraft i takes the draw of (seed, call, i).  lat / lon / alt are
+ * updated in place. */
+int bsa_turb_apply(bsa_ctx *ctx, int64_t n, double dt, const double *sd3, const double *hf, const double *hw,
+                   const double *valt, uint64_t seed, uint64_t call, const double *trk, const double *coslat,
+                   double *lat, double *lon, double *alt);
+/* Woosh as the last stage of every resident step (off by default;
+ * traffic.py:416): after the step's position update, on this rank's rows, with
+ * dt = simdt, the post-step trk and the coslat UpdatePosition left; an
+ * aircraft's index is its current one (bsa_sim_row_ids; after bsa_sim_delete the
+ * compacted one).  The host keeps the call number: 0 at bsa_sim_init, + 1 per
+ * step while on.  While on, the step prepares no records for the next detect
+ * and keeps no tile-pair list on one rank; each detect makes its records from
+ * the perturbed state.  Exact through aborted and re-run
+ * batches.  Several ranks: every rank calls it alike.  sd3 is checked also
+ * when on = 0. */
+int bsa_sim_set_turbulence(bsa_ctx *ctx, int on, const double *sd3, uint64_t seed);
+/* The call number of the next step's draws: set from *set_to when not NULL
+ * (>= 0; continuing another sim's stream), then stored to *call when not NULL. */
+int bsa_sim_turb_call(bsa_ctx *ctx, int64_t *call, const int64_t *set_to);
 /* This rank's rows (bsa_sim_row_ids) of the FMS state, iactwp and the
  * autopilot's targets into full-n host arrays, the clock and the number of
  * ticks since bsa_sim_set_fms; any pointer may be NULL. */

@@ -16,6 +16,9 @@ and outputs as small ``.npz`` files under ``tests/golden/``:
                          (not ``kin_*``: the tests over that pattern hand a
                          fixture's wind on as two scalars)
                          (``--wind3d-only`` writes only these)
+* ``turb_woosh300.npz`` -- ``Turbulence.Woosh`` (turbulence.py:24-46) for two sd settings with the
+                         unit normals it drew, and ``philox_raw.npz``, numpy's Philox4x64-10
+                         words (``--turb-only`` writes only these)
 * ``asas_<case>.npz``  --``ASAS.update``'s bookkeeping + ``ResumeNav``
                          (asas.py:409-504) over a few CD calls, run by the
                          reference's own ``ASAS.update`` on a stand-in ``bs.traf``
@@ -534,6 +537,68 @@ def run_wind3d_all():
     run_wind3d('n5', f['n5'], 2000, 93)
     run_wind3d('n67', f['n67'], 500, 94)
     run_kin_wind3d('wind1500', 1500, 95, 0.05, f['n5'])
+
+
+def run_turb(name, n, seed, dt=0.05):
+    """Turbulence.Woosh (turbulence.py:24-46) by the reference's own object on a stand-in
+    bs.traf, for two sd settings; the unit normals it consumed are recorded by re-seeding
+    numpy and drawing the same three arrays with scale 1.  Also philox_raw.npz: numpy's
+    Philox4x64-10 words for 64 (counter, key) cases, the pin of tests/turb_np.py's generator."""
+    import bluesky as bs
+    from bluesky.traffic.turbulence import Turbulence
+    from tests import turb_np
+    rng = np.random.RandomState(seed)
+    lat = rng.uniform(-80.0, 80.0, n)
+    lat[:2] = [80.0, -80.0]
+    lon = rng.uniform(-180.0, 180.0, n)
+    alt = rng.uniform(0.0, 12000.0, n)
+    trk = rng.uniform(0.0, 360.0, n)
+    trk[2] = 0.0
+    coslat = np.cos(np.deg2rad(lat))     # traffic.py:482
+    out = dict(dt=dt, lat=lat, lon=lon, alt=alt, trk=trk, coslat=coslat)
+    old = getattr(bs, 'traf', None)
+    try:
+        for q, sd in enumerate(([0, 0.1, 0.1], [1, 2, 0.5])):
+            bs.traf = types.SimpleNamespace(ntraf=n, lat=lat.copy(), lon=lon.copy(), alt=alt.copy(),
+                                            trk=trk.copy(), coslat=coslat.copy())
+            tb = Turbulence()
+            tb.SetStandards(sd)
+            tb.SetNoise(True)
+            np.random.seed(seed + 1 + q)
+            tb.Woosh(dt)
+            np.random.seed(seed + 1 + q)
+            z = np.stack([np.random.normal(0, 1, n) for _ in range(3)], axis=1)
+            np.random.seed(seed + 1 + q)     # the scaled draws follow from the unit ones, bitwise
+            for k in range(3):
+                assert np.array_equal(np.random.normal(0, tb.sd[k] * np.sqrt(dt), n), (tb.sd[k] * np.sqrt(dt)) * z[:, k])
+            assert np.array_equal(tb.sd, turb_np.clamp_sd(sd))
+            h = turb_np.woosh_apply(z, dt, sd, trk, coslat, lat, lon, alt)
+            ref = (bs.traf.lat, bs.traf.lon, bs.traf.alt)
+            for a, b, k in zip(h, ref, ('lat', 'lon', 'alt')):
+                assert np.array_equal(a, b), 'helper != reference Woosh %s sd%d' % (k, q)
+            out.update({'sd%d' % q: np.array(sd, dtype=np.float64), 'z%d' % q: z, 'out_lat%d' % q: ref[0],
+                        'out_lon%d' % q: ref[1], 'out_alt%d' % q: ref[2]})
+    finally:
+        bs.traf = old
+    np.savez_compressed(os.path.join(OUT, 'turb_%s.npz' % name), **out)
+    # numpy's Philox: 64 (counter, key) cases, among them carries into the second and the third word
+    M = (1 << 64) - 1
+    ctr = [[int(x) for x in rng.randint(0, 1 << 62, 4)] for _ in range(64)]
+    key = [[int(x) for x in rng.randint(0, 1 << 62, 2)] for _ in range(64)]
+    ctr[0], key[0] = [0, 0, 0, 0], [0, 0]
+    ctr[1], key[1] = [M, 3, 0, 0], [1, 0]          # + 1 carries into word 1
+    ctr[2], key[2] = [M, M, 4, 0], [1, 2]          # ... and into word 2
+    ctr[3], key[3] = [M - 1, 5, 0, 0], [7, 0]      # the second block carries
+    for i in range(4, 20):
+        ctr[i], key[i] = [i - 4, i % 3, 0, 0], [i % 2, 0]   # the shape of the device's counters
+    ctr, key = np.array(ctr, dtype=np.uint64), np.array(key, dtype=np.uint64)
+    raw = np.stack([np.random.Philox(counter=c, key=k).random_raw(8) for c, k in zip(ctr, key)])
+    for c, k, r in zip(ctr, key, raw):
+        c1 = turb_np.numpy_counter(c)
+        assert list(r[:4]) == list(turb_np.philox4x64_10(c1, k)), 'helper Philox != numpy'
+        assert list(r[4:]) == list(turb_np.philox4x64_10(turb_np.numpy_counter(c1), k)), 'helper Philox != numpy'
+    np.savez_compressed(os.path.join(OUT, 'philox_raw.npz'), counter=ctr, key=key, raw=raw)
+    print('turb_%-16s N=%5d dt=%g; philox_raw: %d cases' % (name, n, dt, len(ctr)))
 
 
 def run_limits(name, n, seed):
@@ -1728,6 +1793,9 @@ def main():
     if '--wind3d-only' in sys.argv:
         run_wind3d_all()
         return
+    if '--turb-only' in sys.argv:
+        run_turb('woosh300', 300, 97)
+        return
     if '--geo-only' in sys.argv:
         for case in geo_cases():
             run_geo(*case)
@@ -1759,6 +1827,7 @@ def main():
     run_fms_flight('flight64', 64, 79)
     run_recover('recover2000', 2000, 81)
     run_recover_flight('recover_flight', 48, 83)
+    run_turb('woosh300', 300, 97)
     for case in geo_cases():
         run_geo(*case)
 
