@@ -247,6 +247,57 @@ SIGNATURES.update({
     'bsa_sim_turb_call': (ctypes.c_int, [_vp, _c_i64p, _c_i64p]),
 })
 
+AREA_TYPES = {'LINE': 0, 'BOX': 1, 'CIRCLE': 2, 'POLY': 3}
+AREA_NOCULL = 1
+AREA_SHAPES_MAX = 1024
+AREA_VERTS_MAX = 65536
+
+
+class AreaShape(ctypes.Structure):
+    """bsa_area_shape (include/bsaccel.h)."""
+    _fields_ = [('type', ctypes.c_int32), ('nvert', ctypes.c_int32), ('voff', ctypes.c_int64),
+                ('top', ctypes.c_double), ('bottom', ctypes.c_double), ('c', ctypes.c_double * 4),
+                ('blat', ctypes.c_double * 2), ('blon', ctypes.c_double * 2)]
+
+
+def area_table(areas):
+    """(AreaShape array, vertices (nvert, 2) fp64) of ``areas``: a sequence of
+    ``(type, coordinates, top, bottom)`` with the reference's coordinate lists (areafilter.py:15-24):
+    BOX lat0 lon0 lat1 lon1; CIRCLE clat clon r [NM]; POLY* lat lon lat lon ...; LINE anything."""
+    tab = (AreaShape * max(1, len(areas)))()
+    verts = []
+    nv = 0
+    for k, (typ, coords, top, bottom) in enumerate(areas):
+        t = 'POLY' if str(typ)[:4] == 'POLY' else str(typ)
+        if t not in AREA_TYPES:
+            raise ValueError('unknown area type %r' % (typ,))
+        sh = tab[k]
+        sh.type, sh.top, sh.bottom = AREA_TYPES[t], float(top), float(bottom)
+        co = f64(coords).ravel()
+        need = {'BOX': 4, 'CIRCLE': 3}.get(t, 0)
+        if len(co) < need:
+            raise ValueError('%s needs %d coordinates' % (t, need))
+        for q in range(need):
+            sh.c[q] = co[q]
+        if t == 'POLY':
+            v = co[:2 * (len(co) // 2)].reshape(-1, 2)   # areafilter.py:97
+            sh.nvert, sh.voff = len(v), nv
+            verts.append(v)
+            nv += len(v)
+    verts = np.ascontiguousarray(np.concatenate(verts)) if verts else np.zeros((0, 2))
+    return tab, verts
+
+
+SIGNATURES.update({
+    'bsa_area_inside': (ctypes.c_int, [_vp, ctypes.c_int64, _c_dp, _c_dp, _c_dp, ctypes.c_int64,
+                                       ctypes.POINTER(AreaShape), ctypes.c_int64, _c_dp, ctypes.c_int,
+                                       _c_u64p, _c_u64p]),
+    'bsa_sim_set_areas': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.POINTER(AreaShape), ctypes.c_int64, _c_dp]),
+    'bsa_sim_set_sectors': (ctypes.c_int, [_vp, ctypes.c_int64, _c_i32p, ctypes.c_int64]),
+    'bsa_sim_sectors_poll': (ctypes.c_int, [_vp] + [_c_u64p] * 5 + [_c_i64p, _c_i64p, _c_u64p, _c_u64p]),
+    'bsa_sim_sectors_deleted': (ctypes.c_int, [_vp, ctypes.c_int64, _c_i64p, _c_u64p, _c_i64p]),
+})
+
 UNIQUE_ID_BYTES = 128
 
 _lib = None
@@ -860,6 +911,62 @@ class Context:
         self.check(self.lib.bsa_sim_turb_call(self.h, ctypes.byref(out), new), 'bsa_sim_turb_call')
         return out.value
 
+    # ---------------------------------------------------------------- area filter
+    def area_inside(self, areas, lat, lon, alt, nocull=False):
+        """bsa_area_inside: ``areas`` as for ``area_table``.  Returns (inside (len(areas), n) bool,
+        counts (len(areas),) uint64) from one launch."""
+        lat, lon, alt = f64(lat).ravel(), f64(lon).ravel(), f64(alt).ravel()
+        n, ns = len(lat), len(areas)
+        if len(lon) != n or len(alt) != n:
+            raise ValueError('area filter arrays differ in length')
+        tab, verts = area_table(areas)
+        W = (ns + 63) // 64
+        words = np.zeros((W, n), dtype=np.uint64)
+        counts = np.zeros(ns, dtype=np.uint64)
+        self.check(self.lib.bsa_area_inside(self.h, n, ptr(lat), ptr(lon), ptr(alt), ns, tab, len(verts),
+                                            ptr(verts), AREA_NOCULL if nocull else 0,
+                                            ptr(words, _c_u64p), ptr(counts, _c_u64p)), 'bsa_area_inside')
+        return area_unpack(words, ns), counts
+
+    def sim_set_areas(self, areas):
+        """bsa_sim_set_areas: the resident sim's area table (``areas`` as for ``area_table``; empty clears it)."""
+        tab, verts = area_table(areas)
+        self.check(self.lib.bsa_sim_set_areas(self.h, len(areas), tab, len(verts), ptr(verts)), 'bsa_sim_set_areas')
+
+    def sim_set_sectors(self, shape_idx, every=1):
+        """bsa_sim_set_sectors: sector k = shape ``shape_idx[k]`` of the table, a pass every ``every`` steps."""
+        idx = np.ascontiguousarray(shape_idx, dtype=np.int32).ravel()
+        self.check(self.lib.bsa_sim_set_sectors(self.h, len(idx), ptr(idx, _c_i32p), int(every)), 'bsa_sim_set_sectors')
+        self._nsect = len(idx)
+
+    def sim_sectors_poll(self, masks=False):
+        """bsa_sim_sectors_poll: dict of count / arrived / left / arrived_total / left_total (per sector,
+        uint64), step, updates; with ``masks`` also cur / prev (full-n uint64, this rank's rows filled)."""
+        ns = getattr(self, '_nsect', 0)
+        out = {k: np.zeros(ns, dtype=np.uint64) for k in ('count', 'arrived', 'left', 'arrived_total', 'left_total')}
+        step, upd = ctypes.c_int64(0), ctypes.c_int64(0)
+        cur = np.zeros(self.n, dtype=np.uint64) if masks else None
+        prev = np.zeros(self.n, dtype=np.uint64) if masks else None
+        self.check(self.lib.bsa_sim_sectors_poll(self.h, *[ptr(out[k], _c_u64p) for k in
+                                                           ('count', 'arrived', 'left', 'arrived_total', 'left_total')],
+                                                 ctypes.byref(step), ctypes.byref(upd), ptr(cur, _c_u64p),
+                                                 ptr(prev, _c_u64p)), 'bsa_sim_sectors_poll')
+        out.update(step=step.value, updates=upd.value)
+        if masks:
+            out.update(cur=cur, prev=prev)
+        return out
+
+    def sim_sectors_deleted(self):
+        """bsa_sim_sectors_deleted: (positions in the last delete's index list, mask words) of this rank's
+        deleted aircraft, read once."""
+        cnt = ctypes.c_int64(0)
+        self.check(self.lib.bsa_sim_sectors_deleted(self.h, 0, None, None, ctypes.byref(cnt)), 'bsa_sim_sectors_deleted')
+        pos, words = np.zeros(cnt.value, dtype=np.int64), np.zeros(cnt.value, dtype=np.uint64)
+        if cnt.value:
+            self.check(self.lib.bsa_sim_sectors_deleted(self.h, cnt.value, ptr(pos, _c_i64p), ptr(words, _c_u64p),
+                                                        ctypes.byref(cnt)), 'bsa_sim_sectors_deleted')
+        return pos, words
+
     def sim_read_dropcount(self):
         """bsa_sim_read_dropcount: resopairs ResumeNav dropped per ownship in the last CD
         call (this rank's rows of a full-n int32 array, other rows 0)."""
@@ -1146,6 +1253,15 @@ class Context:
 
 
 _default = {}
+
+
+def area_unpack(words, nshapes):
+    """Mask words (W, n) uint64 -> inside (nshapes, n) bool: bit s % 64 of word s // 64."""
+    words = np.asarray(words, dtype=np.uint64)
+    s = np.arange(nshapes)
+    if words.shape[0] == 0:
+        return np.zeros((nshapes, words.shape[1]), dtype=bool)
+    return ((words[s // 64] >> (s % 64).astype(np.uint64)[:, None]) & np.uint64(1)).astype(bool)
 
 
 def default_context(device=0):

@@ -428,6 +428,24 @@ struct Ctx {
   unsigned long long turb_seed = 0;
   int64_t turb_call = 0;
 
+  // The area filter (bsa_area.hip).  area_stage: bsa_area_inside's points, masks, counts and table
+  DevBuf area_stage;
+  // Sector occupancy in the resident step (bsa_sim_set_areas / _set_sectors): the packed area
+  // table (host) and its vertices (device); the sectors' shapes in sector order (sect_tab), their counts
+  // (sect_cnt, kSect* words), the mask word of every aircraft at the last update (s_scur) and at the one before
+  // (s_sprev), both per-aircraft arrays (kSimArrays).  sect_ctr: steps since bsa_sim_set_sectors, the host's,
+  // replayed after an abort; sect_gone: deleted aircraft's words until the next bsa_sim_sectors_deleted
+  std::vector<bsa_area_shape> area_tab;
+  DevBuf area_verts, sect_tab, sect_cnt, s_scur, s_sprev;
+  bool sim_sect = false;
+  std::vector<int32_t> sect_idx;
+  int64_t sect_every = 1, sect_ctr = 0;
+  struct SectGone {
+    int64_t pos;
+    unsigned long long word;
+  };
+  std::vector<SectGone> sect_gone;
+
   // standalone geo matrices (bsa_geo.hip)
   DevBuf geo_in, geo_pts, geo_out;
   hipEvent_t geo_ev[2] = {nullptr, nullptr};
@@ -502,7 +520,7 @@ inline void *ptr_at(const void *strct, int k) { return ((void *const *)strct)[k]
 // it (bsa_traffic.hip: per_aircraft), bsa_sim_init allocates its kSimAlways rows
 // guard: kSimAlways allocated by bsa_sim_init; kSimDetect the last detect's per-row outputs (the detect's to
 // allocate); kSimOnUse once allocated (the reso lists); the others while Ctx::sim_<switch> is on
-enum SimGuard { kSimAlways, kSimDetect, kSimOnUse, kSimLimits, kSimPerf, kSimForces, kSimFms, kSimAtmos };
+enum SimGuard { kSimAlways, kSimDetect, kSimOnUse, kSimLimits, kSimPerf, kSimForces, kSimFms, kSimAtmos, kSimSectors };
 struct SimArray {
   BufRef buf;
   int esz, count;  // element size; sub-arrays of length n in the buffer
@@ -536,6 +554,7 @@ inline const SimArray kSimArrays[] = {
     {{&Ctx::s_fused}, 8, 1, false, kSimForces},     {{&Ctx::s_fpend}, 8, 1, false, kSimForces},
     {{&Ctx::s_fmsr}, 8, kFmsReals, false, kSimFms}, {{&Ctx::s_fmsf}, 1, kFmsFlags, false, kSimFms},
     {{&Ctx::s_fmsi}, 4, kFmsInts, false, kSimFms},   {{&Ctx::s_dropcnt}, 4, 1, false, kSimAlways},
+    {{&Ctx::s_scur}, 8, 1, false, kSimSectors},      {{&Ctx::s_sprev}, 8, 1, false, kSimSectors},
 };
 // is the array part of the sim now (to be carried through a delete / create)?
 inline bool sim_array_on(Ctx *c, const SimArray &a) {
@@ -546,6 +565,7 @@ inline bool sim_array_on(Ctx *c, const SimArray &a) {
     case kSimForces: return c->sim_forces;
     case kSimFms: return c->sim_fms;
     case kSimAtmos: return c->sim_atmos;
+    case kSimSectors: return c->sim_sect;
     default: return true;
   }
 }
@@ -640,6 +660,15 @@ WindField wind_field_pa(const Ctx *c);
 // enqueued after the step's K4' on the arrays it wrote
 int turb_sim_launch(Ctx *c, int64_t rb, int64_t re, const unsigned *sticky, const double *trk, double *lat,
                     double *lon, double *alt);
+
+// Sector occupancy (bsa_area.hip): sect_step after the last stage of every step while Ctx::sim_sect (the step
+// counter, and the pass when it reaches a multiple of the cadence); sect_note_deleted by bsa_sim_delete before
+// anything moves; sect_off forgets the sectors.  sim_download_rows (bsa_sim.hip): this rank's rows of up to two
+// device arrays into full-n host arrays in index order (a NULL host array is left out)
+int sect_step(Ctx *c);
+int sect_note_deleted(Ctx *c, int64_t k, const int64_t *idx);
+void sect_off(Ctx *c);
+int sim_download_rows(Ctx *c, const void *dev0, void *host0, const void *dev1, void *host1, int esz);
 
 // OpenAP drag / thrust / fuel flow (bsa_perf.hip).  forces_consts: Ctx::f_const
 // filled (once).  forces_sim_launch: k_sim_forces of the step about to be

@@ -484,10 +484,11 @@ struct BatchBase {
   double fms_simt, fms_t0;  // the FMS clock
   int64_t fms_ticks;
   int64_t turb_call;  // the draws' call number
+  int64_t sect_ctr;   // the sector pass's step counter
 };
 static int batch_begin(Ctx *c, bool kin, BatchBase *b) {
   *b = BatchBase{kin, c->sim_steps, c->sim_cd_calls, c->sim_gs_derivable, c->fms_simt, c->fms_t0, c->fms_ticks,
-                 c->turb_call};
+                 c->turb_call, c->sect_ctr};
   BSA_HIP(c, hipMemsetAsync((char *)c->sim_ctl.p + kSimCtlSticky, 0, 40, c->stream));  // sticky, steps_done, demands, stale
   return 0;
 }
@@ -528,6 +529,9 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long lon
   // the draws are a pure function of (seed, call, index): the completed steps took one call number each, the
   // aborted step's k_sim_turb returned behind the sticky word -- nothing to undo
   if (base.kin && c->sim_turb) c->turb_call = base.turb_call + done;
+  // the sector pass only reads state: the completed steps' updates are counted, the aborted step's pass returned
+  // behind the sticky word like every later one, so the re-run counts each update once
+  if (base.kin && c->sim_sect) c->sect_ctr = base.sect_ctr + done;
   // the last detect's counters: every detect after the abort ran on the same, unchanged state
   Counters h;
   BSA_HIP(c, hipMemcpy(&h, c->counters.p, sizeof(h), hipMemcpyDeviceToHost));
@@ -568,6 +572,12 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long lon
   if (worst > c->cand_cap / kCandShards)
     c->cand_cap = std::max(2 * c->cand_cap, (unsigned long long)kCandShards * (worst + worst / 4 + 1024));
   return 0;
+}
+
+int sim_download_rows(Ctx *c, const void *dev0, void *host0, const void *dev1, void *host1, int esz) {
+  HomeBatch down(c, false, c->sim_rb, c->sim_re);
+  if ((host0 && down.add(dev0, nullptr, host0, esz)) || (host1 && down.add(dev1, nullptr, host1, esz))) return -1;
+  return down.run();
 }
 
 static int check_params(Ctx *c, const bsa_sim_params *p) {
@@ -735,6 +745,7 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
     if (turb_sim_launch(c, c->sim_rb, c->sim_re, d.sticky, d.trk, d.lat, d.lon, d.alt)) return -1;
     c->turb_call++;
   }
+  if (c->sim_sect && sect_step(c)) return -1;  // sector occupancy: reads what the step left (sectorcount.py:53-79)
   if (sp.prep)
     c->prep.keep({pa.rpz, pa.hpz, pa.tla, (double)pa.mid, c->n});
   else
@@ -774,6 +785,8 @@ int bsa_sim_init(bsa_ctx *cc, int64_t n, const bsa_sim_state *s, const bsa_sim_p
   c->sim_noreso = c->sim_resooff = false;  // empty NORESO / RESOOFF lists
   c->sim_atmos = c->sim_limits = c->sim_perf = c->sim_forces = c->sim_fms = c->sim_recovery = c->sim_turb = false;
   c->turb_call = 0;
+  bsa::sect_off(c);
+  c->area_tab.clear();
   // every always-present array (kSimArrays); the all-gathered ones hold nranks
   // x rpr entries (in-place all-gather).  Zero unless a state field fills it:
   // asas.vs, asase / asasn, inactive, traf.ax, no ResumeNav drops

@@ -421,6 +421,7 @@ int bsa_sim_delete(bsa_ctx *cc, int64_t k, const int64_t *idx) {
   if (d.empty()) return 0;
   BSA_HIP(c, hipSetDevice(c->device));
   BSA_HIP(c, hipStreamSynchronize(c->stream));
+  if (bsa::sect_note_deleted(c, k, idx)) return -1;  // sector occupancy: they count as left
   bsa::Multi mu;
   if (bsa::multi_begin(c, mu)) return -1;
   // old index -> new index (np.delete keeps the order of the rest), -1 = deleted

@@ -134,3 +134,17 @@ def merge_rank_pairs(parts, rows=None):
             full[ids] = v
             out[k] = full
     return out
+
+
+def merge_sectors(parts):
+    """``ResidentSim.sectors()`` of every rank -> one answer: counts and totals summed, the
+    lists concatenated and sorted (each aircraft is one rank's row)."""
+    out = {}
+    for name in parts[0]:
+        d = dict(step=parts[0][name]['step'])
+        for k in ('count', 'arrived_total', 'left_total'):
+            d[k] = sum(p[name][k] for p in parts)
+        for k in ('arrived', 'left', 'left_deleted'):
+            d[k] = sorted(x for p in parts for x in p[name][k])
+        out[name] = d
+    return out

@@ -197,15 +197,94 @@ class ResidentSim:
         rows, and ``simt``, ``t0``, ``ticks`` (bsa_sim_read_fms)."""
         return self.ctx.sim_read_fms()
 
-    def create(self, state):
+    def create(self, state, ids=None):
         """Append aircraft (Traffic.create; ``state`` as ``initial_state`` returns,
-        m long each): indices n..n+m-1 (bsa_sim_create; collective with several ranks)."""
+        m long each): indices n..n+m-1 (bsa_sim_create; collective with several ranks).
+        ``ids``: their callsigns, when ``set_sectors`` was given ids."""
+        if getattr(self, 'ids', None) is not None:
+            if ids is None or len(ids) != len(state['lat']):
+                raise ValueError('create: one id per new aircraft (set_sectors was given ids)')
+            self.ids = self.ids + list(ids)
         self.ctx.sim_create(state)
 
     def delete(self, idx):
         """Remove aircraft ``idx`` (Traffic.delete: the rest shift down in order),
-        keeping the callsign-keyed ASAS bookkeeping of the others (bsa_sim_delete)."""
-        self.ctx.sim_delete(idx)
+        keeping the callsign-keyed ASAS bookkeeping of the others (bsa_sim_delete).
+        With sectors on, those that were inside a sector are reported as ``left`` by
+        the next ``sectors()``."""
+        d = np.unique(np.asarray(idx, dtype=np.int64).ravel())
+        self.ctx.sim_delete(d)
+        if getattr(self, '_sect_names', None):
+            pos, words = self.ctx.sim_sectors_deleted()
+            ids = getattr(self, 'ids', None)
+            for q, w in zip(pos, words):
+                who = ids[d[q]] if ids is not None else int(d[q])
+                self._sect_gone.append((who, int(w)))
+        if getattr(self, 'ids', None) is not None:
+            gone = set(int(x) for x in d)
+            self.ids = [x for k, x in enumerate(self.ids) if k not in gone]
+
+    def set_areas(self, areas):
+        """The sim's area table (bsa_sim_set_areas): ``areas`` maps a name to ``(type, coordinates,
+        top, bottom)`` -- ``bluesky_amd.areafilter.areas`` is such a dict.  Forgets the sectors.
+        Sharded: every rank calls it alike."""
+        self._area_names = list(areas)
+        self._sect_names, self._sect_gone = [], []
+        self.ctx.sim_set_areas([areas[k] for k in self._area_names])
+
+    def set_sectors(self, names, every=1, ids=None):
+        """Sector occupancy inside the step (plugins/sectorcount.py:53-96; bsa_sim_set_sectors):
+        the areas ``names`` (at most 64, of ``set_areas``) are tested every ``every`` steps --
+        ``every = max(1, round(update_interval / simdt))`` -- after the step's last stage; the
+        masks are seeded at the current state, as SECTORCOUNT ADD does.  ``ids``: the callsigns
+        by aircraft index; ``sectors()`` then lists callsigns, and ``create`` wants the new
+        ones.  ``names = []`` switches it off.  Sharded: every rank calls it alike."""
+        tab = getattr(self, '_area_names', [])
+        missing = [k for k in names if k not in tab]
+        if missing:
+            raise ValueError('set_sectors: no area %r (set_areas)' % (missing[0],))
+        if ids is not None and len(ids) != self.ctx.n:
+            raise ValueError('set_sectors: one id per aircraft')
+        self.ctx.sim_set_sectors([tab.index(k) for k in names], every)
+        self._sect_names, self._sect_gone = list(names), []
+        self._sect_gone_total = np.zeros(len(names), dtype=np.int64)
+        self.ids = None if ids is None else list(ids)
+
+    def sectors(self, masks=False):
+        """The LAST sector update of this rank's rows (bsa_sim_sectors_poll): per sector name a dict
+        of ``count``, ``arrived`` and ``left`` (aircraft indices, ascending; callsigns, sorted, with
+        ids), ``arrived_total`` / ``left_total`` over every update since ``set_sectors`` (also those
+        inside a batch) and ``step``, the step count of that update (0: the seeding pass).  Aircraft
+        deleted since the last call that were inside are listed in ``left_deleted`` (their
+        index when deleted, or callsign), count in ``left_total`` and, with ids, are part of
+        ``left`` -- once.  ``masks``: also ``inside`` / ``inside_before``, bool per row of
+        ``row_ids()``.  Several ranks: ``dist.merge_sectors`` sums the ranks' answers."""
+        names = getattr(self, '_sect_names', None)
+        if not names:
+            raise ValueError('sectors: set_sectors first')
+        r = self.ctx.sim_sectors_poll(masks=True)
+        rows = self.row_ids()
+        cur, prev = r['cur'][rows], r['prev'][rows]
+        ids = getattr(self, 'ids', None)
+        gone, self._sect_gone = self._sect_gone, []
+        out = {}
+        for k, name in enumerate(names):
+            bit = np.uint64(1) << np.uint64(k)
+            c, p = (cur & bit) != 0, (prev & bit) != 0
+            arrived, left = rows[c & ~p], rows[p & ~c]
+            deleted = [who for who, w in gone if (w >> k) & 1]
+            self._sect_gone_total[k] += len(deleted)
+            if ids is not None:
+                arrived = sorted(ids[i] for i in arrived)
+                left = sorted([ids[i] for i in left] + deleted)
+            else:
+                arrived, left = [int(i) for i in arrived], [int(i) for i in left]
+            out[name] = dict(count=int(r['count'][k]), arrived=arrived, left=left, left_deleted=sorted(deleted),
+                             arrived_total=int(r['arrived_total'][k]),
+                             left_total=int(r['left_total'][k]) + int(self._sect_gone_total[k]), step=r['step'])
+            if masks:
+                out[name].update(inside=c, inside_before=p)
+        return out
 
     def read(self):
         return self.ctx.sim_read()

@@ -22,6 +22,10 @@
  *       bluesky/traffic/windfield.py:158-202         Windfield.getdata, 3-D field (per position)
  *   bsa_turb_draws, bsa_turb_apply, bsa_sim_set_turbulence
  *       bluesky/traffic/turbulence.py:24-46          Turbulence.Woosh (build-defined draws)
+ *   bsa_area_inside, bsa_sim_set_areas
+ *       bluesky/tools/areafilter.py:29-35,61-104     checkInside of Box / Circle / Poly / Line
+ *   bsa_sim_set_sectors, bsa_sim_sectors_poll, bsa_sim_sectors_deleted
+ *       plugins/sectorcount.py:53-96                 per-sector occupancy, arrived / left
  *   bsa_qdrdist
  *       bluesky/tools/geo.py:110-162,347-363         qdrdist_matrix / kwikqdrdist_matrix, materialised
  *   bsa_sim_set_limits
@@ -637,6 +641,89 @@ int bsa_sim_set_turbulence(bsa_ctx *ctx, int on, const double *sd3, uint64_t see
 /* The call number of the next step's draws: set from *set_to when not NULL
  * (>= 0; continuing another sim's stream), then stored to *call when not NULL. */
 int bsa_sim_turb_call(bsa_ctx *ctx, int64_t *call, const int64_t *set_to);
+/* ---------------------------------------------------------------- area filter
+ * areafilter.checkInside (bluesky/tools/areafilter.py:29-35) for a table of
+ * shapes in one launch.  A shape (areafilter.py:52-104):
+ *   BSA_AREA_LINE    never inside
+ *   BSA_AREA_BOX     c = lat, lon, lat, lon of two opposite corners (any order):
+ *                    lat0 <= lat <= lat1 & lon0 <= lon <= lon1, inclusive
+ *   BSA_AREA_CIRCLE  c = clat, clon, r [NM]: geo.kwikdist(clat, clon, lat, lon) <= r
+ *                    (geo.py:288-305, its operation order)
+ *   BSA_AREA_POLY    nvert ring vertices from vertex voff of `verts` ((lat, lon)
+ *                    pairs, fp64): matplotlib's Path.contains_points with x = lat,
+ *                    y = lon -- an even-odd crossing count over the ring closed from
+ *                    its last vertex to its first; for each edge (x0,y0)->(x1,y1):
+ *                      f0 = (y0 >= y); f1 = (y1 >= y)
+ *                      if f0 != f1 and (((y1 - y)*(x0 - x1) >= (x1 - x)*(y0 - y1)) == f1): inside ^= 1
+ *                    A ring of fewer than 3 vertices holds nothing, and a point
+ *                    with a non-finite lat or lon is in no polygon.
+ * and bottom <= alt <= top for all but LINE (top / bottom in either order:
+ * areafilter.py:64-65).  fp64, no contraction.  blat / blon are the library's
+ * (cull bounds); what the caller writes there is ignored. */
+#define BSA_AREA_LINE   0
+#define BSA_AREA_BOX    1
+#define BSA_AREA_CIRCLE 2
+#define BSA_AREA_POLY   3
+typedef struct bsa_area_shape {
+  int32_t type;
+  int32_t nvert; /* POLY: >= 1 */
+  int64_t voff;  /* POLY: first vertex */
+  double top, bottom;
+  double c[4];
+  double blat[2], blon[2];
+} bsa_area_shape;
+#define BSA_AREA_NOCULL 1 /* test aid: every shape for every point (no wave-level cull; also env BSA_AREA_CULL=0);
+                             results are identical, only the speed differs */
+/* n points (host arrays) against nshapes shapes (<= 1024) over nvert vertices
+ * (verts: 2 nvert doubles, <= 65536 vertices).  out_words: W = ceil(nshapes /
+ * 64) arrays of n 64-bit words, word-major: bit s % 64 of out_words[(s / 64) * n
+ * + i] = point i is inside shape s.  counts (nshapes words, may be NULL): points
+ * inside each shape.  Errors (bsa_last_error): NULL arrays, n < 0, a table
+ * beyond the limits, an unknown type, a polygon of fewer than 1 vertex, of a
+ * vertex range outside the array or of a non-finite vertex, an unknown flag. */
+int bsa_area_inside(bsa_ctx *ctx, int64_t n, const double *lat, const double *lon, const double *alt,
+                    int64_t nshapes, const bsa_area_shape *shapes, int64_t nvert, const double *verts, int flags,
+                    uint64_t *out_words, uint64_t *counts);
+/* ---------------------------------------------------------------- sector occupancy
+ * plugins/sectorcount.py:53-96 inside the resident step (off by default; nothing
+ * is launched while off).  bsa_sim_set_areas uploads the sim's area table
+ * (shapes / verts as for bsa_area_inside, same checks and limits; nshapes = 0
+ * clears it) and forgets the sectors, which name its shapes. */
+int bsa_sim_set_areas(bsa_ctx *ctx, int64_t nshapes, const bsa_area_shape *shapes, int64_t nvert,
+                      const double *verts);
+/* nsect sectors (<= 64: one mask word per aircraft; 0 = off), sector k the
+ * shape shape_idx[k] of the table.  SECTORCOUNT ADD (sectorcount.py:91-96): the
+ * previous masks are seeded with one inside pass at the current state, whose
+ * occupancy the next poll reports with nothing arrived or left.  A step counter
+ * starts at 0 here; after the last stage of each step that brings it to a
+ * multiple of `every` (>= 1; the caller's max(update_interval, simdt) / simdt,
+ * tools/plugin.py:127) the pass runs on this rank's rows: the current masks,
+ * per sector n_tot, arrived = now & ~before, left = before & ~now for this
+ * update and summed (64-bit) since this call; the current masks then become the
+ * previous ones.  The pass only reads simulation state, and it is exact through
+ * aborted and re-run batches (each update counted once).  The mask words are
+ * per-aircraft arrays: bsa_sim_create (new aircraft: 0, outside), bsa_sim_delete
+ * and the re-partition on several ranks carry them.  Several ranks: every rank
+ * calls it alike and counts its own rows; the caller sums. */
+int bsa_sim_set_sectors(bsa_ctx *ctx, int64_t nsect, const int32_t *shape_idx, int64_t every);
+/* The LAST update, this rank's rows.  Per sector (nsect words each, any may be
+ * NULL): n_tot, arrived, left, and arrived_total / left_total since
+ * bsa_sim_set_sectors (every update, also those inside a batch).  *step: the
+ * step count (since bsa_sim_set_sectors) of that update, 0 = the seeding pass;
+ * *updates: how many there were.  cur_words / prev_words (may be NULL): bit k =
+ * inside sector k at the last update / at the one before, this rank's rows of
+ * full-n host arrays in aircraft-index order (bsa_sim_row_ids names the rows;
+ * other entries are left alone). */
+int bsa_sim_sectors_poll(bsa_ctx *ctx, uint64_t *n_tot, uint64_t *arrived, uint64_t *left, uint64_t *arrived_total,
+                         uint64_t *left_total, int64_t *step, int64_t *updates, uint64_t *cur_words,
+                         uint64_t *prev_words);
+/* Aircraft of this rank's rows that bsa_sim_delete removed while sectors were
+ * on ("left by deletion", sectorcount.py's set difference): pos[k] = position in
+ * that call's index list, words[k] = the masks it had.  *count = how many are
+ * pending; they are copied and forgotten when cap >= *count, else left for a
+ * call with room.  Read it after each bsa_sim_delete: positions of two calls
+ * are not told apart. */
+int bsa_sim_sectors_deleted(bsa_ctx *ctx, int64_t cap, int64_t *pos, uint64_t *words, int64_t *count);
 /* This rank's rows (bsa_sim_row_ids) of the FMS state, iactwp and the
  * autopilot's targets into full-n host arrays, the clock and the number of
  * ticks since bsa_sim_set_fms; any pointer may be NULL. */
