@@ -298,6 +298,36 @@ SIGNATURES.update({
     'bsa_sim_sectors_deleted': (ctypes.c_int, [_vp, ctypes.c_int64, _c_i64p, _c_u64p, _c_i64p]),
 })
 
+GEOVEC_GSMIN, GEOVEC_GSMAX, GEOVEC_TRK, GEOVEC_VSMIN, GEOVEC_VSMAX = 1, 2, 4, 8, 16
+GEOVEC_MAX = 256
+GEOVEC_TARGETS = ('selspd', 'ap_trk', 'selvs', 'selalt')
+
+
+class Geovec(ctypes.Structure):
+    """bsa_geovec (include/bsaccel.h)."""
+    _fields_ = [('shape', ctypes.c_int32), ('given', ctypes.c_int32)] + \
+               [(k, ctypes.c_double) for k in ('gsmin', 'gsmax', 'trkmin', 'trkmax', 'vsmin', 'vsmax')]
+
+
+def geovec_rows(rows):
+    """A ``Geovec`` array of ``rows``: such an array already, or a sequence of
+    ``(shape, given, gsmin, gsmax, trkmin, trkmax, vsmin, vsmax)``."""
+    if isinstance(rows, ctypes.Array) and getattr(rows, '_type_', None) is Geovec:
+        return rows, len(rows)
+    tab = (Geovec * max(1, len(rows)))()
+    for k, r in enumerate(rows):
+        tab[k] = Geovec(int(r[0]), int(r[1]), *[float(x) for x in r[2:8]])
+    return tab, len(rows)
+
+
+SIGNATURES.update({
+    'bsa_geovec_apply': (ctypes.c_int, [_vp, ctypes.c_int64] + [_c_dp] * 5 +
+                         [ctypes.c_int64, ctypes.POINTER(AreaShape), ctypes.c_int64, _c_dp,
+                          ctypes.c_int64, ctypes.POINTER(Geovec), ctypes.c_int] + [_c_dp] * 4 + [_c_u64p]),
+    'bsa_sim_set_geovectors': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.POINTER(Geovec), ctypes.c_int64]),
+    'bsa_sim_geovec_stats': (ctypes.c_int, [_vp, _c_i64p, _c_u64p]),
+})
+
 UNIQUE_ID_BYTES = 128
 
 _lib = None
@@ -966,6 +996,39 @@ class Context:
             self.check(self.lib.bsa_sim_sectors_deleted(self.h, cnt.value, ptr(pos, _c_i64p), ptr(words, _c_u64p),
                                                         ctypes.byref(cnt)), 'bsa_sim_sectors_deleted')
         return pos, words
+
+    # ---------------------------------------------------------------- geovectoring
+    def geovec_apply(self, areas, rows, lat, lon, alt, trk, vs, selspd, ap_trk, selvs, selalt, nocull=False,
+                     ngv=None):
+        """bsa_geovec_apply: ``areas`` as for ``area_table``, ``rows`` as for ``geovec_rows`` (row k's
+        ``shape`` indexes ``areas``).  Returns (dict of the four GEOVEC_TARGETS after the call, new
+        arrays; changed (4,) uint64).  The inputs stay as they are."""
+        tr = [f64(x).ravel() for x in (lat, lon, alt, trk, vs)]
+        io = [np.array(f64(x).ravel()) for x in (selspd, ap_trk, selvs, selalt)]
+        n = len(tr[0])
+        if any(len(a) != n for a in tr + io):
+            raise ValueError('geovector arrays differ in length')
+        tab, verts = area_table(areas)
+        gv, m = geovec_rows(rows)
+        changed = np.zeros(4, dtype=np.uint64)
+        self.check(self.lib.bsa_geovec_apply(self.h, n, *[ptr(a) for a in tr], len(areas), tab, len(verts), ptr(verts),
+                                             m if ngv is None else int(ngv), gv, AREA_NOCULL if nocull else 0,
+                                             *[ptr(a) for a in io], ptr(changed, _c_u64p)), 'bsa_geovec_apply')
+        return dict(zip(GEOVEC_TARGETS, io)), changed
+
+    def sim_set_geovectors(self, rows, every=1):
+        """bsa_sim_set_geovectors: ``rows`` as for ``geovec_rows``, ``shape`` an index into the table of
+        ``sim_set_areas``; applied every ``every`` steps; no rows = off."""
+        gv, m = geovec_rows(rows)
+        self.check(self.lib.bsa_sim_set_geovectors(self.h, m, gv, int(every)), 'bsa_sim_set_geovectors')
+
+    def sim_geovec_stats(self):
+        """bsa_sim_geovec_stats: dict of ``applies`` and ``changed`` (GEOVEC_TARGETS -> aircraft changed, this
+        rank's rows, summed over the applications)."""
+        applies = ctypes.c_int64(0)
+        ch = np.zeros(4, dtype=np.uint64)
+        self.check(self.lib.bsa_sim_geovec_stats(self.h, ctypes.byref(applies), ptr(ch, _c_u64p)), 'bsa_sim_geovec_stats')
+        return dict(applies=applies.value, changed={k: int(v) for k, v in zip(GEOVEC_TARGETS, ch)})
 
     def sim_read_dropcount(self):
         """bsa_sim_read_dropcount: resopairs ResumeNav dropped per ownship in the last CD

@@ -21,14 +21,12 @@
 #include <cstdlib>
 #include <unordered_set>
 
-#include "bsa_area_math.h"
+#include "bsa_area_wave.h"
 
 #pragma clang fp contract(off)
 
 namespace bsa {
 
-constexpr int kAreaBlock = 64;  // one wave: the cull and the LDS chunk are the wave's own
-constexpr int kAreaChunk = 64;  // ring vertices in LDS at a time (1 KiB)
 constexpr int kAreaShapesMax = 1024, kAreaVertsMax = 65536;
 
 struct AreaArgs {
@@ -51,21 +49,6 @@ struct AreaArgs {
 constexpr int kSectMax = 64, kSectTot = 0, kSectArr = 64, kSectLeft = 128, kSectArrCum = 192, kSectLeftCum = 256,
               kSectWords = 320;
 
-__device__ __forceinline__ double wave_uniform(double v) {  // (equal on every lane already: tell the compiler)
-  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-// min / max over the wave, NaNs left out (fmin / fmax return the other operand)
-__device__ __forceinline__ double wave_min(double v) {
-  for (int m = 32; m >= 1; m >>= 1) v = fmin(v, __shfl_xor(v, m, 64));
-  return wave_uniform(v);
-}
-__device__ __forceinline__ double wave_max(double v) {
-  for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
-  return wave_uniform(v);
-}
-
 __global__ void k_sect_zero(const unsigned *sticky, unsigned long long *sect) {
   if (*sticky != 0u) return;
   if (threadIdx.x < kSectArrCum) sect[threadIdx.x] = 0ull;
@@ -80,42 +63,15 @@ __global__ __launch_bounds__(kAreaBlock) void k_area_inside(AreaArgs a) {
   // a lane past the end holds a NaN point: inside nothing, and left out of the wave's intervals
   const double nan = __longlong_as_double((long long)kNanBits);
   const double lat = live ? a.lat[h] : nan, lon = live ? a.lon[h] : nan, alt = live ? a.alt[h] : nan;
-  const double lat0 = wave_min(lat), lat1 = wave_max(lat), lon0 = wave_min(lon), lon1 = wave_max(lon),
-               alt0 = wave_min(alt), alt1 = wave_max(alt);
+  const WaveBounds wb = wave_bounds(lat, lon, alt);
   const bool pt_ok = area::poly_point_ok(lat, lon);
   unsigned long long word = 0ull;
   for (int s = 0; s < a.nshapes; ++s) {
     const area::Shape sh = a.shapes[s];  // (the same address on every lane)
-    // no comparison with a NaN interval end is true: such a wave skips nothing
-    const bool skip = !a.nocull && (alt1 < sh.bottom || alt0 > sh.top || lat1 < sh.blat[0] || lat0 > sh.blat[1] ||
-                                    lon1 < sh.blon[0] || lon0 > sh.blon[1]);
+    const bool skip = !a.nocull && wave_skips(wb, sh);
     bool in = false;
     if (!skip) {
-      if (sh.type == BSA_AREA_BOX) {
-        in = area::box_inside(sh, lat, lon, alt);
-      } else if (sh.type == BSA_AREA_CIRCLE) {
-        in = area::circle_inside(sh, lat, lon, alt);
-      } else if (sh.type == BSA_AREA_POLY && sh.nvert >= area::kPolyMinVerts) {
-        const area::Vert *r = a.verts + sh.voff;
-        const int nv = sh.nvert;
-        double x0 = r[nv - 1].x, y0 = r[nv - 1].y;  // the closing edge first: last vertex -> first
-        bool f0 = y0 >= lon;
-        for (int base = 0; base < nv; base += kAreaChunk) {
-          const int m = nv - base < kAreaChunk ? nv - base : kAreaChunk;
-          __syncthreads();  // (the chunk before has been read)
-          if (lane < m) ring[lane] = r[base + lane];
-          __syncthreads();
-          for (int k = 0; k < m; ++k) {
-            const double x1 = ring[k].x, y1 = ring[k].y;
-            const bool f1 = y1 >= lon;
-            in ^= area::edge_toggles(x0, y0, x1, y1, f0, f1, lat, lon);
-            x0 = x1;
-            y0 = y1;
-            f0 = f1;
-          }
-        }
-        in = in && pt_ok && area::in_levels(sh, alt);
-      }
+      in = wave_shape_inside(sh, a.verts, ring, lane, lat, lon, alt, pt_ok);
       const unsigned long long b = __ballot(in);
       if (lane == 0 && b != 0ull && a.counts) atomicAdd(&a.counts[s], (unsigned long long)__popcll(b));
     }
@@ -145,7 +101,7 @@ __global__ __launch_bounds__(kAreaBlock) void k_area_inside(AreaArgs a) {
 }
 
 // BSA_AREA_CULL=0: every shape for every lane (A/B and test aid, read once)
-static bool area_env_nocull() {
+bool area_env_nocull() {
   static const bool off = [] {
     const char *e = getenv("BSA_AREA_CULL");
     return e && e[0] == '0';
@@ -329,6 +285,7 @@ extern "C" int bsa_sim_set_areas(bsa_ctx *cc, int64_t nshapes, const bsa_area_sh
   BSA_HIP(c, hipSetDevice(c->device));
   BSA_HIP(c, hipStreamSynchronize(c->stream));  // (no pass in flight reads the old table)
   bsa::sect_off(c);  // the sectors named shapes of the old table
+  bsa::geovec_off(c);  // ... and so did the geovectors
   if (!bsa::ensure(c, c->area_verts, (size_t)std::max<int64_t>(nvert, 1) * 16, "area vertices")) return -1;
   if (nvert) BSA_HIP(c, hipMemcpy(c->area_verts.p, verts, (size_t)nvert * 16, hipMemcpyHostToDevice));
   c->area_tab = tab;

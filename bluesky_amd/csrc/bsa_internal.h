@@ -446,6 +446,16 @@ struct Ctx {
   };
   std::vector<SectGone> sect_gone;
 
+  // Geovectoring (bsa_geovec.hip).  gv_stage: bsa_geovec_apply's arrays and tables.  In the
+  // resident step (bsa_sim_set_geovectors): the rows (gv_tab, shape = row number) and their shapes in list order
+  // (gv_shapes), the undo set an applying launch fills first (gv_undo, 4 x n fp64: selspd ap_trk selvs selalt at
+  // the step's start), the counters (gv_cnt, kGvCntWords u64).  gv_ctr: steps completed since
+  // bsa_sim_set_geovectors, the host's, replayed after an abort
+  DevBuf gv_stage, gv_tab, gv_shapes, gv_undo, gv_cnt;
+  bool sim_gv = false;
+  int gv_n = 0;
+  int64_t gv_every = 1, gv_ctr = 0;
+
   // standalone geo matrices (bsa_geo.hip)
   DevBuf geo_in, geo_pts, geo_out;
   hipEvent_t geo_ev[2] = {nullptr, nullptr};
@@ -669,6 +679,21 @@ int sect_step(Ctx *c);
 int sect_note_deleted(Ctx *c, int64_t k, const int64_t *idx);
 void sect_off(Ctx *c);
 int sim_download_rows(Ctx *c, const void *dev0, void *host0, const void *dev1, void *host1, int esz);
+// the area table as the kernels read it (bsa_area.hip): every argument checked, corners and levels sorted, the
+// cull bounds filled in; BSA_AREA_CULL=0 in the environment
+int area_pack(Ctx *c, const char *who, int64_t nshapes, const bsa_area_shape *shapes, int64_t nvert,
+              const double *verts, std::vector<bsa_area_shape> *out);
+bool area_env_nocull();
+
+// Geovectoring in the resident step (bsa_geovec.hip).  geovec_sim_step: first on the stream of
+// the step about to be enqueued while Ctx::sim_gv -- the launch when the steps completed since
+// bsa_sim_set_geovectors are a positive multiple of the cadence, then the counter.  geovec_applies_at: does the
+// step at the counter's present value apply?  geovec_sim_restore: the undo set back into the state,
+// stream-ordered (after an aborted applying step).  geovec_off forgets the geovectors
+int geovec_sim_step(Ctx *c);
+bool geovec_applies_at(const Ctx *c);
+int geovec_sim_restore(Ctx *c);
+void geovec_off(Ctx *c);
 
 // OpenAP drag / thrust / fuel flow (bsa_perf.hip).  forces_consts: Ctx::f_const
 // filled (once).  forces_sim_launch: k_sim_forces of the step about to be

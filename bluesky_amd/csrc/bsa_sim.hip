@@ -228,7 +228,8 @@ void sim_release(Ctx *c) {
   for (const SimArray &a : kSimArrays) release(buf_at(c, a.buf));
   // not per aircraft: staging, control words, tables, the FMS undo set, K2 + K4' double buffers
   DevBuf *rest[] = {&c->red, &c->g_send, &c->g_recv, &c->pg_send, &c->pg_recv, &c->sim_ctl, &c->s_ptab, &c->s_ftab,
-                    &c->f_const, &c->s_fmsrows, &c->s_fmsur, &c->s_fmsuf, &c->s_fmsui, &c->xfer_stage, &c->lbyidx,
+                    &c->f_const, &c->s_fmsrows, &c->s_fmsur, &c->s_fmsuf, &c->s_fmsui, &c->gv_tab, &c->gv_shapes, &c->gv_undo,
+                    &c->gv_cnt, &c->xfer_stage, &c->lbyidx,
                     &c->fetch_stage, &c->tpr_snap, &c->tpr_ctl, &c->nx_alt, &c->nx_vs, &c->nx_gse, &c->nx_gsn};
   for (auto *b : rest) release(*b);
   bk_release(c);
@@ -485,10 +486,11 @@ struct BatchBase {
   int64_t fms_ticks;
   int64_t turb_call;  // the draws' call number
   int64_t sect_ctr;   // the sector pass's step counter
+  int64_t gv_ctr;     // the geovector stage's step counter
 };
 static int batch_begin(Ctx *c, bool kin, BatchBase *b) {
   *b = BatchBase{kin, c->sim_steps, c->sim_cd_calls, c->sim_gs_derivable, c->fms_simt, c->fms_t0, c->fms_ticks,
-                 c->turb_call, c->sect_ctr};
+                 c->turb_call, c->sect_ctr, c->gv_ctr};
   BSA_HIP(c, hipMemsetAsync((char *)c->sim_ctl.p + kSimCtlSticky, 0, 40, c->stream));  // sticky, steps_done, demands, stale
   return 0;
 }
@@ -525,6 +527,13 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long lon
     c->fms_ticks = base.fms_ticks;
     for (int64_t k = 0; k < done; ++k) fms_clock_step(c);
     if (fms_ticks_at(c->fms_simt, c->fms_t0) && fms_sim_restore(c)) return -1;
+  }
+  // the geovector stage writes persistent state: its counter is replayed over the completed steps; if the aborted
+  // step applied, its launch ran (later ones returned behind the sticky word) and the undo set it filled holds the
+  // step's start.  After the FMS undo set, whose selspd / ap_trk / selalt are the values the stage left
+  if (base.kin && c->sim_gv) {
+    c->gv_ctr = base.gv_ctr + done;
+    if (geovec_applies_at(c) && geovec_sim_restore(c)) return -1;
   }
   // the draws are a pure function of (seed, call, index): the completed steps took one call number each, the
   // aborted step's k_sim_turb returned behind the sticky word -- nothing to undo
@@ -727,7 +736,10 @@ static int step_launch(Ctx *c, const StepPlan &sp, const CdOut &cd, const PrepAr
 
 // one step of the batch (enqueue only), and the host state that follows it
 static int step_enqueue(Ctx *c, const StepPlan &sp) {
-  // (forces and FMS read the pre-step state: first on the step's stream)
+  // geovectoring is the plugin's preupdate (tools/plugin.py:161-169): the first launch on the step's stream, so
+  // that Autopilot.update already reads the limited selspd / selvs / selalt / ap.trk
+  if (c->sim_gv && geovec_sim_step(c)) return -1;
+  // (forces and FMS read the pre-step state)
   if (c->sim_forces && forces_sim_launch(c, sp.commit_fuel)) return -1;
   if (c->sim_fms && step_fms(c, sp)) return -1;
   CdOut cd;
@@ -786,6 +798,7 @@ int bsa_sim_init(bsa_ctx *cc, int64_t n, const bsa_sim_state *s, const bsa_sim_p
   c->sim_atmos = c->sim_limits = c->sim_perf = c->sim_forces = c->sim_fms = c->sim_recovery = c->sim_turb = false;
   c->turb_call = 0;
   bsa::sect_off(c);
+  bsa::geovec_off(c);
   c->area_tab.clear();
   // every always-present array (kSimArrays); the all-gathered ones hold nranks
   // x rpr entries (in-place all-gather).  Zero unless a state field fills it:
@@ -1013,6 +1026,7 @@ int bsa_sim_set_fms(bsa_ctx *cc, int64_t nrows, const double *route_rows, const 
   BSA_HIP(c, hipSetDevice(c->device));
   if (!route_rows) {
     c->sim_fms = c->sim_recovery = false;
+    bsa::geovec_off(c);  // selspd / selvs live in the FMS arrays
     return 0;
   }
   if (nrows < 0 || nrows > 0x7fffffff / 8) return bsa::fail(c, "bsa_sim_set_fms: bad route row count");
@@ -1026,6 +1040,8 @@ int bsa_sim_set_fms(bsa_ctx *cc, int64_t nrows, const double *route_rows, const 
   const int64_t n = c->n;
   if (bsa::fms_check_routes(c, "bsa_sim_set_fms", n, nrows, rt_off, rt_n, iactwp, st->swlnav)) return -1;
   c->sim_fms = false;
+  const bool gv_on = c->sim_gv;  // a new FMS state keeps the geovectors; a failed upload leaves both off
+  c->sim_gv = false;
   const size_t N = (size_t)n;
   if (!bsa::ensure(c, c->s_fmsr, bsa::kFmsReals * N * 8, "FMS state") || !bsa::ensure(c, c->s_fmsf, bsa::kFmsFlags * N, "FMS flags") ||
       !bsa::ensure(c, c->s_fmsi, bsa::kFmsInts * N * 4, "route indices") ||
@@ -1048,6 +1064,7 @@ int bsa_sim_set_fms(bsa_ctx *cc, int64_t nrows, const double *route_rows, const 
   c->fms_t0 = t0;
   c->fms_ticks = 0;
   c->sim_fms = true;
+  c->sim_gv = gv_on;
   return 0;
 }
 

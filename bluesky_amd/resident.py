@@ -286,6 +286,24 @@ class ResidentSim:
                 out[name].update(inside=c, inside_before=p)
         return out
 
+    def set_geovectors(self, geovecs, every=1):
+        """Geovectoring inside the step (plugins/geovector.py:76-128; bsa_sim_set_geovectors):
+        ``geovecs`` is the plugin's list of ``[area, gsmin, gsmax, trkmin, trkmax, vsmin, vsmax]``
+        (m/s, deg, m/s; ``bluesky_amd.geovector.geovecs`` is such a list), the areas those of
+        ``set_areas``; a geovector on an unknown area is skipped, a limit is on by Python truth.
+        Applied as the first stage of a step, every ``every`` steps counted from this call --
+        ``every = max(1, round(max(update_interval, simdt) / simdt))``, the first time one interval
+        from now.  Needs ``set_areas`` and ``set_fms``; ``set_areas`` forgets the geovectors,
+        ``set_fms(None)`` switches them off, as does an empty list.  Sharded: every rank calls it alike."""
+        from . import geovector
+        rows, _ = geovector.table(geovecs, getattr(self, '_area_names', []))
+        self.ctx.sim_set_geovectors(rows, every)
+
+    def geovector_stats(self):
+        """dict of ``applies`` (applications since ``set_geovectors``) and ``changed`` (per target
+        array, this rank's aircraft changed, summed over the applications)."""
+        return self.ctx.sim_geovec_stats()
+
     def read(self):
         return self.ctx.sim_read()
 

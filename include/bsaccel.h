@@ -26,6 +26,8 @@
  *       bluesky/tools/areafilter.py:29-35,61-104     checkInside of Box / Circle / Poly / Line
  *   bsa_sim_set_sectors, bsa_sim_sectors_poll, bsa_sim_sectors_deleted
  *       plugins/sectorcount.py:53-96                 per-sector occupancy, arrived / left
+ *   bsa_geovec_apply, bsa_sim_set_geovectors, bsa_sim_geovec_stats
+ *       plugins/geovector.py:76-128                  applygeovec: speed, track and V/S limits per area
  *   bsa_qdrdist
  *       bluesky/tools/geo.py:110-162,347-363         qdrdist_matrix / kwikqdrdist_matrix, materialised
  *   bsa_sim_set_limits
@@ -724,6 +726,68 @@ int bsa_sim_sectors_poll(bsa_ctx *ctx, uint64_t *n_tot, uint64_t *arrived, uint6
  * call with room.  Read it after each bsa_sim_delete: positions of two calls
  * are not told apart. */
 int bsa_sim_sectors_deleted(bsa_ctx *ctx, int64_t cap, int64_t *pos, uint64_t *words, int64_t *count);
+/* ---------------------------------------------------------------- geovectoring
+ * plugins/geovector.py:76-128: per area an allowed interval for ground speed,
+ * track and vertical speed.  The geovectors are an ordered list; each is
+ * applied to every aircraft before the next, so a later one reads what an
+ * earlier one wrote (per aircraft a sequential fold: one lane per aircraft).
+ * For an aircraft inside the geovector's shape (the area filter's test), in
+ * this order:
+ *   GSMIN  casmin = vtas2cas(gsmin, alt); selspd < casmin: selspd = casmin
+ *   GSMAX  casmax = vtas2cas(gsmax, alt); selspd > casmax: selspd = casmax
+ *   TRK    degto180(trk - trkmin) < 0: ap_trk = trkmin; then
+ *          degto180(trk - trkmax) > 0: ap_trk = trkmax   (the max wins)
+ *          degto180(a) = (a + 180) % 360 - 180, numpy's %
+ *   VSMIN  vs < vsmin: selvs = vsmin, selalt = alt + sign(vsmin) * 200 ft
+ *   VSMAX  vs > vsmax: selvs = vsmax, selalt = alt + sign(vsmax) * 200 ft
+ * trk, vs and alt are the traffic's and are never written; no comparison with a
+ * NaN is true.  The reference switches a limit on by Python truth, so a bound of
+ * exactly 0 is "off" there: `given` says which limits are on, and a given bound
+ * (for TRK either of the two) that is exactly 0 is refused here.  An aircraft
+ * that no limit changes keeps its four values bit for bit. */
+#define BSA_GEOVEC_GSMIN 1
+#define BSA_GEOVEC_GSMAX 2
+#define BSA_GEOVEC_TRK   4 /* both track bounds */
+#define BSA_GEOVEC_VSMIN 8
+#define BSA_GEOVEC_VSMAX 16
+#define BSA_GEOVEC_MAX   256 /* geovectors per call / per sim */
+typedef struct bsa_geovec {
+  int32_t shape; /* index into the shape table */
+  int32_t given; /* BSA_GEOVEC_* bits */
+  double gsmin, gsmax, trkmin, trkmax, vsmin, vsmax; /* m/s, deg, m/s */
+} bsa_geovec;
+/* n aircraft (host arrays) under ngv geovectors (<= BSA_GEOVEC_MAX) over the
+ * shape table (as for bsa_area_inside, same checks and limits).  selspd, ap_trk,
+ * selvs and selalt are read and written in place.  flags: BSA_AREA_NOCULL (test
+ * aid; results identical).  changed (4 words, may be NULL): aircraft whose
+ * selspd / ap_trk / selvs / selalt differs bitwise from what came in.  Errors,
+ * all before any launch: NULL arrays, n < 0, ngv beyond the limit, a shape index
+ * outside the table, unknown `given` bits, a given bound that is exactly 0, an
+ * unknown flag, and the table's own errors. */
+int bsa_geovec_apply(bsa_ctx *ctx, int64_t n, const double *lat, const double *lon, const double *alt,
+                     const double *trk, const double *vs, int64_t nshapes, const bsa_area_shape *shapes,
+                     int64_t nvert, const double *verts, int64_t ngv, const bsa_geovec *gv, int flags,
+                     double *selspd, double *ap_trk, double *selvs, double *selalt, uint64_t *changed);
+/* Geovectoring inside the resident step (off by default; nothing is launched
+ * while off; ngv = 0: off).  gv[k].shape names a shape of bsa_sim_set_areas'
+ * table; selspd / selvs are the FMS state's (bsa_sim_set_fms), ap_trk / selalt
+ * the sim's: refused while the sim has no area table or no guidance.
+ * bsa_sim_set_areas forgets the geovectors, bsa_sim_set_fms(NULL) switches them
+ * off.  The stage is the plugin's preupdate (tools/plugin.py:127-132,161-169):
+ * the first launch of a step, on this rank's rows of the pre-step state, at the
+ * start of every step before which a positive multiple of `every` (>= 1; an
+ * integer count of steps, the caller's max(update_interval, simdt) / simdt) steps
+ * have completed since this call -- the first application comes one interval
+ * after loading.  Exact through aborted and re-run batches: an applying launch
+ * first saves the four arrays' rows, and an aborted applying step gets them back
+ * (after the FMS undo set).  None of the four arrays is a detect input.  Several
+ * ranks: every rank calls it alike and applies to its own rows. */
+int bsa_sim_set_geovectors(bsa_ctx *ctx, int64_t ngv, const bsa_geovec *gv, int64_t every);
+/* *applies: applications in completed steps since bsa_sim_set_geovectors;
+ * changed4_total (4 words): this rank's aircraft whose selspd / ap_trk / selvs /
+ * selalt an application changed, summed over them.  Either may be NULL.  An
+ * error while geovectoring is off. */
+int bsa_sim_geovec_stats(bsa_ctx *ctx, int64_t *applies, uint64_t *changed4_total);
 /* This rank's rows (bsa_sim_row_ids) of the FMS state, iactwp and the
  * autopilot's targets into full-n host arrays, the clock and the number of
  * ticks since bsa_sim_set_fms; any pointer may be NULL. */
