@@ -1249,11 +1249,16 @@ class Context:
         (default on where rows and columns are the same aircraft; results never depend on it)."""
         self.check(self.lib.bsa_set_symmetric_sweep(self.h, int(bool(on))), 'bsa_set_symmetric_sweep')
 
+    def set_sweep_level(self, level=2):
+        """bsa_set_symmetric_sweep by level: 0 both orders, 1 each unordered tile pair once,
+        2 (a fresh context's) also the triangular sweep inside a diagonal tile pair."""
+        self.check(self.lib.bsa_set_symmetric_sweep(self.h, int(level)), 'bsa_set_symmetric_sweep')
+
     def symmetric_sweep_stats(self):
-        """bsa_symmetric_sweep_stats: detects planned symmetric, whether the last one was."""
+        """bsa_symmetric_sweep_stats: detects planned symmetric, whether the last one was, its level."""
         v = np.zeros(2, np.int64)
         self.check(self.lib.bsa_symmetric_sweep_stats(self.h, ptr(v, _c_i64p)), 'bsa_symmetric_sweep_stats')
-        return dict(detects=int(v[0]), last=bool(v[1]))
+        return dict(detects=int(v[0]), last=bool(v[1]), level=int(v[1]))
 
     def sim_probe_rank(self, rank, nranks):
         """bsa_sim_probe_rank (measurement aid): the one-rank sim's steps play rank `rank` of `nranks`."""

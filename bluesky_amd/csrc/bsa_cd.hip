@@ -475,7 +475,8 @@ constexpr int kTPThreads = 1024;
 constexpr int kSuper = 8;  // tiles per super tile (each side)
 constexpr int kSlicesPerTile = kTile / kGroup;  // 64-row slices (work items) per row tile
 static_assert(kSlicesPerTile == 8, "8 slices per tile (item bit layout, slice boxes = group boxes)");
-constexpr unsigned kItemMirror = 1u << 31;  // item word 0: row tile (22 bits) | slice << 22 | mirrored
+constexpr unsigned kItemMirror = 1u << 31;  // item word 0: row tile (22 bits) | slice << 22 | triangular | mirrored
+constexpr unsigned kItemTri = 1u << 30;     // (bits 25-29 are free)
 // present (halo mode, nullable): column tiles whose data this rank holds --
 // its own [p0, p1) and the halo tiles it received.  A kept pair with any
 // other column tile means the halo plan disagreed with this test (it cannot:
@@ -539,10 +540,12 @@ __device__ __forceinline__ void tp_emit(bool kn, bool kf, unsigned sm, int rt, i
     }
   }
   __syncthreads();
-  if (ni) {  // item = (row tile | slice << 22 | mirrored << 31, column tile); near ones from the front
+  if (ni) {  // item = (row tile | slice << 22 | flags, column tile); near ones from the front
     // mirrored (kItemMirror): an off-diagonal pair of a symmetric list -- the
     // sweep refines its stage-1 survivors as (row, column) and as (column, row)
-    const unsigned mir = sym && rt != ct ? kItemMirror : 0u;
+    // triangular (kItemTri, level 2): a diagonal pair -- the sweep skips the
+    // column sub-groups below the slice's own and mirrors the ones above
+    const unsigned mir = sym && rt != ct ? kItemMirror : (sym >= 2 && rt == ct ? kItemTri : 0u);
     unsigned long long k = (kn ? bbase[0] + wpre[0][w] + xn : bbase[1] + wpre[1][w] + xf) - ni;
     for (unsigned m = sm; m; m &= m - 1u, ++k) {
       const uint2 v = make_uint2((unsigned)rt | (unsigned)__builtin_ctz(m) << 22 | mir, (unsigned)ct);
@@ -1286,6 +1289,11 @@ __global__ __launch_bounds__(PF_BLOCK) PF_OCC void k_prefilter(
     // tile): the tile pair (column tile, row tile) is not listed -- the drain
     // refines every stage-1 survivor in both orientations (wave-uniform)
     const bool mir = !NOPRUNE && __builtin_amdgcn_readfirstlane(it.x & kItemMirror) != 0u;
+    // a triangular item (K0d, level 2: slice q of tile t against column tile t,
+    // DESIGN.md 3.2d): the sub-groups below the slice's own columns are skipped
+    // (the items of the slices below cover those pairs), the ones above them
+    // are mirrored, the slice's own 64 x 64 block is swept as ever (wave-uniform)
+    const bool tri = !NOPRUNE && __builtin_amdgcn_readfirstlane(it.x & kItemTri) != 0u;
     // column sub-groups of this tile that may interact with the wave's row box:
     // the stage-1 test on box gaps (one sub-group box per lane), evaluated as
     // the item starts
@@ -1298,11 +1306,17 @@ __global__ __launch_bounds__(PF_BLOCK) PF_OCC void k_prefilter(
       const TileBox rg = gbox_r[((int)rc.x * kTile) / kGroup + (int)slice];
       gm = __ballot(lane < nsub && (noprune || boxes_may_interact(rg, sb)));
     }
+    if (tri) gm &= ~0ull << (8u * slice);  // (sub-group lane k: columns cbase + 8 k ..; the slice's own: 8 q .. 8 q + 7)
     if (npc > 1)  // piece p: the set bits of rank p, p + npc, ... (equal shares of a dense mask)
       gm = __ballot(((gm >> lane) & 1ull) && (lane_prefix(gm) & (npc - 1u)) == piece);
     const int rbase = (int)rc.x * kTile + (int)slice * PF_WROWS;
     const int cbase = (int)rc.y * kTile;
     if (!gm) break;
+    // the drain refines a survivor the other way round too when its column is
+    // mlo or above: every column of a mirrored item, the columns above the
+    // slice's own 64 of a triangular one, none otherwise (wave-uniform)
+    const unsigned mlo = mir ? 0u : (tri ? (unsigned)(rbase + PF_WROWS) : ~0u);
+    const bool mt = mir || tri;
     subs += (unsigned)__popcll(gm);
 #ifdef BSA_PF_TRACE
     tr_subs = (unsigned)__popcll(gm);
@@ -1410,10 +1424,11 @@ __global__ __launch_bounds__(PF_BLOCK) PF_OCC void k_prefilter(
           gi = (unsigned)rbase + rl;
           gj = sci[cl];
           keep = NOPRUNE ? true : pf_refine(rsp[w][rl], rv[rl], rbs[w][rl], sx[cl], sv[cl], prm);
-          // mirrored item: the same routine with the roles swapped -- the
-          // column as the row (its basis staged with the batch), the row as
-          // the column; the staged row and column values have one layout
-          if (mir) {
+          // mirrored item, or a column above a triangular item's own 64: the
+          // same routine with the roles swapped -- the column as the row (its
+          // basis staged with the batch), the row as the column; the staged
+          // row and column values have one layout
+          if (mt && gj >= mlo) {
             const float4 cp = sx[cl];
             const float2 cb = cbs[w][cl];
             keepm = pf_refine(cp, sv[cl], make_float4(cp.x * cb.x, cp.y * cb.x, cb.y, 0.f), rsp[w][rl], rv[rl], prm);
@@ -1434,7 +1449,7 @@ __global__ __launch_bounds__(PF_BLOCK) PF_OCC void k_prefilter(
         if (mk) {
           emit(mk, keep, make_uint2(gi, gj));
         }
-        if (mir) {  // candidate (row gj, column gi): rows are the columns from 0 on (diag == 0)
+        if (mt) {  // candidate (row gj, column gi): rows are the columns from 0 on (diag == 0)
           const unsigned long long mm = __ballot(keepm);
           if (mm) emit(mm, keepm, make_uint2(gj, gi));
         }
@@ -1505,7 +1520,7 @@ __global__ __launch_bounds__(PF_BLOCK) PF_OCC void k_prefilter(
         sx[lane] = make_float4(np.x, np.y, np.z, nx.pad);
         sv[lane] = make_float4(nv.flags ? qnan : nv.u * kInvRS, nv.v * kInvRS, nv.vs, nx.alt);
         sci[lane] = (unsigned)jn;
-        if (mir) {  // the column's refine basis as a row's (rbs above: x/rho, y/rho, rho), once per
+        if (mt) {  // the column's refine basis as a row's (rbs above: x/rho, y/rho, rho), once per
                     // staged column; 1/rho and rho only -- 8 B per column keep the workgroup within 40 KB
           const float rho2 = np.x * np.x + np.y * np.y;
           const float irho = __builtin_amdgcn_rsqf(rho2);
@@ -2517,7 +2532,7 @@ const DetectEnv &detect_env() {
                      num("BSA_FUSE_EXACT", -1),
                      num("BSA_OV_GRID_A", 2),
                      num("BSA_K1B_GRID", 0),
-                     num("BSA_PF_SYM", 1) != 0,
+                     std::min(std::max(num("BSA_PF_SYM", 2), 0), 2),
                      num("BSA_K24", 1) != 0,
                      (k4b == 64 || k4b == 128 || k4b == 256) ? k4b : 64,
                      num("BSA_SIM_PREP", 1) != 0};
@@ -2716,9 +2731,12 @@ struct DetectPlan {
   // and every row is detected, so K0d lists each unordered tile pair once
   // (row tile <= column tile) and the sweep refines the stage-1 survivors of
   // an off-diagonal item in both orientations.  One rank, midpoint stage 1,
-  // no KWIK / NOPRUNE / candidate reuse; bsa_set_symmetric_sweep and
-  // BSA_PF_SYM=0 switch it off (A/B).  Part of the kept tile-pair list's key.
-  bool sym;
+  // no KWIK / NOPRUNE / candidate reuse.  The level: 0 both orders, 1 as
+  // above, 2 also the triangular sweep inside a diagonal tile pair (3.2d: a
+  // slice skips the column sub-groups below its own and refines the ones above
+  // both ways); the lower of bsa_set_symmetric_sweep's and BSA_PF_SYM's (A/B).
+  // Part of the kept tile-pair list's key.
+  int sym;
   // the resident step's K4' already wrote this detect's column records and
   // boxes from the state it computed (Ctx::prep; any detect consumes or
   // invalidates them: it rewrites the same buffers)
@@ -3003,11 +3021,12 @@ static int detect_decide(Ctx *c, const DetectRequest &q, DetectPlan *plan) {
   p.tp_list = p.halo && !env.tp_halo_all && !env.tp_super;
   p.tpr = env.tpr && c->tpr_on && p.home && !p.reuse && flags == 0 && !env.tp_super &&
           ((!p.halo && p.prepped && (n + kTile - 1) / kTile <= kTPDirectMax) || p.tp_list);
-  p.sym = env.pf_sym && c->sym_on && p.shared && rb == 0 && re == n && !p.halo && c->nranks == 1 && p.mid &&
-          !p.noprune && !p.kwik && !p.reuse;
+  p.sym = p.shared && rb == 0 && re == n && !p.halo && c->nranks == 1 && p.mid && !p.noprune && !p.kwik && !p.reuse
+              ? std::min(env.pf_sym, c->sym_on)
+              : 0;
   c->last_sym = p.sym;
   if (p.sym) c->sym_count++;
-  const KeptTilePairs::Key tkey{rpz, hpz, tla, (double)p.mid, (double)rb, (double)re, p.sym ? 1.0 : 0.0, n};
+  const KeptTilePairs::Key tkey{rpz, hpz, tla, (double)p.mid, (double)rb, (double)re, (double)p.sym, n};
   p.tvalid = p.tpr && c->tiles.matches(tkey);
   if (decide_hk(c, p, q.host_decides)) return -1;
   if (p.tpr)  // (every rank, also one without rows: the kept state stays collective)
@@ -3267,12 +3286,12 @@ static int detect_tilepairs(DetectRun &R) {
                        p.halo ? halo_present(c) : nullptr, p.a0, p.a1,
                        p.nozero ? (const TileBox *)c->gbox_c.p : (const TileBox *)nullptr,
                        p.tp_list ? (const int *)c->h_hl.p : (const int *)nullptr, (int)c->halo_hl,
-                       p.tp_list ? halo_list_count(c) : (const unsigned *)nullptr, R.tp, p.sym ? 1 : 0);
+                       p.tp_list ? halo_list_count(c) : (const unsigned *)nullptr, R.tp, p.sym);
   else
     hipLaunchKernelGGL(k_tilepairs, dim3((unsigned)((p.nrt + kSuper - 1) / kSuper)), dim3(kTPThreads), 0, c->stream,
                        p.nrt, p.nct, (int)p.nrows, R.tbox_r, R.gbox_r, (const TileBox *)c->tbox_c.p, p.noprune,
                        (uint2 *)c->tilepairs.p, p.icap, R.dcnt, (unsigned long long *)c->workq.p, R.build,
-                       p.halo ? halo_present(c) : nullptr, p.a0, p.a1, p.sym ? 1 : 0);
+                       p.halo ? halo_present(c) : nullptr, p.a0, p.a1, p.sym);
   BSA_HIP(c, hipGetLastError());
   return 0;
 }

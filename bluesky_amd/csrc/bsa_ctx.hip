@@ -694,9 +694,10 @@ int bsa_exact_fusion_stats(bsa_ctx *c, int64_t *out3) {
   return 0;
 }
 
-int bsa_set_symmetric_sweep(bsa_ctx *c, int on) {
+int bsa_set_symmetric_sweep(bsa_ctx *c, int level) {
   if (!c) return -1;
-  c->sym_on = on != 0;
+  if (level < 0 || level > 2) return bsa::fail(c, "the sweep level is 0 (both orders), 1 (symmetric) or 2 (triangular)");
+  c->sym_on = level;
   bsa::invalidate(c, bsa::Change::SetSymSweep);  // (a kept tile-pair list is the other kind: the next detect builds)
   return 0;
 }
@@ -704,7 +705,7 @@ int bsa_set_symmetric_sweep(bsa_ctx *c, int on) {
 int bsa_symmetric_sweep_stats(bsa_ctx *c, int64_t *out2) {
   if (!c || !out2) return -1;
   out2[0] = c->sym_count;
-  out2[1] = c->last_sym ? 1 : 0;
+  out2[1] = c->last_sym;
   return 0;
 }
 

@@ -397,8 +397,8 @@ struct Ctx {
   bool fuse_on = true;      // bsa_set_exact_fusion
   int fuse_recs = kFuseRecsMax;  // ... per-wave mid-sweep flush records (testing knob)
   int64_t fuse_count = 0, fuse_retries = 0;  // bsa_exact_fusion_stats
-  bool sym_on = true;       // bsa_set_symmetric_sweep (DetectPlan::sym)
-  bool last_sym = false;    // the last detect swept each unordered tile pair once
+  int sym_on = 2;           // bsa_set_symmetric_sweep: the level allowed (DetectPlan::sym)
+  int last_sym = 0;         // the last detect's level (> 0: it swept each unordered tile pair once)
   int64_t sym_count = 0;    // ... and how many did (bsa_symmetric_sweep_stats)
   // region layout agreement (comm_halo): every rank's send lengths / offsets
   // are compared with every receiver's expectation whenever the layout may have
@@ -904,7 +904,7 @@ struct DetectEnv {
   int fuse_exact;      // BSA_FUSE_EXACT=0/1: K1b fused into the prefilter (-1: detect_decide's rule)
   int ov_grid_a;       // BSA_OV_GRID_A: workgroups per CU of the overlap's own-tile sweep (<= 0: the whole grid)
   int k1b_grid;        // BSA_K1B_GRID>0: K1b's grid
-  bool pf_sym;         // BSA_PF_SYM=0: every tile pair swept in both orders (no symmetric sweep, DetectPlan::sym)
+  int pf_sym;          // BSA_PF_SYM=0/1/2: the highest sweep level a plan takes (DetectPlan::sym; unset: 2)
   // the resident step (bsa_sim.hip: step_decide)
   bool k24;            // BSA_K24=0: K2 and K4' as two launches
   int k4_block;        // BSA_K4_BLOCK=64/128/256: K4' workgroup size (anything else: 64)

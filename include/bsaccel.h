@@ -160,12 +160,16 @@ int bsa_exact_fusion_stats(bsa_ctx *ctx, int64_t *out3);
  * and the columns of a detect are the same aircraft (own == intruder, every
  * row, one rank; midpoint stage 1, not KWIK / NOPRUNE / candidate reuse) each
  * unordered pair of 512-aircraft tiles is listed and stage-1-tested once, and
- * its survivors are refined in both orientations.  Results never depend on
- * it; off sweeps both orders (A/B; the BSA_PF_SYM=0 environment variable does
- * the same for every context). */
+ * its survivors are refined in both orientations.  `on` is a level: 0 sweeps
+ * both orders, 1 is the above, 2 (a fresh context's) adds the triangular
+ * sweep inside a diagonal tile pair (a 64-row slice skips the
+ * column sub-groups below its own columns and refines the ones above them in
+ * both orientations); any other value is refused.  Results never depend on
+ * it (A/B; the BSA_PF_SYM=0 / 1 / 2 environment variable caps the level of
+ * every context). */
 int bsa_set_symmetric_sweep(bsa_ctx *ctx, int on);
-/* [0] detects enqueued with the symmetric sweep, [1] whether the last detect
- * used it (0 / 1). */
+/* [0] detects enqueued with the symmetric sweep, [1] the last detect's level
+ * (0: both orders, 1 / 2 as above). */
 int bsa_symmetric_sweep_stats(bsa_ctx *ctx, int64_t *out2);
 /* Candidate-list reuse across detects (own == intruder, whole row range, not
  * KWIK / NOPRUNE).  A detect that builds the list inflates

@@ -3,7 +3,9 @@ blocks (64 rows x 8 columns) and the (tile pair, 64-row slice) items of a
 detect whose rows are its columns, split by tile pair -- diagonal (a = a),
 upper (a < b), lower (a > b).  Today's sweep runs all three; the symmetric
 sweep lists the diagonal and the upper pairs only and refines the upper
-pairs' stage-1 survivors in both orientations.
+pairs' stage-1 survivors in both orientations.  The triangular sweep (3.2d,
+blocks['tri']) also drops, inside a diagonal pair, the blocks whose column
+sub-group lies below the slice's own columns.
 
 Order, records and box test are tools/octet_model.py's (the device's Hilbert
 key, make_pf_mid in fp64, boxes_may_interact).
@@ -24,7 +26,8 @@ CLASSES = ('diagonal', 'upper', 'lower')
 def sym_model(t, R=synth.RPZ, H=synth.HPZ, T=synth.TLOOKAHEAD, seed=7):
     """t: a workload name or a Traffic.  Returns dict(n, blocks, items), blocks
     and items being dicts over CLASSES plus 'today' (all three) and 'sym'
-    (diagonal + upper)."""
+    (diagonal + upper); blocks also has 'tri' (sym without the diagonal pairs'
+    lower blocks)."""
     if isinstance(t, str):
         t = synth.workload(t, seed=seed)
     P, s, lo, hi = om.records(t, R, H, T)
@@ -40,18 +43,23 @@ def sym_model(t, R=synth.RPZ, H=synth.HPZ, T=synth.TLOOKAHEAD, seed=7):
     it_r, it_c = it_r[ok], it_c[ok]
     cls = np.where(it_r // 8 == it_c, 0, np.where(it_r // 8 < it_c, 1, 2))
     blocks, items = np.zeros(3, np.int64), np.bincount(cls, minlength=3)
+    low = 0   # blocks of diagonal items whose column sub-group lies below the slice's own eight
     CH = 4096
     for k in range(0, len(it_r), CH):
         r, c = it_r[k:k + CH], it_c[k:k + CH]
         col_sg = c[:, None] * 64 + np.arange(64)[None, :]       # the column tile's sub-groups
         gm = (col_sg < nsb) & om.interact(gb, r[:, None], sb, np.minimum(col_sg, nsb - 1))   # the sweep's mask
         blocks += np.bincount(cls[k:k + CH], weights=gm.sum(1), minlength=3).astype(np.int64)
+        below = np.arange(64)[None, :] < 8 * (r % 8)[:, None]
+        low += int((gm & below & (cls[k:k + CH] == 0)[:, None]).sum())
 
     def table(v):
         d = {name: int(v[q]) for q, name in enumerate(CLASSES)}
         d.update(today=int(v.sum()), sym=int(v[0] + v[1]))
         return d
-    return dict(n=len(P), blocks=table(blocks), items=table(items))
+    b = table(blocks)
+    b['tri'] = b['sym'] - low   # the triangular sweep (3.2d): no lower blocks inside a diagonal tile pair
+    return dict(n=len(P), blocks=b, items=table(items))
 
 
 def main(wl):
@@ -65,6 +73,7 @@ def main(wl):
     print('%-22s %14d (%+.1f %%) %18d (%+.1f %%)' % ('diagonal + upper only', b['sym'],
                                                      100.0 * (b['sym'] / max(b['today'], 1) - 1.0), it['sym'],
                                                      100.0 * (it['sym'] / max(it['today'], 1) - 1.0)))
+    print('%-22s %14d (%+.1f %%)' % ('... triangular inside', b['tri'], 100.0 * (b['tri'] / max(b['today'], 1) - 1.0)))
 
 
 if __name__ == '__main__':
