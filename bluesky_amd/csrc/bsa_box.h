@@ -1,5 +1,5 @@
 // Tile / group bounding boxes of the prefilter records and the box test the
-// tile-pair cull (K0d, bsa_cd.hip) and the halo plan of the row-sharded step
+// tile-pair cull (K0d, bsa_k0.hip) and the halo plan of the row-sharded step
 // (bsa_halo.hip) share: both must take the same decision for the same boxes.
 #pragma once
 #include "bsa_internal.h"

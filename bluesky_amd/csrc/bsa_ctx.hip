@@ -454,7 +454,7 @@ bsa_ctx *bsa_create(int device) {
     return nullptr;
   }
   c->device = device;
-  // longest prefilter items first (bsa_cd.hip HeavyArgs): the listing
+  // longest prefilter items first (bsa_cd_args.h HeavyArgs): the listing
   // threshold, or off (BSA_PF_HEAVY=0); results never depend on it
   if (const char *v = getenv("BSA_PF_HEAVY_US")) {
     c->hv_us = atof(v);

@@ -1,5 +1,5 @@
 // Device restatements of bluesky/tools/geo.py shared by the fused CD kernel
-// (bsa_cd.hip, K1b) and the standalone matrix producers (bsa_geo.hip).
+// (bsa_pair_math.h, K1b) and the standalone matrix producers (bsa_geo.hip).
 // Same operation order as the numpy code, compiled with -ffp-contract=off,
 // so every + - * / sqrt rounds like numpy's.
 #pragma once

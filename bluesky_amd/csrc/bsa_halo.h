@@ -1,4 +1,4 @@
-// Halo exchange pieces shared by bsa_halo.hip (plan, exchange) and bsa_cd.hip
+// Halo exchange pieces shared by bsa_halo.hip (plan, exchange) and bsa_k0.hip
 // (the own-tile K0b fills the plan's zeroed buffers and box block; the halo
 // K0b unpacks each received tile before preparing it) -- DESIGN.md 6.
 #pragma once

@@ -279,7 +279,7 @@ struct Ctx {
   int64_t hk_keeps = 0, hk_builds = 0, hk_stale = 0, hk_waits = 0;  // statistics
   float hk_f = 0.75f;                  // prediction fraction of the budgets (BSA_HK_F)
   unsigned long long *hk_host = nullptr, *hk_hdev = nullptr;  // pinned ring (host / device view)
-  // longest items first (bsa_cd.hip HeavyArgs): per list slot cost / flag, two item lists and counts
+  // longest items first (bsa_cd_args.h HeavyArgs): per list slot cost / flag, two item lists and counts
   DevBuf hv_cost, hv_flag, hv_list[4], hv_cnt;  // lists: [parity][tier]
   unsigned long long hv_icap = 0;
   unsigned hv_epoch = 0;
@@ -392,7 +392,7 @@ struct Ctx {
   int64_t halo_grows = 0;          // capacity regrowths (aborted steps)
   int64_t halo_rx = 0, halo_tx = 0;  // bytes received / sent per CD step (the capacities' transfers)
   int halo_fields = 8;             // fp64 arrays per halo row of the last exchange (6 when derivable)
-  bool last_fused = false;  // the last detect ran K1b fused into the prefilter (ExactFuse, bsa_cd.hip)
+  bool last_fused = false;  // the last detect ran K1b fused into the prefilter (ExactFuse, bsa_cd_args.h)
   bool fuse_skip = false;   // a fused detect ran out of flush records: its retry runs K1b as its own launch
   bool fuse_on = true;      // bsa_set_exact_fusion
   int fuse_recs = kFuseRecsMax;  // ... per-wave mid-sweep flush records (testing knob)
@@ -752,7 +752,7 @@ void halo_release(Ctx *c);
 const uint8_t *halo_present(const Ctx *c);  // the received-tile mask of the last halo_mid
 const unsigned *halo_list_count(const Ctx *c);  // the probe's halo list length (device), else NULL
 // K0b over every column tile (fused boxes, no per-detect zeroing): the halo
-// plan's view of all tile boxes when every rank's state is on this GPU (bsa_cd.hip)
+// plan's view of all tile boxes when every rank's state is on this GPU (bsa_k0.hip)
 // every column tile's records and boxes (one K0b); nf_epoch != 0: non-finite
 // columns store it into Ctx::nonfin (the detect that takes that epoch sees them)
 int prep_all_tiles(Ctx *c, double rpz, double hpz, double tla, unsigned long long nf_epoch = 0);
@@ -760,9 +760,9 @@ int prep_all_tiles(Ctx *c, double rpz, double hpz, double tla, unsigned long lon
 // colrec (rec only), pfcol, pfvcol, pfpcol and the tile / group / sub-group boxes
 bool ensure_col_prep(Ctx *c, int64_t n, bool rec);
 
-// exclusive prefix sum of n words, one launch (bsa_cd.hip)
+// exclusive prefix sum of n words, one launch (bsa_scan.hip)
 int scan_excl(Ctx *c, const unsigned *in, unsigned *out, int n);
-// spatial (home) order of the n aircraft in own[] (bsa_cd.hip): home -> aircraft index
+// spatial (home) order of the n aircraft in own[] (bsa_k0.hip): home -> aircraft index
 int home_order(Ctx *c, double tla, std::vector<unsigned> &h2id);
 // the last detect's pair lists and per-row outputs in aircraft-index terms
 // (bsa_ctx.hip): home rows -> indices, rows in ascending index order

@@ -1,7 +1,7 @@
 // Per-pair part of MVP.resolve (MVP.py:33-56): MVP.MVP (MVP.py:149-231) and
 // the priority rules (MVP.py:235-300; only the first return value is kept,
 // MVP.py:46).  Shared by k_mvp_pair (bsa_mvp.hip) and the resident step's
-// K2 (k_rank, bsa_cd.hip), which evaluates it as it places each pair.
+// K2 (k_rank, bsa_rank.hip), which evaluates it as it places each pair.
 #pragma once
 #include "bsa_internal.h"
 

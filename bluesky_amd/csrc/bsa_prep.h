@@ -1,4 +1,4 @@
-// K0b / K0c pieces shared by the detect (bsa_cd.hip: k_prep_cols, k_boxes)
+// K0b / K0c pieces shared by the detect (bsa_k0.hip: k_prep_cols, k_boxes)
 // and the resident step's K4' (bsa_sim.hip), which prepares the next CD
 // step's column records and boxes from the state it has just computed
 // (DESIGN.md 3.7): the same expressions, so the records are bitwise those

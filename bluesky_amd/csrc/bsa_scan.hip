@@ -1,0 +1,124 @@
+// Exclusive prefix sum of unsigned words in one launch (scan_excl,
+// bsa_internal.h): K2's row offsets at bucket width 0, the halo plan's lists.
+#include "bsa_internal.h"
+#include "bsa_wave.h"
+
+namespace bsa {
+
+// ------------------------------------------------------------------ single-pass scan
+// Exclusive prefix sum of n unsigned words in ONE launch (replaces hipcub's
+// three: look-back init + scan, ~16 us per detect at 100k): decoupled
+// look-back over 8192-word tiles.  Tiles are numbered by a ticket (a running
+// device counter; the host knows its base), so a tile only ever waits on tiles
+// that already started.  Tile status words carry the launch's epoch, so they
+// need no zeroing between launches: {epoch:30 | flag:2 | value:32}, flag 1 =
+// the tile's own total, 2 = inclusive prefix through the tile.
+// Tiles of kScanThreads x kScanItems words: 2048 below 2^19 words (more tiles
+// in flight: K2 26.3 -> 24.6 us at 100k, 19.9 -> 14.6 us for one rank of 8),
+// 8192 above (at 1M a 2048-word tiling's ~1000 tiles lengthened the ticket
+// queue and the look-back: 62 -> 139 us)
+__device__ __forceinline__ unsigned long long scan_word(unsigned epoch, unsigned flag, unsigned v) {
+  return ((unsigned long long)(epoch & 0x3fffffffu) << 34) | ((unsigned long long)flag << 32) | v;
+}
+template <int kScanThreads, int kScanItems>
+__global__ __launch_bounds__(kScanThreads) void k_scan_excl(const unsigned *__restrict__ in, unsigned *__restrict__ out,
+                                                            int n, unsigned long long *__restrict__ ticket,
+                                                            unsigned long long base,
+                                                            unsigned long long *__restrict__ status, unsigned epoch) {
+  constexpr int kScanTile = kScanThreads * kScanItems;
+  __shared__ unsigned wsum[kScanThreads / 64];
+  __shared__ unsigned s_tile, s_excl;
+  if (threadIdx.x == 0) s_tile = (unsigned)(atomicAdd(ticket, 1ull) - base);
+  __syncthreads();
+  const unsigned tile = s_tile;
+  const long long i0 = (long long)tile * kScanTile + (long long)threadIdx.x * kScanItems;
+  unsigned v[kScanItems], tsum = 0;
+#pragma unroll
+  for (int k = 0; k < kScanItems; ++k) {
+    v[k] = (i0 + k < n) ? in[i0 + k] : 0u;
+    tsum += v[k];
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned x = wave_incl_scan(tsum);
+  if (lane == 63) wsum[w] = x;
+  __syncthreads();
+  // wave 0: tile total, then a wave-wide look-back (64 predecessors per round:
+  // the nearest inclusive prefix, plus the aggregates after it)
+  if (w == 0) {
+    const unsigned wv = lane < kScanThreads / 64 ? wsum[lane] : 0u;
+    const unsigned wx = wave_incl_scan(wv);
+    if (lane < kScanThreads / 64) wsum[lane] = wx - wv;  // exclusive per-wave offsets
+    const unsigned total = __builtin_amdgcn_readlane(wx, 63);
+    unsigned excl = 0;
+    if (tile == 0) {
+      if (lane == 0)
+        __hip_atomic_store(&status[0], scan_word(epoch, 2, total), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      if (lane == 0)
+        __hip_atomic_store(&status[tile], scan_word(epoch, 1, total), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      int top = (int)tile - 1;  // highest predecessor not yet summed
+      for (;;) {
+        const int j = top - lane;
+        unsigned long long st = 0;
+        if (j >= 0) st = __hip_atomic_load(&status[j], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned flag = ((unsigned)(st >> 34) == (epoch & 0x3fffffffu)) ? ((unsigned)(st >> 32) & 3u) : 0u;
+        // lanes past tile 0 count as "inclusive 0"
+        const bool incl = j < 0 || flag == 2, ready = j < 0 || flag != 0;
+        const unsigned long long mi = __ballot(incl), mr = __ballot(ready);
+        // first lane (nearest predecessor) holding an inclusive prefix, or 64
+        const int fi = mi ? __builtin_ctzll(mi) : 64;
+        // every lane up to fi must be ready, else spin on this window
+        const unsigned long long need = fi >= 63 ? ~0ull : ((2ull << fi) - 1);
+        if ((mr & need) != need) {
+          __builtin_amdgcn_s_sleep(1);
+          continue;
+        }
+        unsigned part = (lane <= fi && j >= 0) ? (unsigned)st : 0u;
+        for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+        excl += part;
+        if (fi < 64) break;
+        top -= 64;
+      }
+      if (lane == 0)
+        __hip_atomic_store(&status[tile], scan_word(epoch, 2, excl + total), __ATOMIC_RELEASE,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (lane == 0) s_excl = excl;
+  }
+  __syncthreads();
+  unsigned run = s_excl + wsum[w] + x - tsum;
+#pragma unroll
+  for (int k = 0; k < kScanItems; ++k) {
+    if (i0 + k < n) out[i0 + k] = run;
+    run += v[k];
+  }
+}
+
+int scan_excl(Ctx *c, const unsigned *in, unsigned *out, int n) {
+  if (n <= 0) return 0;
+  const bool small = n <= (1 << 19);
+  const int kScanTile = small ? 512 * 4 : 1024 * 8;
+  const unsigned tiles = (unsigned)((n + kScanTile - 1) / kScanTile);
+  const size_t had = c->scan_ws.bytes;
+  if (!ensure_keep(c, c->scan_ws, 8 * (size_t)(1 + tiles), "scan tile status")) return -1;
+  if (c->scan_ws.bytes != had) c->scan_ready = false;  // grown: the new words are uninitialised
+  if (!c->scan_ready) {  // ticket counter and tile status start at 0
+    BSA_HIP(c, hipMemsetAsync(c->scan_ws.p, 0, c->scan_ws.bytes, c->stream));
+    c->scan_ready = true;
+    c->scan_tickets = 0;
+    c->scan_epoch = 0;
+  }
+  const unsigned epoch = ++c->scan_epoch;  // never 0: fresh (zeroed) status words are never ready
+  unsigned long long *ws = (unsigned long long *)c->scan_ws.p;
+  if (small)
+    hipLaunchKernelGGL((k_scan_excl<512, 4>), dim3(tiles), dim3(512), 0, c->stream, in, out, n, ws, c->scan_tickets,
+                       ws + 1, epoch);
+  else
+    hipLaunchKernelGGL((k_scan_excl<1024, 8>), dim3(tiles), dim3(1024), 0, c->stream, in, out, n, ws,
+                       c->scan_tickets, ws + 1, epoch);
+  BSA_HIP(c, hipGetLastError());
+  c->scan_tickets += tiles;
+  return 0;
+}
+
+}  // namespace bsa

@@ -599,7 +599,7 @@ static int check_params(Ctx *c, const bsa_sim_params *p) {
 
 // ---- one step of a batch: StepPlan (every decision, taken by step_decide
 // before anything of the step is enqueued), one function per stage,
-// step_enqueue runs them in order (the detect side: DetectPlan, bsa_cd.hip)
+// step_enqueue runs them in order (the detect side: DetectPlan, bsa_detect.h)
 struct StepPlan {
   // OpenAP forces: the pending fuel of the step before is committed first --
   // not by the first step of a re-run attempt: it is the aborted step's own

@@ -1,6 +1,6 @@
 // One row of the resident step's K4' (Pilot.APorASAS + the kinematic update +
 // the next detect's record), shared by k_sim_pilot_kin (bsa_sim.hip) and K2's
-// fused form (k_rank_rows<true>, bsa_cd.hip).
+// fused form (k_rank_rows<true>, bsa_rank.hip).
 #pragma once
 #include "bsa_kin_math.h"
 #include "bsa_mvp_row.h"
@@ -171,7 +171,7 @@ struct K24Args {
   int winddim, prep;
   HkPub pub;          // HK: this detect's prediction to the host (slot NULL: none)
 };
-// the K2 launch a detect kept (DetectResult::k2, k2_ev), fused (bsa_cd.hip)
+// the K2 launch a detect kept (DetectResult::k2, k2_ev), fused (bsa_rank.hip)
 int k24_launch(Ctx *c, const RankLaunch &k2, hipEvent_t k2_ev, const K24Args &ka);
 
 }  // namespace bsa

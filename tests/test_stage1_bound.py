@@ -1,4 +1,4 @@
-"""Host check of the midpoint stage-1 bound (bsa_cd.hip
+"""Host check of the midpoint stage-1 bound (bsa_prep.h
 make_pf_mid): every conflict and LoS pair the reference reports must satisfy
 |m_i - m_j| < s_i + s_j and |a_i - a_j| < h_i + h_j with the per-aircraft
 midpoint records.  The GPU path tests the same pairs in a projection (which

@@ -1,6 +1,6 @@
 """Host model of the prefilter's work at a given cull granularity, in the
 DEVICE's own spatial order (3-D Hilbert key of the look-ahead midpoints,
-curve_key / k_keys in bsa_cd.hip) and with its own box test
+curve_key / k_keys in bsa_k0.hip) and with its own box test
 (boxes_may_interact, bsa_box.h): for every (tile pair, 64-row slice) item that
 K0d lists, the column sub-groups (8 columns) whose box may interact with the
 slice box (the sweep's mask today), and -- finer -- which of the slice's
@@ -33,7 +33,7 @@ def expand10(v):
 
 
 def curve_key(P):
-    """curve_key of bsa_cd.hip: Skilling's transpose, 10 bits per axis."""
+    """curve_key of bsa_k0.hip: Skilling's transpose, 10 bits per axis."""
     X = [np.clip(((P[:, k] + 1.0) * 512.0).astype(np.int64), 0, 1023).astype(np.uint32) for k in range(3)]
     Q = np.uint32(1 << 9)
     while Q > 1:
