@@ -22,6 +22,7 @@
 #include <unordered_set>
 
 #include "bsa_area_wave.h"
+#include "bsa_xfer.h"
 
 #pragma clang fp contract(off)
 
@@ -344,7 +345,11 @@ extern "C" int bsa_sim_sectors_poll(bsa_ctx *cc, uint64_t *n_tot, uint64_t *arri
     for (size_t k = 0; dst[q] && k < c->sect_idx.size(); ++k) dst[q][k] = h[off[q] + k];
   if (updates) *updates = c->sect_ctr / c->sect_every;
   if (step) *step = c->sect_ctr / c->sect_every * c->sect_every;
-  return bsa::sim_download_rows(c, c->s_scur.p, cur_words, c->s_sprev.p, prev_words, 8);
+  bsa::HomeBatch down(c, false, c->sim_rb, c->sim_re);  // this rank's rows of the masks, index order (NULL: left out)
+  if ((cur_words && down.add(c->s_scur.p, nullptr, cur_words, 8)) ||
+      (prev_words && down.add(c->s_sprev.p, nullptr, prev_words, 8)))
+    return -1;
+  return down.run();
 }
 
 extern "C" int bsa_sim_sectors_deleted(bsa_ctx *cc, int64_t cap, int64_t *pos, uint64_t *words, int64_t *count) {

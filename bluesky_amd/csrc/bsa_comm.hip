@@ -6,7 +6,7 @@
 //  * an in-process group (bsa_group_*): several contexts in ONE process, each
 //    driven by its own host thread, exchanging through device-to-device copies
 //    ordered by HIP events and a host barrier.  RCCL rejects two ranks on one
-//    GPU, so this is how the nranks > 1 code paths (k_pack / k_unpack, the gate
+//    GPU, so this is how the nranks > 1 code paths (the row gathers, the gate
 //    all-reduce, the rank-order pair gather, the global unique-pair counts) run
 //    and are checked on a one-GPU box; it also serves a single process that
 //    drives several GPUs from several threads.

@@ -315,7 +315,7 @@ struct Ctx {
 
   // MVP / kinematics staging (host-buffer entry points)
   DevBuf seg, mvp_stage, kin_stage, mvp_pdv, mvp_pfl, mvp_rowdv;
-  DevBuf xfer_stage;  // batched home-order transfers (bsa_sim.hip: HomeBatch), index-order staging
+  DevBuf xfer_stage;  // batched home-order transfers (bsa_xfer.hip: HomeBatch), index-order staging
   // pinned host staging of the drop-ins' transfers (pin_stage, bsa_ctx.hip):
   // one DMA per batch; pin_ev guards the buffer while a DMA from it may run
   void *pin = nullptr;
@@ -357,7 +357,7 @@ struct Ctx {
   DevBuf s_tas, s_hdg, s_gse, s_gsn;                        // traffic state besides own[]
   DevBuf s_aptrk, s_aptas, s_apalt, s_apvs, s_selalt, s_bank, s_eps, s_accel;  // frozen
   DevBuf s_atrk, s_atas, s_avs, s_aalt, s_ase, s_asn, s_active;  // ASAS (full n)
-  DevBuf g_send, g_recv;                                    // all-gather staging
+  DevBuf g_send, g_recv;  // all-gather staging (bsa_xfer.hip: gather_rows; g_send also comm_allgather_inplace's)
   // Non-finite tcpa inputs (StateBasedCD.py:90: tcpamax = np.max(tcpa *
   // swconfl) is NaN on every row once one tcpa is NaN): nonfin[0] = the epoch
   // of the last column records holding a non-finite lat / lon / u / v (its
@@ -673,12 +673,10 @@ int turb_sim_launch(Ctx *c, int64_t rb, int64_t re, const unsigned *sticky, cons
 
 // Sector occupancy (bsa_area.hip): sect_step after the last stage of every step while Ctx::sim_sect (the step
 // counter, and the pass when it reaches a multiple of the cadence); sect_note_deleted by bsa_sim_delete before
-// anything moves; sect_off forgets the sectors.  sim_download_rows (bsa_sim.hip): this rank's rows of up to two
-// device arrays into full-n host arrays in index order (a NULL host array is left out)
+// anything moves; sect_off forgets the sectors
 int sect_step(Ctx *c);
 int sect_note_deleted(Ctx *c, int64_t k, const int64_t *idx);
 void sect_off(Ctx *c);
-int sim_download_rows(Ctx *c, const void *dev0, void *host0, const void *dev1, void *host1, int esz);
 // the area table as the kernels read it (bsa_area.hip): every argument checked, corners and levels sorted, the
 // cull bounds filled in; BSA_AREA_CULL=0 in the environment
 int area_pack(Ctx *c, const char *who, int64_t nshapes, const bsa_area_shape *shapes, int64_t nvert,

@@ -26,6 +26,7 @@
 #include "bsa_perf_math.h"
 #include "bsa_prep.h"
 #include "bsa_sim_row.h"
+#include "bsa_xfer.h"
 
 #pragma clang fp contract(off)
 
@@ -75,33 +76,6 @@ __global__ __launch_bounds__(256) void k_sim_pilot_kin(int rb, int re, double si
   pilot_kin_row<FUSE, PREP>(rb, k, simdt, winddim, vwn, vwe, wf, d, mv, mp, pa);
 }
 
-// field list of one all-gather: fp64 arrays (full n) + optionally one uint8 array
-struct Fields {
-  double *f[8];
-  int nf;
-  uint8_t *u8;  // transported as 0.0 / 1.0 in one extra slot (may be NULL)
-};
-
-__global__ __launch_bounds__(256) void k_pack(int rb, int re, int rpr, Fields fl, double *__restrict__ send) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= rpr) return;
-  const int k = rb + r;
-  const bool v = k < re;
-  for (int f = 0; f < fl.nf; ++f) send[(size_t)f * rpr + r] = v ? fl.f[f][k] : 0.0;
-  if (fl.u8) send[(size_t)fl.nf * rpr + r] = v ? (double)fl.u8[k] : 0.0;
-}
-
-__global__ __launch_bounds__(256) void k_unpack(int n, int rpr, int self, Fields fl, int slots,
-                                                const double *__restrict__ recv) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  const int q = k / rpr, r = k - q * rpr;
-  if (q == self) return;
-  const double *blk = recv + (size_t)q * slots * rpr;
-  for (int f = 0; f < fl.nf; ++f) fl.f[f][k] = blk[(size_t)f * rpr + r];
-  if (fl.u8) fl.u8[k] = blk[(size_t)fl.nf * rpr + r] != 0.0;
-}
-
 static SimDev sim_dev(Ctx *c) {
   SimDev d;
   d.lat = (double *)c->own[0].p;
@@ -143,24 +117,6 @@ static SimDev sim_dev(Ctx *c) {
   return d;
 }
 
-// one all-gather (RCCL or in-process group) of the listed arrays' rows [sim_rb, sim_re) of every rank
-static int gather_fields(Ctx *c, const Fields &fl) {
-  const int64_t rpr = c->sim_rpr, n = c->n;
-  const int slots = fl.nf + (fl.u8 ? 1 : 0);
-  const size_t blk = (size_t)slots * rpr;
-  if (!ensure(c, c->g_send, blk * 8, "gather send") ||
-      !ensure(c, c->g_recv, blk * 8 * c->nranks, "gather recv"))
-    return -1;
-  hipLaunchKernelGGL(k_pack, dim3((unsigned)((rpr + 255) / 256)), dim3(256), 0, c->stream, (int)c->sim_rb,
-                     (int)c->sim_re, (int)rpr, fl, (double *)c->g_send.p);
-  BSA_HIP(c, hipGetLastError());
-  if (comm_allgather(c, c->g_send.p, c->g_recv.p, blk * 8)) return -1;
-  hipLaunchKernelGGL(k_unpack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (int)n,
-                     (int)rpr, c->rank, fl, slots, (const double *)c->g_recv.p);
-  BSA_HIP(c, hipGetLastError());
-  return 0;
-}
-
 // Without wind, K4' sets gs = tas, trk = hdg and gseast / gsnorth =
 // tas sin / cos(hdg) (traffic.py:455-460, bsa_kin_math.h): every rank derives
 // the other ranks' gseast / gsnorth from their gathered gs / trk with the same
@@ -200,10 +156,10 @@ static int sim_gather(Ctx *c) {
 // read-time gather of the per-rank ASAS outputs (only own rows are computed)
 static int sim_gather_asas(Ctx *c) {
   if (c->nranks == 1) return 0;
-  Fields fl{{(double *)c->s_atrk.p, (double *)c->s_atas.p, (double *)c->s_avs.p, (double *)c->s_aalt.p,
-             (double *)c->s_tas.p, (double *)c->s_hdg.p, nullptr, nullptr},
-            6, (uint8_t *)c->s_active.p};
-  return gather_fields(c, fl);
+  // (not synchronised here: the HomeBatch::run() of the read that follows does)
+  return gather_rows(c, {{c->s_atrk.p, 8}, {c->s_atas.p, 8}, {c->s_avs.p, 8}, {c->s_aalt.p, 8}, {c->s_tas.p, 8},
+                         {c->s_hdg.p, 8}, {c->s_active.p, 1}},
+                     false);
 }
 
 // the resident step's last CD call as "the last detect" (its counts are
@@ -236,111 +192,6 @@ void sim_release(Ctx *c) {
   halo_release(c);
   comm_release(c);
 }
-
-// ---- home order (host side): arrays cross the ABI in aircraft-index order
-// and live on the device in home order (Ctx::h2id_h).  HomeBatch is the one
-// way between the two: the arrays of a batch cross PCIe
-// through the pinned stage in ONE DMA, ONE kernel moves every field between
-// the device arrays and the staging area, one stream synchronisation per batch
-// (a host permutation loop and a synchronisation per array cost the ASAS
-// drop-in ~0.2 ms per array at 100k aircraft).  Upload and download of all
-// rows: index order in the staging area, stage[h2id[h]] <-> dev[h].  Download
-// of a rank's rows [hb, he): packed, stage[h - hb] = dev[h]; the host then
-// writes host[h2id[h]] for these rows and no other entry
-constexpr int kXferMax = 32;  // (bsa_sim_read_fms moves 25 arrays)
-enum XferMode { kXferUp, kXferDown, kXferDownPacked };
-struct XferFields {
-  void *dev[kXferMax];
-  unsigned long long off[kXferMax];  // byte offset of the field in the staging area
-  int esz[kXferMax];
-  int nf, mode;
-};
-template <typename T>
-__device__ __forceinline__ void xfer_one(void *dev, void *stage, int h, unsigned i, bool up) {
-  if (up) ((T *)dev)[h] = ((const T *)stage)[i];
-  else ((T *)stage)[i] = ((const T *)dev)[h];
-}
-__global__ __launch_bounds__(256) void k_home_xfer(int hb, int he, XferFields f, const unsigned *__restrict__ h2id,
-                                                   unsigned char *__restrict__ stage) {
-  const int h = hb + blockIdx.x * blockDim.x + threadIdx.x;
-  if (h >= he) return;
-  const unsigned i = f.mode == kXferDownPacked ? (unsigned)(h - hb) : h2id[h];
-  const bool up = f.mode == kXferUp;
-  for (int q = 0; q < f.nf; ++q) {
-    if (f.esz[q] == 8) xfer_one<unsigned long long>(f.dev[q], stage + f.off[q], h, i, up);
-    else if (f.esz[q] == 4) xfer_one<unsigned>(f.dev[q], stage + f.off[q], h, i, up);
-    else xfer_one<unsigned char>(f.dev[q], stage + f.off[q], h, i, up);
-  }
-}
-
-template <typename T>
-static void scatter_rows(void *dst, const void *src, const unsigned *ids, int64_t rows) {
-  for (int64_t r = 0; r < rows; ++r) ((T *)dst)[ids[r]] = ((const T *)src)[r];
-}
-
-struct HomeBatch {
-  Ctx *c;
-  int64_t hb, he;  // home rows (an upload: all)
-  XferFields f{};
-  const void *hsrc[kXferMax] = {};
-  void *hdst[kXferMax] = {};
-  size_t bytes = 0;
-  HomeBatch(Ctx *cc, bool upload, int64_t hb_ = 0, int64_t he_ = -1) : c(cc), hb(hb_), he(he_ < 0 ? cc->n : he_) {
-    f.mode = upload ? kXferUp : hb == 0 && he == c->n ? kXferDown : kXferDownPacked;
-  }
-  // upload: device array dev <- host src (index order); download: host dst <- dev
-  int add(const void *dev, const void *hsrc_, void *hdst_, int esz) {
-    if (f.nf == kXferMax && run()) return -1;
-    const int q = f.nf++;
-    f.dev[q] = const_cast<void *>(dev);
-    f.esz[q] = esz;
-    f.off[q] = bytes;
-    hsrc[q] = hsrc_;
-    hdst[q] = hdst_;
-    bytes += ((size_t)std::max<int64_t>(he - hb, 0) * esz + 255) / 256 * 256;
-    return 0;
-  }
-  int run() {
-    const int64_t rows = he - hb;
-    const bool up = f.mode == kXferUp;
-    const int nf = f.nf;
-    const size_t total = bytes;
-    f.nf = 0;  // (the batch is empty again, whatever happens below)
-    bytes = 0;
-    if (nf == 0 || rows <= 0) return 0;  // (a rank without rows: nothing to launch)
-    if (!ensure(c, c->xfer_stage, total, "transfer staging")) return -1;
-    unsigned char *st = (unsigned char *)c->xfer_stage.p;
-    // the host side through the pinned staging: one parallel host copy and
-    // ONE DMA of the whole batch (pin_stage, bsa_ctx.hip)
-    unsigned char *pin = pin_stage(c, total);
-    if (!pin) return -1;
-    HostCopy jobs[kXferMax];
-    if (up) {
-      for (int q = 0; q < nf; ++q) jobs[q] = HostCopy{pin + f.off[q], hsrc[q], (size_t)rows * f.esz[q]};
-      host_copy(jobs, nf);
-      BSA_HIP(c, hipMemcpyAsync(st, pin, total, hipMemcpyHostToDevice, c->stream));
-    }
-    XferFields g = f;
-    g.nf = nf;
-    hipLaunchKernelGGL(k_home_xfer, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, (int)hb, (int)he, g,
-                       (const unsigned *)c->h2id.p, st);
-    BSA_HIP(c, hipGetLastError());
-    if (!up) BSA_HIP(c, hipMemcpyAsync(pin, st, total, hipMemcpyDeviceToHost, c->stream));
-    BSA_HIP(c, hipStreamSynchronize(c->stream));
-    if (f.mode == kXferDown) {
-      for (int q = 0; q < nf; ++q) jobs[q] = HostCopy{hdst[q], pin + f.off[q], (size_t)rows * f.esz[q]};
-      host_copy(jobs, nf);
-    } else if (f.mode == kXferDownPacked) {
-      const unsigned *ids = c->h2id_h.data() + hb;
-      for (int q = 0; q < nf; ++q) {
-        const int e = f.esz[q];
-        const auto scatter = e == 8 ? scatter_rows<uint64_t> : e == 4 ? scatter_rows<uint32_t> : scatter_rows<uint8_t>;
-        scatter(hdst[q], pin + f.off[q], ids, rows);
-      }
-    }
-    return 0;
-  }
-};
 
 // the maps of a home order h2id_h (host + device) and this rank's lpos
 int set_home_maps(Ctx *c) {
@@ -581,12 +432,6 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long lon
   if (worst > c->cand_cap / kCandShards)
     c->cand_cap = std::max(2 * c->cand_cap, (unsigned long long)kCandShards * (worst + worst / 4 + 1024));
   return 0;
-}
-
-int sim_download_rows(Ctx *c, const void *dev0, void *host0, const void *dev1, void *host1, int esz) {
-  HomeBatch down(c, false, c->sim_rb, c->sim_re);
-  if ((host0 && down.add(dev0, nullptr, host0, esz)) || (host1 && down.add(dev1, nullptr, host1, esz))) return -1;
-  return down.run();
 }
 
 static int check_params(Ctx *c, const bsa_sim_params *p) {

@@ -23,36 +23,18 @@
 #include <algorithm>
 #include <vector>
 
-#include "bsa_internal.h"
+#include "bsa_xfer.h"
 
 namespace bsa {
 
-struct GatherDesc {
-  const void *src;
-  void *dst;
-  int esz;  // 1, 4 or 8
-};
-constexpr int kMaxGather = 40;
-struct GatherBatch {
-  GatherDesc d[kMaxGather];
-  int n;
-};
-
-// dst[newidx[o]] = src[o] for every kept o (newidx[o] >= 0), all arrays at once
-__global__ __launch_bounds__(256) void k_compact(int nold, const int *__restrict__ newidx, GatherBatch b) {
+// dst.p[q][newidx[o]] = src.p[q][o] for every kept o (newidx[o] >= 0), all arrays at once
+__global__ __launch_bounds__(256) void k_compact(int nold, const int *__restrict__ newidx, ArrayBatch src,
+                                                 ArrayBatch dst) {
   const int o = blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= nold) return;
   const int t = newidx[o];
   if (t < 0) return;
-  for (int q = 0; q < b.n; ++q) {
-    const GatherDesc &g = b.d[q];
-    if (g.esz == 8)
-      ((unsigned long long *)g.dst)[t] = ((const unsigned long long *)g.src)[o];
-    else if (g.esz == 4)
-      ((unsigned *)g.dst)[t] = ((const unsigned *)g.src)[o];
-    else
-      ((uint8_t *)g.dst)[t] = ((const uint8_t *)g.src)[o];
-  }
+  for (int q = 0; q < src.n; ++q) copy_elem(src.esz[q], dst.p[q], t, src.p[q], o);
 }
 
 struct PerAc {
@@ -131,89 +113,6 @@ static void remap_csr(const std::vector<unsigned> &p, const std::vector<unsigned
 // gathered pair keys) comes to every rank's host, so the change is the same
 // computation everywhere; afterwards the rows are re-partitioned over the new
 // n (set_rank_rows) and each rank keeps the bookkeeping of its new range.
-struct RowDesc {
-  char *p;
-  int esz;
-};
-constexpr int kMaxRowDesc = 32;
-struct RowBatch {
-  RowDesc d[kMaxRowDesc];
-  int n, rowbytes;
-};
-
-template <typename T>
-__device__ __forceinline__ void cp_row(char *dst, const char *src) {
-  *reinterpret_cast<T *>(dst) = *reinterpret_cast<const T *>(src);
-}
-__device__ __forceinline__ void cp_esz(int esz, char *dst, const char *src) {
-  if (esz == 8) cp_row<unsigned long long>(dst, src);
-  else if (esz == 4) cp_row<unsigned>(dst, src);
-  else *dst = *src;
-}
-
-// this rank's rows [rb, re) of every array into its block (array k at rpr x
-// (sum of the earlier arrays' element sizes))
-__global__ __launch_bounds__(256) void k_rows_pack(int rb, int re, int rpr, RowBatch b, char *__restrict__ send) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= rpr || rb + r >= re) return;
-  size_t off = 0;
-  for (int k = 0; k < b.n; ++k) {
-    const int e = b.d[k].esz;
-    cp_esz(e, send + off + (size_t)r * e, b.d[k].p + (size_t)(rb + r) * e);
-    off += (size_t)rpr * e;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_rows_unpack(int n, int rpr, int me, RowBatch b, const char *__restrict__ recv) {
-  const int h = blockIdx.x * blockDim.x + threadIdx.x;
-  if (h >= n) return;
-  const int q = h / rpr, r = h - q * rpr;
-  if (q == me) return;
-  const char *blk = recv + (size_t)q * rpr * b.rowbytes;
-  size_t off = 0;
-  for (int k = 0; k < b.n; ++k) {
-    const int e = b.d[k].esz;
-    cp_esz(e, b.d[k].p + (size_t)h * e, blk + off + (size_t)r * e);
-    off += (size_t)rpr * e;
-  }
-}
-
-static int gather_rows(Ctx *c, const std::vector<PerAc> &arrs) {
-  const int64_t n = c->n, rpr = c->sim_rpr;
-  std::vector<RowDesc> ds;
-  for (const PerAc &pa : arrs) {
-    if (!pa.b->p) continue;
-    for (int s = 0; s < pa.count; ++s) ds.push_back(RowDesc{(char *)pa.b->p + (size_t)s * n * pa.esz, pa.esz});
-  }
-  DevBuf snd, rcv;
-  struct Rel {
-    DevBuf *a, *b;
-    ~Rel() {
-      release(*a);
-      release(*b);
-    }
-  } rel{&snd, &rcv};
-  for (size_t k0 = 0; k0 < ds.size(); k0 += kMaxRowDesc) {
-    RowBatch b{};
-    for (size_t k = k0; k < ds.size() && b.n < kMaxRowDesc; ++k) {
-      b.d[b.n++] = ds[k];
-      b.rowbytes += ds[k].esz;
-    }
-    const size_t blk = (size_t)rpr * b.rowbytes;
-    if (!ensure(c, snd, std::max<size_t>(blk, 16), "row gather send") ||
-        !ensure(c, rcv, std::max<size_t>(blk * c->nranks, 16), "row gather recv"))
-      return -1;
-    hipLaunchKernelGGL(k_rows_pack, dim3((unsigned)((rpr + 255) / 256)), dim3(256), 0, c->stream, (int)c->sim_rb,
-                       (int)c->sim_re, (int)rpr, b, (char *)snd.p);
-    BSA_HIP(c, hipGetLastError());
-    if (comm_allgather(c, snd.p, rcv.p, blk)) return -1;
-    hipLaunchKernelGGL(k_rows_unpack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (int)n, (int)rpr,
-                       c->rank, b, (const char *)rcv.p);
-    BSA_HIP(c, hipGetLastError());
-  }
-  BSA_HIP(c, hipStreamSynchronize(c->stream));
-  return 0;
-}
 
 // every rank's vector of words on every rank (host)
 static int allgather_words(Ctx *c, const std::vector<unsigned> &mine, std::vector<std::vector<unsigned>> &all) {
@@ -278,7 +177,10 @@ static int multi_begin(Ctx *c, Multi &m) {
     BSA_HIP(c, hipMemcpyAsync((char *)m.gtcp.p + (size_t)rb * 8, c->tcpamax.p, (size_t)nr * 8, hipMemcpyDeviceToDevice,
                               c->stream));
   }
-  if (gather_rows(c, change_arrays(c, m))) return -1;
+  std::vector<ArrayRef> rows;  // every sub-array, for the shared row gather (bsa_xfer.hip)
+  for (const PerAc &pa : change_arrays(c, m))
+    for (int s = 0; pa.b->p && s < pa.count; ++s) rows.push_back({(char *)pa.b->p + (size_t)s * n * pa.esz, pa.esz});
+  if (gather_rows(c, rows, true)) return -1;
   if (!c->bk_ready) return 0;
   // resopairs: [ptr (rows + 1) | cols] of every rank
   std::vector<unsigned> p, q;
@@ -469,13 +371,13 @@ int bsa_sim_delete(bsa_ctx *cc, int64_t k, const int64_t *idx) {
   keep.map = map;
   map = bsa::DevBuf{};
   const int *dmap = (const int *)keep.map.p;
-  bsa::GatherBatch gb{};
+  bsa::ArrayBatch src{}, dst{};
   auto launch = [&]() -> int {
-    if (!gb.n) return 0;
+    if (!src.n) return 0;
     hipLaunchKernelGGL(bsa::k_compact, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (int)n, dmap,
-                       gb);
+                       src, dst);
     BSA_HIP(c, hipGetLastError());
-    gb.n = 0;
+    src.n = 0;
     return 0;
   };
   const size_t NA = bsa::rows_alloc(c, nn);
@@ -485,9 +387,10 @@ int bsa_sim_delete(bsa_ctx *cc, int64_t k, const int64_t *idx) {
     if (!bsa::ensure(c, fresh[a], (pa.count == 1 ? NA : (size_t)nn) * pa.esz * pa.count, "compacted traffic array"))
       return -1;
     for (int s = 0; s < pa.count; ++s) {
-      if (gb.n == bsa::kMaxGather && launch()) return -1;
-      gb.d[gb.n++] = bsa::GatherDesc{(const char *)pa.b->p + (size_t)s * n * pa.esz,
-                                     (char *)fresh[a].p + (size_t)s * nn * pa.esz, pa.esz};
+      if (src.n == bsa::kBatchMax && launch()) return -1;
+      src.p[src.n] = (char *)pa.b->p + (size_t)s * n * pa.esz;
+      dst.p[src.n] = (char *)fresh[a].p + (size_t)s * nn * pa.esz;
+      src.esz[src.n++] = pa.esz;
     }
   }
   if (launch()) return -1;

@@ -2,7 +2,7 @@
 contexts in one process form the ranks of the row-sharded resident sim through
 the in-process group transport (bsa_group_*, bsa_comm.hip), one host thread per
 rank.  Everything the RCCL path does between ranks runs here too -- the state
-all-gather before each CD (k_pack / k_unpack), the gate all-reduce, the global
+all-gather before each CD, the read-time row gather, the gate all-reduce, the global
 unique-pair key all-gather, the C2 rank-order pair gather -- only the transport
 differs (device-to-device copies instead of xGMI).
 
@@ -906,6 +906,33 @@ def test_reads_on_a_rank_without_rows(ctx):
     for _, _, st in res:
         for k, v in exp_st.items():
             assert np.array_equal(st[k], v), k
+
+
+def test_sharded_read_equals_world1_bytewise(ctx):
+    """Three ranks, 1100 aircraft (rpr = 512: 512 + 512 + 76 rows, the last block
+    of the row gather mostly padding), MVP with resume_nav (asas.active a mix of
+    0 and 1), 5 steps with CD every step: bsa_sim_read on every rank -- the state
+    all-gather plus the typed row gather of asas.trk / tas / vs / alt, tas, hdg
+    (8 bytes) and active (1 byte) -- equals the one-rank read in every key, on
+    the arrays' raw bytes (-0.0 is not +0.0)."""
+    t = synth.box(1100, 200.0, seed=151)
+    init = resident.initial_state(t)
+    p = resident.params(cd_every=1, resume_nav=True)
+    exp = world1(init, p, 5, ctx).read()
+    assert exp['active'].any() and not exp['active'].all()   # (a property of the seed)
+
+    def rank(r, c, g):
+        sim = resident.ResidentSim(init, p, ctx=c, rank=r, world=3, group=g)
+        sim.step(5)
+        return sim.read(), sim.row_ids()
+
+    res = run_ranks(3, rank)
+    assert [len(i) for _, i in res] == [512, 512, 76]
+    for r, (got, _) in enumerate(res):
+        assert got.keys() == exp.keys()
+        for k, v in exp.items():
+            assert got[k].dtype == v.dtype and np.array_equal(got[k].view(np.uint8), v.view(np.uint8)), \
+                'rank %d %s' % (r, k)
 
 
 def test_sharded_update_keeps_the_kept_state_collective(ctx):
