@@ -430,7 +430,10 @@ def test_resident_openap_phase_matches_oracle(ctx):
 def test_resident_row_bucket_overflow_retry_is_exact(ctx):
     """K2 row buckets one pair wide overflow on the first dense row: the
     resident step aborts, widens them and re-runs (bsa_sim_step's retry) --
-    the state after several MVP steps equals the default run's bitwise."""
+    the state after several MVP steps equals the default run's bitwise.  The
+    same start on another fresh context, one step at a time, also equals the
+    oracle step: the step that overflowed and re-ran, and the next one at the
+    grown width."""
     from bluesky_amd import _lib
     t = synth.box(1500, 60.0, seed=53)
     init = resident.initial_state(t)
@@ -447,6 +450,27 @@ def test_resident_row_bucket_overflow_retry_is_exact(ctx):
         for k in exp:
             assert np.array_equal(got[k], exp[k]), k
         assert sim.stats()['n_conf'] == ref.stats()['n_conf'] > 0
+    finally:
+        c.close()
+    c = _lib.Context(0)
+    try:
+        c.set_row_bucket(1)
+        sim = resident.ResidentSim(init, p, ctx=c)
+        op = oracle_params(p)
+        prev = dict(init)
+        prev.update(asas_trk=init['trk'].copy(), asas_tas=init['tas'].copy(),
+                    asas_vs=np.zeros(t.ntraf), active=np.zeros(t.ntraf, bool))
+        for k in range(2):
+            want = ostep.sim_step(prev, op, do_cd=True)
+            sim.step(1)
+            got = full_state(init, sim.read())
+            compare(got, want, k)
+            assert sim.stats()['n_conf'] == want['n_conf'] > 0
+            prev = got
+        sim.step(2)
+        got = sim.read()
+        for k in exp:
+            assert np.array_equal(got[k], exp[k]), k
     finally:
         c.close()
 
