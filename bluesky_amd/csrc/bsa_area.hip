@@ -238,12 +238,10 @@ static AreaArgs sect_args(Ctx *c, bool seed) {
   return a;
 }
 
-// after the last stage of a step: the step counter, and the pass when it reaches a multiple of the cadence.
-// Reads simulation state only; an aborted batch replays the counter (batch_rollback) and the aborted and later
-// steps' passes returned behind the sticky word, so no update is counted twice
-int sect_step(Ctx *c) {
-  c->sect_ctr++;
-  if (c->sect_ctr % c->sect_every != 0) return 0;
+// after the last stage of a step with which the step counter reaches a multiple of the cadence
+// (StepPlan::sect_pass).  Reads simulation state only; an aborted batch replays the counter (batch_rollback) and
+// the aborted and later steps' passes returned behind the sticky word, so no update is counted twice
+int sect_sim_launch(Ctx *c) {
   const AreaArgs a = sect_args(c, false);
   hipLaunchKernelGGL(k_sect_zero, dim3(1), dim3(kSectArrCum), 0, c->stream, a.sticky, a.sect);
   BSA_HIP(c, hipGetLastError());
@@ -271,7 +269,7 @@ void sect_off(Ctx *c) {
   c->sim_sect = false;
   c->sect_idx.clear();
   c->sect_gone.clear();
-  c->sect_ctr = 0;
+  c->clk.sect_ctr = 0;
 }
 
 }  // namespace bsa
@@ -343,8 +341,8 @@ extern "C" int bsa_sim_sectors_poll(bsa_ctx *cc, uint64_t *n_tot, uint64_t *arri
   const int off[5] = {bsa::kSectTot, bsa::kSectArr, bsa::kSectLeft, bsa::kSectArrCum, bsa::kSectLeftCum};
   for (int q = 0; q < 5; ++q)
     for (size_t k = 0; dst[q] && k < c->sect_idx.size(); ++k) dst[q][k] = h[off[q] + k];
-  if (updates) *updates = c->sect_ctr / c->sect_every;
-  if (step) *step = c->sect_ctr / c->sect_every * c->sect_every;
+  if (updates) *updates = c->clk.sect_ctr / c->sect_every;
+  if (step) *step = c->clk.sect_ctr / c->sect_every * c->sect_every;
   bsa::HomeBatch down(c, false, c->sim_rb, c->sim_re);  // this rank's rows of the masks, index order (NULL: left out)
   if ((cur_words && down.add(c->s_scur.p, nullptr, cur_words, 8)) ||
       (prev_words && down.add(c->s_sprev.p, nullptr, prev_words, 8)))

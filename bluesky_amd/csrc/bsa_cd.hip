@@ -182,7 +182,7 @@ static int decide_hk(Ctx *c, DetectPlan &p, bool host_decides) {
       (build ? c->hk_builds : c->hk_keeps)++;
       if (detect_env().hk_trace)
         fprintf(stderr, "[bsa hk] rank %d detect %lld: %s (tvalid %d, step %lld)\n", c->rank, (long long)hm,
-                build ? "build" : "keep", p.tvalid ? 1 : 0, (long long)c->sim_steps);
+                build ? "build" : "keep", p.tvalid ? 1 : 0, (long long)c->clk.steps);
     }
   } else if (p.tpr) {
     c->hk.drop();  // a device-decided detect: the build history is no longer the host's

@@ -71,12 +71,12 @@ static int feed_request(Ctx *c) {
   }
   if (!c->feed_ev) BSA_HIP(c, hipEventCreateWithFlags(&c->feed_ev, hipEventDisableTiming));
   // inconf / tcpamax hold the last CD call's rows (the rank's rows once a CD step ran)
-  const bool have_cd = c->sim_cd_calls > 0 && c->inconf.p && c->last_rb == rb && c->last_re == c->sim_re;
+  const bool have_cd = c->clk.cd_calls > 0 && c->inconf.p && c->last_rb == rb && c->last_re == c->sim_re;
   FeedSrc s;
   const void *src[kFeedF64 - 1] = {c->own[0].p, c->own[1].p, c->own[4].p, c->s_tas.p,
                                    c->s_altprev.p, c->own[3].p, c->own[2].p, c->own[5].p};
   for (int f = 0; f < kFeedF64 - 1; ++f) s.f[f] = (const double *)src[f];
-  s.stepped = c->sim_steps > 0;
+  s.stepped = c->clk.steps > 0;
   s.tcpamax = have_cd ? (const double *)c->tcpamax.p : nullptr;
   s.inconf = have_cd ? (const uint8_t *)c->inconf.p : nullptr;
   s.asasn = (const float *)c->s_asn.p;
@@ -88,7 +88,7 @@ static int feed_request(Ctx *c) {
   BSA_HIP(c, hipMemcpyAsync(c->feed_host, c->feed_dev.p, bytes, hipMemcpyDeviceToHost, c->stream));
   BSA_HIP(c, hipEventRecord(c->feed_ev, c->stream));
   c->feed_pending = true;
-  c->feed_steps = c->sim_steps;
+  c->feed_steps = c->clk.steps;
   c->feed_rb = rb;
   c->feed_re = c->sim_re;
   return 0;

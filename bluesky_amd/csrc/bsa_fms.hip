@@ -5,6 +5,7 @@
 // per-aircraft arrays are SoA; the route table (8 doubles = 64 B per
 // waypoint) stays in HBM and only a lane that switches waypoint reads its row.
 #include "bsa_fms_math.h"
+#include "bsa_xfer.h"
 
 #pragma clang fp contract(off)
 
@@ -220,6 +221,12 @@ int fms_check_routes(Ctx *c, const char *who, int64_t n, int64_t nrows, const in
   return 0;
 }
 
+void fms_off(Ctx *c) {
+  c->sim_fms = c->sim_recovery = false;
+  c->clk.fms_simt = 0.0, c->clk.fms_t0 = -999.0, c->clk.fms_ticks = 0;
+  geovec_off(c);  // selspd / selvs live in the FMS arrays
+}
+
 }  // namespace bsa
 
 using bsa::Ctx;
@@ -385,5 +392,104 @@ extern "C" int bsa_fms_recover(bsa_ctx *cc, int64_t n, int64_t nrows, const doub
     BSA_HIP(c, hipMemcpyAsync(ff.flags[q], d1[q], (size_t)n, hipMemcpyDeviceToHost, c->stream));
   BSA_HIP(c, hipMemcpyAsync(iactwp, d4[0], (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
   BSA_HIP(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---- the resident step's guidance: set / read, waypoint recovery
+extern "C" int bsa_sim_set_fms(bsa_ctx *cc, int64_t nrows, const double *route_rows, const int32_t *rt_off,
+                               const int32_t *rt_n, const int32_t *iactwp, const bsa_fms_state *st, double simt,
+                               double t0) {
+  Ctx *c = (Ctx *)cc;
+  if (!c) return -1;
+  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_set_fms before bsa_sim_init");
+  BSA_HIP(c, hipSetDevice(c->device));
+  if (!route_rows) {
+    bsa::fms_off(c);
+    return 0;
+  }
+  if (nrows < 0 || nrows > 0x7fffffff / 8) return bsa::fail(c, "bsa_sim_set_fms: bad route row count");
+  if (!rt_off || !rt_n || !iactwp || !st) return bsa::fail(c, "bsa_sim_set_fms: NULL array");
+  const bsa::FmsFields ff = bsa::fms_fields(*st);
+  for (auto q : ff.reals)
+    if (!q) return bsa::fail(c, "bsa_sim_set_fms: NULL array");
+  for (auto q : ff.flags)
+    if (!q) return bsa::fail(c, "bsa_sim_set_fms: NULL array");
+  if (!std::isfinite(simt) || std::isnan(t0)) return bsa::fail(c, "bsa_sim_set_fms: simt / t0 not finite");
+  const int64_t n = c->n;
+  if (bsa::fms_check_routes(c, "bsa_sim_set_fms", n, nrows, rt_off, rt_n, iactwp, st->swlnav)) return -1;
+  c->sim_fms = false;
+  const bool gv_on = c->sim_gv;  // a new FMS state keeps the geovectors; a failed upload leaves both off
+  c->sim_gv = false;
+  const size_t N = (size_t)n;
+  if (!bsa::ensure(c, c->s_fmsr, bsa::kFmsReals * N * 8, "FMS state") || !bsa::ensure(c, c->s_fmsf, bsa::kFmsFlags * N, "FMS flags") ||
+      !bsa::ensure(c, c->s_fmsi, bsa::kFmsInts * N * 4, "route indices") ||
+      !bsa::ensure(c, c->s_fmsrows, (size_t)nrows * 64 + 64, "route table") ||
+      !bsa::ensure(c, c->s_fmsur, bsa::kFmsUndoReals * N * 8, "FMS undo set") || !bsa::ensure(c, c->s_fmsuf, 2 * N, "FMS undo flags") ||
+      !bsa::ensure(c, c->s_fmsui, N * 4, "FMS undo waypoints"))
+    return -1;
+  bsa::HomeBatch up(c, true);
+  const int32_t *ints[bsa::kFmsInts] = {iactwp, rt_off, rt_n};
+  for (int q = 0; q < bsa::kFmsReals; ++q)
+    if (up.add((double *)c->s_fmsr.p + q * N, ff.reals[q], nullptr, 8)) return -1;
+  for (int q = 0; q < bsa::kFmsFlags; ++q)
+    if (up.add((uint8_t *)c->s_fmsf.p + q * N, ff.flags[q], nullptr, 1)) return -1;
+  for (int q = 0; q < bsa::kFmsInts; ++q)
+    if (up.add((int32_t *)c->s_fmsi.p + q * N, ints[q], nullptr, 4)) return -1;
+  if (up.run()) return -1;
+  if (nrows) BSA_HIP(c, hipMemcpyAsync(c->s_fmsrows.p, route_rows, (size_t)nrows * 64, hipMemcpyHostToDevice, c->stream));
+  BSA_HIP(c, hipStreamSynchronize(c->stream));
+  c->clk.fms_simt = simt;
+  c->clk.fms_t0 = t0;
+  c->clk.fms_ticks = 0;
+  c->sim_fms = true;
+  c->sim_gv = gv_on;
+  return 0;
+}
+
+extern "C" int bsa_sim_set_recovery(bsa_ctx *cc, int on) {
+  Ctx *c = (Ctx *)cc;
+  if (!c) return -1;
+  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_set_recovery before bsa_sim_init");
+  if (on && !c->sim_fms) return bsa::fail(c, "waypoint recovery needs the FMS guidance (bsa_sim_set_fms)");
+  c->sim_recovery = on != 0;
+  return 0;
+}
+
+extern "C" int bsa_sim_read_dropcount(bsa_ctx *cc, int32_t *count) {
+  Ctx *c = (Ctx *)cc;
+  if (!c || !count) return -1;
+  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_read_dropcount before bsa_sim_init");
+  BSA_HIP(c, hipSetDevice(c->device));
+  bsa::HomeBatch down(c, false, c->sim_rb, c->sim_re);
+  if (down.add(c->s_dropcnt.p, nullptr, count, 4)) return -1;
+  return down.run();
+}
+
+extern "C" int bsa_sim_read_fms(bsa_ctx *cc, const bsa_fms_state *st, int32_t *iactwp, double *ap_trk, double *ap_tas,
+                                double *ap_alt, double *ap_vs, double *selalt, double *simt, double *t0,
+                                int64_t *ticks) {
+  Ctx *c = (Ctx *)cc;
+  if (!c) return -1;
+  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_read_fms before bsa_sim_init");
+  if (!c->sim_fms) return bsa::fail(c, "no FMS state: bsa_sim_set_fms is off");
+  BSA_HIP(c, hipSetDevice(c->device));
+  const size_t N = (size_t)c->n;
+  bsa::HomeBatch down(c, false, c->sim_rb, c->sim_re);
+  if (st) {
+    const bsa::FmsFields ff = bsa::fms_fields(*st);
+    for (int q = 0; q < bsa::kFmsReals; ++q)
+      if (ff.reals[q] && down.add((const double *)c->s_fmsr.p + q * N, nullptr, ff.reals[q], 8)) return -1;
+    for (int q = 0; q < bsa::kFmsFlags; ++q)
+      if (ff.flags[q] && down.add((const uint8_t *)c->s_fmsf.p + q * N, nullptr, ff.flags[q], 1)) return -1;
+  }
+  if (iactwp && down.add(c->s_fmsi.p, nullptr, iactwp, 4)) return -1;
+  double *tg[5] = {ap_trk, ap_tas, ap_alt, ap_vs, selalt};
+  const void *src[5] = {c->s_aptrk.p, c->s_aptas.p, c->s_apalt.p, c->s_apvs.p, c->s_selalt.p};
+  for (int q = 0; q < 5; ++q)
+    if (tg[q] && down.add(src[q], nullptr, tg[q], 8)) return -1;
+  if (down.run()) return -1;
+  if (simt) *simt = c->clk.fms_simt;
+  if (t0) *t0 = c->clk.fms_t0;
+  if (ticks) *ticks = c->clk.fms_ticks;
   return 0;
 }

@@ -166,12 +166,9 @@ static GeovecArgs gv_sim_args(Ctx *c) {
   return a;
 }
 
-bool geovec_applies_at(const Ctx *c) { return c->gv_ctr > 0 && c->gv_ctr % c->gv_every == 0; }
+bool geovec_applies_at(const Ctx *c) { return c->clk.gv_ctr > 0 && c->clk.gv_ctr % c->gv_every == 0; }
 
-int geovec_sim_step(Ctx *c) {
-  const bool apply = geovec_applies_at(c);
-  c->gv_ctr++;
-  if (!apply) return 0;
+int geovec_sim_launch(Ctx *c) {
   // (the aircraft count may have changed since the last application: bsa_sim_delete)
   if (!ensure(c, c->gv_undo, (size_t)c->n * 32, "geovector undo set")) return -1;
   const GeovecArgs a = gv_sim_args(c);
@@ -195,7 +192,7 @@ int geovec_sim_restore(Ctx *c) {
 void geovec_off(Ctx *c) {
   c->sim_gv = false;
   c->gv_n = 0;
-  c->gv_ctr = 0;
+  c->clk.gv_ctr = 0;
 }
 
 }  // namespace bsa
@@ -241,7 +238,8 @@ extern "C" int bsa_sim_geovec_stats(bsa_ctx *cc, int64_t *applies, uint64_t *cha
   Ctx *c = (Ctx *)cc;
   if (!c) return -1;
   if (!c->sim_ready || !c->sim_gv) return bsa::fail(c, "bsa_sim_geovec_stats: no geovectors (bsa_sim_set_geovectors)");
-  if (applies) *applies = c->gv_ctr >= 1 ? (c->gv_ctr - 1) / c->gv_every : 0;  // steps k = every, 2 every, ... < gv_ctr
+  const int64_t ctr = c->clk.gv_ctr;
+  if (applies) *applies = ctr >= 1 ? (ctr - 1) / c->gv_every : 0;  // steps k = every, 2 every, ... < gv_ctr
   if (changed4_total) {
     BSA_HIP(c, hipSetDevice(c->device));
     unsigned long long h[4];

@@ -196,6 +196,19 @@ int pin_issued(Ctx *c);
 bool ensure_keep(Ctx *c, DevBuf &b, size_t bytes, const char *what);  // grows, keeps contents
 void release(DevBuf &b);
 
+// The host clocks of the resident step: everything the host counts per enqueued step, as one
+// value.  step_advance (bsa_sim.hip) is the one function that moves them over a step, after the step is
+// enqueued; a batch saves them with one assignment and replays them with the same function.  Each stage reads
+// its own clock, its _off resets it
+struct StepClocks {
+  int64_t steps = 0, cd_calls = 0;         // completed steps; CD calls (bsa_sim_cd's among them)
+  double fms_simt = 0.0, fms_t0 = -999.0;  // FMS: the simt of the next step, Autopilot.t0,
+  int64_t fms_ticks = 0;                   // ... the ticks of completed steps
+  int64_t turb_call = 0;                   // turbulence (3.25): the call number of the next step's draws
+  int64_t sect_ctr = 0;                    // sectors (3.27): steps since bsa_sim_set_sectors
+  int64_t gv_ctr = 0;                      // geovectors (3.28): steps completed since bsa_sim_set_geovectors
+};
+
 struct Ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -350,7 +363,8 @@ struct Ctx {
   bool sim_ready = false;
   DevBuf nx_alt, nx_vs, nx_gse, nx_gsn;  // K2 fused with K4' (one rank): alt / vs / gseast / gsnorth double buffers
   bsa_sim_params simp{};
-  int64_t sim_steps = 0, sim_cd_calls = 0, sim_rb = 0, sim_re = 0, sim_rpr = 0;
+  StepClocks clk;
+  int64_t sim_rb = 0, sim_re = 0, sim_rpr = 0;
   int64_t sim_last_conf = 0, sim_last_los = 0;
   bool sim_gathered = true;  // replicas consistent with every rank's rows
   bool sim_gs_derivable = false;  // gseast / gsnorth of every row follow from gs / trk (K4' without wind ran)
@@ -420,26 +434,25 @@ struct Ctx {
   double wf3_altstep = 0.0;
 
   // Turbulence.Woosh in the resident step (bsa_sim_set_turbulence, bsa_turb.hip): sd as given
-  // (clamped where the scale is made), the seed, and the call number of the next step's draws -- the host's,
-  // advanced per enqueued step while on and replayed after an abort.  turb_stage: bsa_turb_draws / _apply's arrays
+  // (clamped where the scale is made) and the seed; the call number of the next step's draws is clk.turb_call.
+  // turb_stage: bsa_turb_draws / _apply's arrays
   DevBuf turb_stage;
   bool sim_turb = false;
   double turb_sd[3] = {0.0, 0.0, 0.0};
   unsigned long long turb_seed = 0;
-  int64_t turb_call = 0;
 
   // The area filter (bsa_area.hip).  area_stage: bsa_area_inside's points, masks, counts and table
   DevBuf area_stage;
   // Sector occupancy in the resident step (bsa_sim_set_areas / _set_sectors): the packed area
   // table (host) and its vertices (device); the sectors' shapes in sector order (sect_tab), their counts
   // (sect_cnt, kSect* words), the mask word of every aircraft at the last update (s_scur) and at the one before
-  // (s_sprev), both per-aircraft arrays (kSimArrays).  sect_ctr: steps since bsa_sim_set_sectors, the host's,
-  // replayed after an abort; sect_gone: deleted aircraft's words until the next bsa_sim_sectors_deleted
+  // (s_sprev), both per-aircraft arrays (kSimArrays).  sect_every: the cadence, in steps of clk.sect_ctr;
+  // sect_gone: deleted aircraft's words until the next bsa_sim_sectors_deleted
   std::vector<bsa_area_shape> area_tab;
   DevBuf area_verts, sect_tab, sect_cnt, s_scur, s_sprev;
   bool sim_sect = false;
   std::vector<int32_t> sect_idx;
-  int64_t sect_every = 1, sect_ctr = 0;
+  int64_t sect_every = 1;
   struct SectGone {
     int64_t pos;
     unsigned long long word;
@@ -449,12 +462,11 @@ struct Ctx {
   // Geovectoring (bsa_geovec.hip).  gv_stage: bsa_geovec_apply's arrays and tables.  In the
   // resident step (bsa_sim_set_geovectors): the rows (gv_tab, shape = row number) and their shapes in list order
   // (gv_shapes), the undo set an applying launch fills first (gv_undo, 4 x n fp64: selspd ap_trk selvs selalt at
-  // the step's start), the counters (gv_cnt, kGvCntWords u64).  gv_ctr: steps completed since
-  // bsa_sim_set_geovectors, the host's, replayed after an abort
+  // the step's start), the counters (gv_cnt, kGvCntWords u64).  gv_every: the cadence, in steps of clk.gv_ctr
   DevBuf gv_stage, gv_tab, gv_shapes, gv_undo, gv_cnt;
   bool sim_gv = false;
   int gv_n = 0;
-  int64_t gv_every = 1, gv_ctr = 0;
+  int64_t gv_every = 1;
 
   // standalone geo matrices (bsa_geo.hip)
   DevBuf geo_in, geo_pts, geo_out;
@@ -483,12 +495,9 @@ struct Ctx {
   // home order: the 15 fp64 arrays of bsa_fms_state (15 x n), its 4 flags
   // (4 x n u8), iactwp / rt_off / rt_n (3 x n int32), the route table, and the
   // undo set a ticking launch fills first (17 x n fp64: the 13 mutable reals,
-  // ap_trk / ap_alt / ap_vs / selalt; 2 x n u8; n int32).  fms_simt: the simt of
-  // the next step; fms_t0: Autopilot.t0; fms_ticks: ticks of completed steps
+  // ap_trk / ap_alt / ap_vs / selalt; 2 x n u8; n int32).  Its clock: clk.fms_*
   DevBuf s_fmsr, s_fmsf, s_fmsi, s_fmsrows, s_fmsur, s_fmsuf, s_fmsui;
   bool sim_fms = false;
-  double fms_simt = 0.0, fms_t0 = -999.0;
-  int64_t fms_ticks = 0;
   // NORESO / RESOOFF membership (bsa_sim_set_reso_lists, u8 in home order) and
   // the rows whose ResumeNav dropped a pair in the last CD call (u8, home order)
   // and how many pairs it dropped per row (int32: waypoint recovery runs once per pair)
@@ -666,15 +675,16 @@ WindField wind_field(const Ctx *c);  // device view of the context's 2-D field (
 // wind_field_pa(c), the per-aircraft wind it writes
 int wind3d_launch(Ctx *c, int64_t rb, int64_t re, int64_t n, const double *lat, const double *lon, const double *alt);
 WindField wind_field_pa(const Ctx *c);
-// Turbulence.Woosh of the step (bsa_turb.hip): k_sim_turb on home rows [rb, re), call number Ctx::turb_call,
-// enqueued after the step's K4' on the arrays it wrote
+// Turbulence.Woosh of the step (bsa_turb.hip): k_sim_turb on home rows [rb, re), call number clk.turb_call,
+// enqueued after the step's K4' on the arrays it wrote.  turb_off: off, the call number back at 0
 int turb_sim_launch(Ctx *c, int64_t rb, int64_t re, const unsigned *sticky, const double *trk, double *lat,
                     double *lon, double *alt);
+void turb_off(Ctx *c);
 
-// Sector occupancy (bsa_area.hip): sect_step after the last stage of every step while Ctx::sim_sect (the step
-// counter, and the pass when it reaches a multiple of the cadence); sect_note_deleted by bsa_sim_delete before
-// anything moves; sect_off forgets the sectors
-int sect_step(Ctx *c);
+// Sector occupancy (bsa_area.hip): sect_sim_launch after the last stage of a step whose StepPlan::sect_pass is
+// set (clk.sect_ctr + 1 a multiple of the cadence); sect_note_deleted by bsa_sim_delete before anything moves;
+// sect_off forgets the sectors
+int sect_sim_launch(Ctx *c);
 int sect_note_deleted(Ctx *c, int64_t k, const int64_t *idx);
 void sect_off(Ctx *c);
 // the area table as the kernels read it (bsa_area.hip): every argument checked, corners and levels sorted, the
@@ -683,13 +693,13 @@ int area_pack(Ctx *c, const char *who, int64_t nshapes, const bsa_area_shape *sh
               const double *verts, std::vector<bsa_area_shape> *out);
 bool area_env_nocull();
 
-// Geovectoring in the resident step (bsa_geovec.hip).  geovec_sim_step: first on the stream of
-// the step about to be enqueued while Ctx::sim_gv -- the launch when the steps completed since
-// bsa_sim_set_geovectors are a positive multiple of the cadence, then the counter.  geovec_applies_at: does the
-// step at the counter's present value apply?  geovec_sim_restore: the undo set back into the state,
-// stream-ordered (after an aborted applying step).  geovec_off forgets the geovectors
-int geovec_sim_step(Ctx *c);
+// Geovectoring in the resident step (bsa_geovec.hip).  geovec_applies_at: does the step at
+// clk.gv_ctr apply -- are the steps completed since bsa_sim_set_geovectors a positive multiple of the cadence
+// (StepPlan::gv_apply)?  geovec_sim_launch: the launch of such a step, first on its stream.
+// geovec_sim_restore: the undo set back into the state, stream-ordered (after an aborted applying step).
+// geovec_off forgets the geovectors
 bool geovec_applies_at(const Ctx *c);
+int geovec_sim_launch(Ctx *c);
 int geovec_sim_restore(Ctx *c);
 void geovec_off(Ctx *c);
 
@@ -699,16 +709,19 @@ void geovec_off(Ctx *c);
 // is added to fuel_used first (false for the first step of a re-run attempt).
 int forces_consts(Ctx *c);
 int forces_sim_launch(Ctx *c, bool commit);
+void forces_off(Ctx *c);
 
 // Autopilot guidance (bsa_fms.hip).  fms_check_routes: every index the kernels
 // use unguarded, on host arrays.  fms_sim_launch: k_sim_fms of the step about
 // to be enqueued, on this rank's rows (tick: the whole FMS part, after saving
 // the undo set; else ap.tas only).  fms_sim_restore: the undo set back into
-// the state, stream-ordered (after an aborted tick step).
+// the state, stream-ordered (after an aborted tick step).  fms_off: guidance
+// off, and with it what lives in its arrays: waypoint recovery, the geovectors
 int fms_check_routes(Ctx *c, const char *who, int64_t n, int64_t nrows, const int32_t *rt_off, const int32_t *rt_n,
                      const int32_t *iactwp, const uint8_t *swlnav);
 int fms_sim_launch(Ctx *c, bool tick);
 int fms_sim_restore(Ctx *c);
+void fms_off(Ctx *c);
 // waypoint recovery of the CD step just enqueued (after bk_apply, before K4'): k_sim_recover on this rank's rows
 int fms_sim_recover(Ctx *c);
 inline bool fms_ticks_at(double simt, double t0) { return t0 + 1.01 < simt || simt < t0 || simt < 1.01; }

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "bsa_perf_math.h"
+#include "bsa_xfer.h"
 
 #pragma clang fp contract(off)
 
@@ -111,9 +112,81 @@ int forces_sim_launch(Ctx *c, bool commit) {
   return 0;
 }
 
+void forces_off(Ctx *c) { c->sim_forces = false; }
+
 }  // namespace bsa
 
 using bsa::Ctx;
+
+extern "C" int bsa_sim_set_forces(bsa_ctx *cc, int64_t ntypes, const double *ftable, const double *mass) {
+  Ctx *c = (Ctx *)cc;
+  if (!c) return -1;
+  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_set_forces before bsa_sim_init");
+  BSA_HIP(c, hipSetDevice(c->device));
+  if (!ftable) {
+    bsa::forces_off(c);
+    return 0;
+  }
+  if (!c->sim_perf) return bsa::fail(c, "bsa_sim_set_forces needs the type table and index of bsa_sim_set_perf");
+  if (!mass) return bsa::fail(c, "bsa_sim_set_forces: NULL mass");
+  if (ntypes != c->sim_ntypes)
+    return bsa::fail(c, "bsa_sim_set_forces: %lld force-table rows for the %lld types of bsa_sim_set_perf",
+                     (long long)ntypes, (long long)c->sim_ntypes);
+  if (ntypes > bsa::perf::kForceTypesMax)
+    return bsa::fail(c, "bsa_sim_set_forces: %lld types, at most %d", (long long)ntypes, bsa::perf::kForceTypesMax);
+  // thr0 = engnum x engthrust divides the thrust ratio of every fixed wing
+  std::vector<double> tab24((size_t)ntypes * bsa::kin::kPerfCols);
+  BSA_HIP(c, hipMemcpyAsync(tab24.data(), c->s_ptab.p, tab24.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  BSA_HIP(c, hipStreamSynchronize(c->stream));
+  for (int64_t t = 0; t < ntypes; ++t) {
+    const double thr0 = ftable[t * bsa::perf::kForceCols + 1] * ftable[t * bsa::perf::kForceCols + 2];
+    if (tab24[(size_t)t * bsa::kin::kPerfCols + 22] == 1.0 && !std::isfinite(thr0))
+      return bsa::fail(c, "type %lld: engnum x engthrust is not finite", (long long)t);
+  }
+  const int64_t n = c->n;
+  const size_t N8 = (size_t)n * 8;
+  if (!bsa::ensure(c, c->s_ftab, (size_t)ntypes * bsa::perf::kForceCols * 8, "OpenAP force table") ||
+      !bsa::ensure(c, c->s_fmass, N8, "mass") || !bsa::ensure(c, c->s_fout, 6 * N8, "OpenAP forces") ||
+      !bsa::ensure(c, c->s_fused, N8, "fuel used") || !bsa::ensure(c, c->s_fpend, N8, "pending fuel"))
+    return -1;
+  if (bsa::forces_consts(c)) return -1;
+  BSA_HIP(c, hipMemcpyAsync(c->s_ftab.p, ftable, (size_t)ntypes * bsa::perf::kForceCols * 8, hipMemcpyHostToDevice,
+                            c->stream));
+  bsa::HomeBatch up(c, true);
+  if (up.add(c->s_fmass.p, mass, nullptr, 8) || up.run()) return -1;
+  // switching on: outputs (perf.bank among them) and the fuel accumulators start at 0
+  BSA_HIP(c, hipMemsetAsync(c->s_fout.p, 0, 6 * N8, c->stream));
+  BSA_HIP(c, hipMemsetAsync(c->s_fused.p, 0, N8, c->stream));
+  BSA_HIP(c, hipMemsetAsync(c->s_fpend.p, 0, N8, c->stream));
+  BSA_HIP(c, hipStreamSynchronize(c->stream));
+  c->sim_forces = true;
+  return 0;
+}
+
+extern "C" int bsa_sim_read_forces(bsa_ctx *cc, double *cd0, double *drag, double *thrustratio, double *thrust,
+                                   double *fuelflow, double *bank, double *fuel_used) {
+  Ctx *c = (Ctx *)cc;
+  if (!c) return -1;
+  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_read_forces before bsa_sim_init");
+  if (!c->sim_forces) return bsa::fail(c, "no forces: bsa_sim_set_forces is off");
+  BSA_HIP(c, hipSetDevice(c->device));
+  const int64_t n = c->n, rb = c->sim_rb, re = c->sim_re;
+  bsa::HomeBatch down(c, false, rb, re);
+  double *dst[6] = {cd0, drag, thrustratio, thrust, fuelflow, bank};
+  for (int k = 0; k < 6; ++k)
+    if (dst[k] && down.add((const double *)c->s_fout.p + (size_t)k * n, nullptr, dst[k], 8)) return -1;
+  // fuel burnt: the committed steps + the last completed step's share, added
+  // here as the next step's launch will add it (one fp64 add: the same bits)
+  std::vector<double> pend(fuel_used ? (size_t)n : 0, 0.0);
+  if (fuel_used && (down.add(c->s_fused.p, nullptr, fuel_used, 8) || down.add(c->s_fpend.p, nullptr, pend.data(), 8)))
+    return -1;
+  if (down.run()) return -1;
+  for (int64_t h = rb; fuel_used && h < re; ++h) {
+    const unsigned i = c->h2id_h[(size_t)h];
+    fuel_used[i] = fuel_used[i] + pend[i];
+  }
+  return 0;
+}
 
 extern "C" int bsa_openap_forces(bsa_ctx *cc, int64_t n, int64_t ntypes, const double *table, const double *ftable,
                                  const int32_t *type_idx, const uint8_t *phase, const double *mass, const double *tas,

@@ -23,7 +23,6 @@
 
 #include "bsa_kin_math.h"
 #include "bsa_mvp_row.h"
-#include "bsa_perf_math.h"
 #include "bsa_prep.h"
 #include "bsa_sim_row.h"
 #include "bsa_xfer.h"
@@ -117,6 +116,33 @@ static SimDev sim_dev(Ctx *c) {
   return d;
 }
 
+// the ASAS bookkeeping's view of the sim (bsa_asas.hip), and K3's: full-n inputs, outputs on this rank's rows
+static BkDev bk_dev(Ctx *c) {
+  const SimDev s = sim_dev(c);
+  char *ctl = (char *)c->sim_ctl.p;
+  BkDev bk;
+  bk.lat = s.lat, bk.lon = s.lon, bk.gse = s.gse, bk.gsn = s.gsn, bk.trk = s.trk;
+  bk.h2id = (const unsigned *)c->h2id.p, bk.id2h = (const unsigned *)c->id2h.p;
+  bk.active = (uint8_t *)c->s_active.p, bk.dropped = (uint8_t *)c->s_dropped.p, bk.dropcnt = (int *)c->s_dropcnt.p;
+  bk.gate = (unsigned long long *)ctl, bk.sticky = (unsigned *)(ctl + kSimCtlSticky);
+  bk.demand = (unsigned long long *)(ctl + kSimCtlDemand), bk.kdemand = (unsigned long long *)(ctl + kSimCtlKdemand);
+  return bk;
+}
+static MvpDev mvp_dev(Ctx *c) {
+  const SimDev s = sim_dev(c);
+  const int64_t rb = c->sim_rb;
+  MvpDev d;
+  d.gseast = s.gse, d.gsnorth = s.gsn, d.vs = s.vs, d.alt = s.alt, d.trk = s.trk, d.gs = s.gs;
+  d.selalt = (const double *)c->s_selalt.p, d.apvs = s.apvs, d.aptrk = s.aptrk, d.aptas = s.aptas, d.apalt = s.apalt;
+  d.noreso = c->sim_noreso ? (const uint8_t *)c->s_noreso.p : nullptr;
+  d.resooff = c->sim_resooff ? (const uint8_t *)c->s_resooff.p : nullptr;
+  d.asas_alt = (double *)c->s_aalt.p + rb;
+  d.o_trk = (double *)c->s_atrk.p + rb, d.o_tas = (double *)c->s_atas.p + rb, d.o_vs = (double *)c->s_avs.p + rb;
+  d.o_asase = (float *)c->s_ase.p + rb, d.o_asasn = (float *)c->s_asn.p + rb;
+  d.o_tsolv = nullptr;
+  return d;
+}
+
 // Without wind, K4' sets gs = tas, trk = hdg and gseast / gsnorth =
 // tas sin / cos(hdg) (traffic.py:455-460, bsa_kin_math.h): every rank derives
 // the other ranks' gseast / gsnorth from their gathered gs / trk with the same
@@ -165,7 +191,7 @@ static int sim_gather_asas(Ctx *c) {
 // the resident step's last CD call as "the last detect" (its counts are
 // read from the device; the host never synchronised on that detect)
 int sim_adopt_pairs(Ctx *c) {
-  if (c->have_pairs || !c->sim_ready || c->sim_cd_calls == 0) return 0;
+  if (c->have_pairs || !c->sim_ready || c->clk.cd_calls == 0) return 0;
   if (c->empty_detect) {
     c->last_conf = c->last_los = 0;
     c->have_pairs = true;
@@ -234,16 +260,17 @@ struct CdOut {
 // per-row part may run inside the step's K4' (k_sim_pilot_kin<true>), which
 // also publishes a host-decided detect's prediction, so the host may decide
 // the list; a CD call without kinematics (bsa_sim_cd) launches K3 itself.
-// keep_k2: the detect's K2 is left to the step too (StepPlan::k24).
+// keep_k2: the detect's K2 is left to the step too (StepPlan::k24).  The
+// caller counts the call (clk.cd_calls).  Its stages: gather, detect,
+// bookkeeping count, gate all-reduce, K3, bookkeeping apply
 static int sim_cd(Ctx *c, bool in_step, bool keep_k2, CdOut *out) {
   const bsa_sim_params &p = c->simp;
   // several ranks: the detect's halo exchange (bsa_halo.hip) refreshes the
   // other ranks' rows this rank reads; one rank holds everything
   if (c->halo_mode != 1 && sim_gather(c)) return -1;
-  unsigned long long *gate = (unsigned long long *)c->sim_ctl.p;
-  const uint8_t *noreso = c->sim_noreso ? (const uint8_t *)c->s_noreso.p : nullptr;
-  const uint8_t *resooff = c->sim_resooff ? (const uint8_t *)c->s_resooff.p : nullptr;
-  DetectRequest q{p.rpz, p.hpz, p.tla, 0, c->sim_rb, c->sim_re, gate};
+  const BkDev bk = bk_dev(c);
+  const MvpDev d = mvp_dev(c);
+  DetectRequest q{p.rpz, p.hpz, p.tla, 0, c->sim_rb, c->sim_re, bk.gate};
   q.home = true;
   q.host_decides = in_step;
   q.keep_k2 = keep_k2;
@@ -251,60 +278,21 @@ static int sim_cd(Ctx *c, bool in_step, bool keep_k2, CdOut *out) {
   // k_mvp_row folds them after the gate
   if (p.reso) {
     q.mvp = &p.mvp;
-    q.gse = (const double *)c->s_gse.p;
-    q.gsn = (const double *)c->s_gsn.p;
-    q.vs = (const double *)c->own[5].p;
-    q.alt = (const double *)c->own[4].p;
-    q.noreso = noreso;
+    q.gse = d.gseast;
+    q.gsn = d.gsnorth;
+    q.vs = d.vs;
+    q.alt = d.alt;
+    q.noreso = d.noreso;
   }
   if (detect_enqueue(c, q, &out->det)) return -1;
-  c->sim_cd_calls++;
-  unsigned *sticky = (unsigned *)((char *)c->sim_ctl.p + bsa::kSimCtlSticky);
-  BkDev bk;
-  bk.lat = (const double *)c->own[0].p;
-  bk.lon = (const double *)c->own[1].p;
-  bk.gse = (const double *)c->s_gse.p;
-  bk.gsn = (const double *)c->s_gsn.p;
-  bk.trk = (const double *)c->own[2].p;
-  bk.h2id = (const unsigned *)c->h2id.p;
-  bk.id2h = (const unsigned *)c->id2h.p;
-  bk.active = (uint8_t *)c->s_active.p;
-  bk.dropped = (uint8_t *)c->s_dropped.p;
-  bk.dropcnt = (int *)c->s_dropcnt.p;
-  bk.gate = gate;
-  bk.sticky = sticky;
-  bk.demand = (unsigned long long *)((char *)c->sim_ctl.p + kSimCtlDemand);
-  bk.kdemand = (unsigned long long *)((char *)c->sim_ctl.p + kSimCtlKdemand);
   // ASAS bookkeeping, first half: kept-pair counts (may flag a resopairs overflow in the gate)
   if (p.resume_nav && bk_count(c, bk)) return -1;
-  if (comm_allreduce_max_u64(c, gate, kGateWords)) return -1;
-  const int64_t rb = c->sim_rb;
-  MvpDev d;
-  d.gseast = (const double *)c->s_gse.p;
-  d.gsnorth = (const double *)c->s_gsn.p;
-  d.vs = (const double *)c->own[5].p;
-  d.alt = (const double *)c->own[4].p;
-  d.trk = (const double *)c->own[2].p;
-  d.gs = (const double *)c->own[3].p;
-  d.selalt = (const double *)c->s_selalt.p;
-  d.apvs = (const double *)c->s_apvs.p;
-  d.aptrk = (const double *)c->s_aptrk.p;
-  d.aptas = (const double *)c->s_aptas.p;
-  d.apalt = (const double *)c->s_apalt.p;
-  d.noreso = noreso;
-  d.resooff = resooff;
-  d.asas_alt = (double *)c->s_aalt.p + rb;
-  d.o_trk = (double *)c->s_atrk.p + rb;
-  d.o_tas = (double *)c->s_atas.p + rb;
-  d.o_vs = (double *)c->s_avs.p + rb;
-  d.o_asase = (float *)c->s_ase.p + rb;
-  d.o_asasn = (float *)c->s_asn.p + rb;
-  d.o_tsolv = nullptr;
+  if (comm_allreduce_max_u64(c, bk.gate, kGateWords)) return -1;
   // K3 (+ gate, + asas.active = inconf unless ResumeNav runs) on the detect's own row offsets
   // without the bookkeeping (which runs between K3 and K4') K3's rows are
   // deferred into K4' of this step (k_sim_pilot_kin<true>)
   out->mvp_deferred = in_step && !p.resume_nav && c->sim_re > c->sim_rb;
-  if (mvp_device(c, p.mvp, d, (const unsigned *)c->rowoff.p, gate, sticky,
+  if (mvp_device(c, p.mvp, d, (const unsigned *)c->rowoff.p, bk.gate, bk.sticky,
                  p.resume_nav ? nullptr : (const uint8_t *)c->inconf.p, (uint8_t *)c->s_active.p, p.reso != 0,
                  out->det.pairs_done, out->det.rows_folded, out->mvp_deferred ? &out->mv : nullptr))
     return -1;
@@ -312,18 +300,64 @@ static int sim_cd(Ctx *c, bool in_step, bool keep_k2, CdOut *out) {
   return p.resume_nav ? bk_apply(c, bk) : 0;
 }
 
-// the FMS clock over one step: Autopilot.update's tick rule on
-// the host's copy of simt (autopilot.py:61-62, simulation.py:119); returns
-// whether the step ticks.  The enqueue loop and the replay after an abort
-// advance the clock with it.
-static bool fms_clock_step(Ctx *c) {
-  const bool tick = fms_ticks_at(c->fms_simt, c->fms_t0);
-  if (tick) {
-    c->fms_t0 = c->fms_simt;
-    c->fms_ticks++;
-  }
-  c->fms_simt += c->simp.simdt;
-  return tick;
+// ---- one step of a batch: StepPlan (every decision, taken by step_decide
+// from the host clocks before anything of the step is enqueued), one function
+// per stage, step_enqueue runs them in order and step_advance moves the clocks
+// (the stages in launch order: DESIGN.md 3.19; the detect side: DetectPlan, bsa_detect.h)
+struct StepPlan {
+  bool gv_apply;  // geovectoring applies in this step (geovec_applies_at on clk.gv_ctr)
+  // OpenAP forces: the pending fuel of the step before is committed first --
+  // not by the first step of a re-run attempt: it is the aborted step's own
+  // (DESIGN.md 3.20)
+  bool commit_fuel;
+  // Autopilot.update ticks in this step: the reference's rule on the host's
+  // copy of simt (autopilot.py:61-62, simulation.py:119); nothing is read back
+  bool fms_tick;
+  bool cd;  // a CD step (every cd_every steps)
+  // one rank: K2 and this step's K4' as one launch (k24_launch; BSA_K24=0
+  // off) -- K4' then starts on each workgroup's rows as soon as their fold is
+  // done, instead of behind the whole of K2
+  bool k24;
+  // one rank, the next step a CD step: K4' also prepares that detect's
+  // column records and boxes (its K0b launch is skipped; BSA_SIM_PREP=0 off)
+  bool prep;
+  // K4' workgroup size: one wave (at 100k rows 256-lane groups left half the
+  // CUs one group short, 391 groups on 256 CUs: 0.1753 -> 0.1718 ms per
+  // step with 64; BSA_K4_BLOCK=128/256 for A/B)
+  int k4_block;
+  bool sect_pass;  // the sector pass follows this step: clk.sect_ctr + 1 is a multiple of its cadence (3.27)
+};
+static StepPlan step_decide(const Ctx *c, bool rerun_first) {
+  const DetectEnv &env = detect_env();
+  const StepClocks &k = c->clk;
+  const int64_t rb = c->sim_rb, re = c->sim_re;
+  StepPlan sp{};
+  sp.gv_apply = c->sim_gv && geovec_applies_at(c);
+  sp.commit_fuel = !rerun_first;
+  sp.fms_tick = c->sim_fms && fms_ticks_at(k.fms_simt, k.fms_t0);
+  sp.cd = k.steps % c->simp.cd_every == 0;
+  sp.k24 = sp.cd && env.k24 && c->nranks == 1 && c->halo_mode == 0 && !c->simp.resume_nav && re > rb &&
+           c->k2_bucket > 0;
+  sp.prep = env.sim_prep && c->nranks == 1 && c->home && !c->reuse_on && c->halo_mode == 0 && rb == 0 &&
+            re == c->n && (k.steps + 1) % c->simp.cd_every == 0 &&
+            !c->sim_turb;  // turbulence moves the aircraft after K4': the next detect makes its own records (K0b)
+  sp.k4_block = env.k4_block;  // (PREP: whole waves = whole groups, rb = 0)
+  sp.sect_pass = c->sim_sect && (k.sect_ctr + 1) % c->sect_every == 0;
+  return sp;
+}
+
+// The host clocks over one step: the only function that moves them.  step_enqueue calls it once everything
+// of the step is enqueued; batch_rollback replays the completed steps of an aborted batch with it.  A stage
+// that is off keeps its clock still
+static void step_advance(Ctx *c, const StepPlan &sp) {
+  StepClocks &k = c->clk;
+  if (c->sim_gv) k.gv_ctr++;
+  if (sp.fms_tick) k.fms_t0 = k.fms_simt, k.fms_ticks++;  // Autopilot.update's tick: t0 = simt (autopilot.py:62)
+  if (c->sim_fms) k.fms_simt += c->simp.simdt;
+  if (sp.cd) k.cd_calls++;
+  if (c->sim_turb) k.turb_call++;
+  if (c->sim_sect) k.sect_ctr++;
+  k.steps++;
 }
 
 // ---- a batch (the steps of one bsa_sim_step attempt, or one bsa_sim_cd
@@ -331,17 +365,11 @@ static bool fms_clock_step(Ctx *c) {
 // read back once (batch_end), rolled back to the aborted step if it aborted
 struct BatchBase {
   bool kin;  // the batch runs K4' (bsa_sim_step; a CD call alone moves no state)
-  int64_t steps, cd_calls;
+  StepClocks clk;
   bool gs_derivable;
-  double fms_simt, fms_t0;  // the FMS clock
-  int64_t fms_ticks;
-  int64_t turb_call;  // the draws' call number
-  int64_t sect_ctr;   // the sector pass's step counter
-  int64_t gv_ctr;     // the geovector stage's step counter
 };
 static int batch_begin(Ctx *c, bool kin, BatchBase *b) {
-  *b = BatchBase{kin, c->sim_steps, c->sim_cd_calls, c->sim_gs_derivable, c->fms_simt, c->fms_t0, c->fms_ticks,
-                 c->turb_call, c->sect_ctr, c->gv_ctr};
+  *b = BatchBase{kin, c->clk, c->sim_gs_derivable};
   BSA_HIP(c, hipMemsetAsync((char *)c->sim_ctl.p + kSimCtlSticky, 0, 40, c->stream));  // sticky, steps_done, demands, stale
   return 0;
 }
@@ -354,7 +382,7 @@ static int batch_end(Ctx *c, unsigned long long ctl[5]) {
 }
 
 // An aborted batch: the state is that of the aborted step's start (step
-// base.steps + ctl[1]).  The gate is all-reduced, so every rank aborted at the
+// base.clk.steps + ctl[1]).  The gate is all-reduced, so every rank aborted at the
 // same step; each rank grows only what overflowed on IT (another rank's
 // overflow re-runs the step here with unchanged buffers) and all ranks re-run it
 static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long long *ctl) {
@@ -363,35 +391,25 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long lon
   // decisions of the aborted steps never took effect
   invalidate(c, Change::BatchAborted);
   const int64_t done = (int64_t)ctl[1];
-  c->sim_steps = base.steps + done;
+  // the clocks of the completed steps, replayed from the batch base with each step's own plan (a CD call alone
+  // completes no step: its count goes back to the base, the re-run counts it)
+  c->clk = base.clk;
+  for (int64_t k = 0; k < done; ++k) step_advance(c, step_decide(c, false));
   c->sim_gs_derivable = done > 0 ? c->simp.winddim == 0 : base.gs_derivable;  // K4' ran for the completed steps only
-  int64_t cds = 0;
-  for (int64_t k = base.steps; k < base.steps + done; ++k) cds += (k % c->simp.cd_every == 0) ? 1 : 0;
-  c->sim_cd_calls = base.cd_calls + cds;
-  if (base.kin) c->sim_gathered = c->nranks == 1;
-  if (base.kin && c->sim_fms) {
-    // the FMS clock of the completed steps, replayed from the batch base; the
-    // aborted step's launch ran (later ones were no-ops): if it ticked, the
-    // undo set it filled holds the step's start -- put it back
-    c->fms_simt = base.fms_simt;
-    c->fms_t0 = base.fms_t0;
-    c->fms_ticks = base.fms_ticks;
-    for (int64_t k = 0; k < done; ++k) fms_clock_step(c);
-    if (fms_ticks_at(c->fms_simt, c->fms_t0) && fms_sim_restore(c)) return -1;
+  if (base.kin) {
+    c->sim_gathered = c->nranks == 1;
+    // The aborted step's launches ran (later ones were no-ops): its plan, taken again on the replayed clocks,
+    // says what they wrote.  A ticking FMS launch filled its undo set with the step's start -- put it back;
+    // so did an applying geovector launch (later ones returned behind the sticky word) -- after the FMS undo
+    // set, whose selspd / ap_trk / selalt are the values the stage left.
+    // Turbulence: the draws are a pure function of (seed, call, index); the completed steps took one call
+    // number each, the aborted step's k_sim_turb returned behind the sticky word -- nothing to undo.
+    // Sectors: the pass only reads state; the completed steps' updates are counted, the aborted step's pass
+    // returned behind the sticky word like every later one, so the re-run counts each update once
+    const StepPlan sp = step_decide(c, false);
+    if (sp.fms_tick && fms_sim_restore(c)) return -1;
+    if (sp.gv_apply && geovec_sim_restore(c)) return -1;
   }
-  // the geovector stage writes persistent state: its counter is replayed over the completed steps; if the aborted
-  // step applied, its launch ran (later ones returned behind the sticky word) and the undo set it filled holds the
-  // step's start.  After the FMS undo set, whose selspd / ap_trk / selalt are the values the stage left
-  if (base.kin && c->sim_gv) {
-    c->gv_ctr = base.gv_ctr + done;
-    if (geovec_applies_at(c) && geovec_sim_restore(c)) return -1;
-  }
-  // the draws are a pure function of (seed, call, index): the completed steps took one call number each, the
-  // aborted step's k_sim_turb returned behind the sticky word -- nothing to undo
-  if (base.kin && c->sim_turb) c->turb_call = base.turb_call + done;
-  // the sector pass only reads state: the completed steps' updates are counted, the aborted step's pass returned
-  // behind the sticky word like every later one, so the re-run counts each update once
-  if (base.kin && c->sim_sect) c->sect_ctr = base.sect_ctr + done;
   // the last detect's counters: every detect after the abort ran on the same, unchanged state
   Counters h;
   BSA_HIP(c, hipMemcpy(&h, c->counters.p, sizeof(h), hipMemcpyDeviceToHost));
@@ -419,7 +437,7 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long lon
     c->bk_kw = std::max<unsigned long long>(2 * c->bk_kw, (unsigned long long)kdem + (unsigned long long)kdem / 4 + 1024);
   if (detect_env().hk_trace)  // (diagnostics)
     fprintf(stderr, "[bsa hk] rank %d abort at step %lld: stale %d k2 %llu fuse %llu halo %llu/%llu\n", c->rank,
-            (long long)c->sim_steps, ctl[4] ? 1 : 0, h.k2_demand, h.fuse_ovf, h.halo_ovf, h.halo_miss);
+            (long long)c->clk.steps, ctl[4] ? 1 : 0, h.k2_demand, h.fuse_ovf, h.halo_ovf, h.halo_miss);
   if (h.k2_demand) grow_k2_bucket(c, h.k2_demand);  // a K2 row bucket was full on this rank
   if (h.fuse_ovf) {  // fused K1b out of flush records: the re-run's detect unfused
     c->fuse_skip = true;
@@ -439,53 +457,6 @@ static int check_params(Ctx *c, const bsa_sim_params *p) {
   if (p->resume_nav != 0 && p->resume_nav != 1) return fail(c, "resume_nav must be 0 or 1");
   if (p->winddim < 0 || p->winddim > 3) return fail(c, "winddim must be 0, 1, 2 or 3");
   if (p->reso != 0 && p->reso != 1) return fail(c, "reso must be 0 or 1");
-  return 0;
-}
-
-// ---- one step of a batch: StepPlan (every decision, taken by step_decide
-// before anything of the step is enqueued), one function per stage,
-// step_enqueue runs them in order (the detect side: DetectPlan, bsa_detect.h)
-struct StepPlan {
-  // OpenAP forces: the pending fuel of the step before is committed first --
-  // not by the first step of a re-run attempt: it is the aborted step's own
-  // (DESIGN.md 3.20)
-  bool commit_fuel;
-  // Autopilot.update ticks in this step: decided here, by the reference's rule
-  // on the host's copy of simt (fms_clock_step); nothing is read back
-  bool fms_tick;
-  bool cd;  // a CD step (every cd_every steps)
-  // one rank: K2 and this step's K4' as one launch (k24_launch; BSA_K24=0
-  // off) -- K4' then starts on each workgroup's rows as soon as their fold is
-  // done, instead of behind the whole of K2
-  bool k24;
-  // one rank, the next step a CD step: K4' also prepares that detect's
-  // column records and boxes (its K0b launch is skipped; BSA_SIM_PREP=0 off)
-  bool prep;
-  // K4' workgroup size: one wave (at 100k rows 256-lane groups left half the
-  // CUs one group short, 391 groups on 256 CUs: 0.1753 -> 0.1718 ms per
-  // step with 64; BSA_K4_BLOCK=128/256 for A/B)
-  int k4_block;
-};
-static StepPlan step_decide(const Ctx *c, bool rerun_first) {
-  const DetectEnv &env = detect_env();
-  const int64_t rb = c->sim_rb, re = c->sim_re;
-  StepPlan sp{};
-  sp.commit_fuel = !rerun_first;
-  sp.fms_tick = c->sim_fms && fms_ticks_at(c->fms_simt, c->fms_t0);
-  sp.cd = c->sim_steps % c->simp.cd_every == 0;
-  sp.k24 = sp.cd && env.k24 && c->nranks == 1 && c->halo_mode == 0 && !c->simp.resume_nav && re > rb &&
-           c->k2_bucket > 0;
-  sp.prep = env.sim_prep && c->nranks == 1 && c->home && !c->reuse_on && c->halo_mode == 0 && rb == 0 &&
-            re == c->n && (c->sim_steps + 1) % c->simp.cd_every == 0 &&
-            !c->sim_turb;  // turbulence moves the aircraft after K4': the next detect makes its own records (K0b)
-  sp.k4_block = env.k4_block;  // (PREP: whole waves = whole groups, rb = 0)
-  return sp;
-}
-
-// Autopilot.update on the pre-step state (bsa_fms.hip), and the clock over the step
-static int step_fms(Ctx *c, const StepPlan &sp) {
-  if (fms_sim_launch(c, sp.fms_tick)) return -1;
-  fms_clock_step(c);
   return 0;
 }
 
@@ -579,14 +550,15 @@ static int step_launch(Ctx *c, const StepPlan &sp, const CdOut &cd, const PrepAr
   return 0;
 }
 
-// one step of the batch (enqueue only), and the host state that follows it
+// one step of the batch (enqueue only), the stages in their fixed order, and the host state
+// that follows it.  The clocks move last: a step that fails to enqueue leaves them at its start
 static int step_enqueue(Ctx *c, const StepPlan &sp) {
   // geovectoring is the plugin's preupdate (tools/plugin.py:161-169): the first launch on the step's stream, so
   // that Autopilot.update already reads the limited selspd / selvs / selalt / ap.trk
-  if (c->sim_gv && geovec_sim_step(c)) return -1;
+  if (sp.gv_apply && geovec_sim_launch(c)) return -1;
   // (forces and FMS read the pre-step state)
   if (c->sim_forces && forces_sim_launch(c, sp.commit_fuel)) return -1;
-  if (c->sim_fms && step_fms(c, sp)) return -1;
+  if (c->sim_fms && fms_sim_launch(c, sp.fms_tick)) return -1;  // Autopilot.update (bsa_fms.hip)
   CdOut cd;
   if (sp.cd && sim_cd(c, true, sp.k24, &cd)) {
     invalidate(c, Change::StepNotEnqueued);  // (a detect may have been enqueued without its step's publication)
@@ -600,9 +572,8 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
   if (c->sim_turb) {  // Turbulence.Woosh, the last statement of Traffic.update (traffic.py:416), on what K4' wrote
     const SimDev d = sim_dev(c);
     if (turb_sim_launch(c, c->sim_rb, c->sim_re, d.sticky, d.trk, d.lat, d.lon, d.alt)) return -1;
-    c->turb_call++;
   }
-  if (c->sim_sect && sect_step(c)) return -1;  // sector occupancy: reads what the step left (sectorcount.py:53-79)
+  if (sp.sect_pass && sect_sim_launch(c)) return -1;  // sector occupancy: reads what the step left (sectorcount.py:53-79)
   if (sp.prep)
     c->prep.keep({pa.rpz, pa.hpz, pa.tla, (double)pa.mid, c->n});
   else
@@ -612,9 +583,12 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
   // them, traffic.py:463-466, not the other way round)
   c->sim_gs_derivable = c->simp.winddim == 0;
   c->sim_gathered = c->nranks == 1;
-  c->sim_steps++;
+  step_advance(c, sp);
   return 0;
 }
+
+// every stage with a launch of its own, off (fms_off takes recovery and the geovectors with it): a new sim
+static void stages_off(Ctx *c) { forces_off(c), fms_off(c), turb_off(c), sect_off(c); }
 
 }  // namespace bsa
 
@@ -640,10 +614,8 @@ int bsa_sim_init(bsa_ctx *cc, int64_t n, const bsa_sim_state *s, const bsa_sim_p
   bsa::set_rank_rows(c);
   if (bsa::set_home_maps(c)) return -1;
   c->sim_noreso = c->sim_resooff = false;  // empty NORESO / RESOOFF lists
-  c->sim_atmos = c->sim_limits = c->sim_perf = c->sim_forces = c->sim_fms = c->sim_recovery = c->sim_turb = false;
-  c->turb_call = 0;
-  bsa::sect_off(c);
-  bsa::geovec_off(c);
+  c->sim_atmos = c->sim_limits = c->sim_perf = false;
+  bsa::stages_off(c);
   c->area_tab.clear();
   // every always-present array (kSimArrays); the all-gathered ones hold nranks
   // x rpr entries (in-place all-gather).  Zero unless a state field fills it:
@@ -673,7 +645,8 @@ int bsa_sim_init(bsa_ctx *cc, int64_t n, const bsa_sim_state *s, const bsa_sim_p
   // initial capacities (every rank holds the whole state now)
   c->halo_mode = c->nranks > 1 ? 1 : 0;
   if (bsa::halo_init_caps(c)) return -1;
-  c->sim_steps = c->sim_cd_calls = c->sim_last_conf = c->sim_last_los = 0;
+  c->clk = bsa::StepClocks{};
+  c->sim_last_conf = c->sim_last_los = 0;
   c->sim_gathered = true;
   bsa::invalidate(c, bsa::Change::NewSim);
   c->hk.cool = 0;
@@ -707,13 +680,13 @@ int bsa_sim_step(bsa_ctx *cc, int nsteps) {
     return bsa::fail(c, "winddim 3 needs a 3-D wind field (bsa_set_windfield3d)");
   if (nsteps < 0) return bsa::fail(c, "negative step count");
   BSA_HIP(c, hipSetDevice(c->device));
-  const int64_t target = c->sim_steps + nsteps;
-  for (int attempt = 0; c->sim_steps < target; ++attempt) {
+  const int64_t target = c->clk.steps + nsteps;
+  for (int attempt = 0; c->clk.steps < target; ++attempt) {
     if (attempt > 6) return bsa::fail(c, "candidate buffer overflow in the resident step (retries exhausted)");
     bsa::BatchBase base;
     if (bsa::batch_begin(c, true, &base)) return -1;
-    while (c->sim_steps < target)
-      if (bsa::step_enqueue(c, bsa::step_decide(c, attempt > 0 && c->sim_steps == base.steps))) return -1;
+    while (c->clk.steps < target)
+      if (bsa::step_enqueue(c, bsa::step_decide(c, attempt > 0 && c->clk.steps == base.clk.steps))) return -1;
     unsigned long long ctl[5] = {0, 0, 0, 0, 0};
     if (bsa::batch_end(c, ctl)) return -1;  // did every step complete?
 #ifdef BSA_PF_TRACE
@@ -753,7 +726,7 @@ int bsa_sim_set_perf(bsa_ctx *cc, int64_t ntypes, const double *table, const int
   if (!c) return -1;
   if (!c->sim_ready) return bsa::fail(c, "bsa_sim_set_perf before bsa_sim_init");
   BSA_HIP(c, hipSetDevice(c->device));
-  c->sim_forces = false;  // the force table goes with the type table: bsa_sim_set_forces again
+  bsa::forces_off(c);  // the force table goes with the type table: bsa_sim_set_forces again
   if (!table) {
     c->sim_perf = false;
     return 0;
@@ -791,173 +764,6 @@ int bsa_sim_read_perf(bsa_ctx *cc, uint8_t *phase, double *ax) {
   bsa::HomeBatch down(c, false, c->sim_rb, c->sim_re);
   if ((phase && down.add(c->s_phase.p, nullptr, phase, 1)) || (ax && down.add(c->s_ax.p, nullptr, ax, 8))) return -1;
   return down.run();
-}
-
-int bsa_sim_set_forces(bsa_ctx *cc, int64_t ntypes, const double *ftable, const double *mass) {
-  Ctx *c = (Ctx *)cc;
-  if (!c) return -1;
-  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_set_forces before bsa_sim_init");
-  BSA_HIP(c, hipSetDevice(c->device));
-  if (!ftable) {
-    c->sim_forces = false;
-    return 0;
-  }
-  if (!c->sim_perf) return bsa::fail(c, "bsa_sim_set_forces needs the type table and index of bsa_sim_set_perf");
-  if (!mass) return bsa::fail(c, "bsa_sim_set_forces: NULL mass");
-  if (ntypes != c->sim_ntypes)
-    return bsa::fail(c, "bsa_sim_set_forces: %lld force-table rows for the %lld types of bsa_sim_set_perf",
-                     (long long)ntypes, (long long)c->sim_ntypes);
-  if (ntypes > bsa::perf::kForceTypesMax)
-    return bsa::fail(c, "bsa_sim_set_forces: %lld types, at most %d", (long long)ntypes, bsa::perf::kForceTypesMax);
-  // thr0 = engnum x engthrust divides the thrust ratio of every fixed wing
-  std::vector<double> tab24((size_t)ntypes * bsa::kin::kPerfCols);
-  BSA_HIP(c, hipMemcpyAsync(tab24.data(), c->s_ptab.p, tab24.size() * 8, hipMemcpyDeviceToHost, c->stream));
-  BSA_HIP(c, hipStreamSynchronize(c->stream));
-  for (int64_t t = 0; t < ntypes; ++t) {
-    const double thr0 = ftable[t * bsa::perf::kForceCols + 1] * ftable[t * bsa::perf::kForceCols + 2];
-    if (tab24[(size_t)t * bsa::kin::kPerfCols + 22] == 1.0 && !std::isfinite(thr0))
-      return bsa::fail(c, "type %lld: engnum x engthrust is not finite", (long long)t);
-  }
-  const int64_t n = c->n;
-  const size_t N8 = (size_t)n * 8;
-  if (!bsa::ensure(c, c->s_ftab, (size_t)ntypes * bsa::perf::kForceCols * 8, "OpenAP force table") ||
-      !bsa::ensure(c, c->s_fmass, N8, "mass") || !bsa::ensure(c, c->s_fout, 6 * N8, "OpenAP forces") ||
-      !bsa::ensure(c, c->s_fused, N8, "fuel used") || !bsa::ensure(c, c->s_fpend, N8, "pending fuel"))
-    return -1;
-  if (bsa::forces_consts(c)) return -1;
-  BSA_HIP(c, hipMemcpyAsync(c->s_ftab.p, ftable, (size_t)ntypes * bsa::perf::kForceCols * 8, hipMemcpyHostToDevice,
-                            c->stream));
-  bsa::HomeBatch up(c, true);
-  if (up.add(c->s_fmass.p, mass, nullptr, 8) || up.run()) return -1;
-  // switching on: outputs (perf.bank among them) and the fuel accumulators start at 0
-  BSA_HIP(c, hipMemsetAsync(c->s_fout.p, 0, 6 * N8, c->stream));
-  BSA_HIP(c, hipMemsetAsync(c->s_fused.p, 0, N8, c->stream));
-  BSA_HIP(c, hipMemsetAsync(c->s_fpend.p, 0, N8, c->stream));
-  BSA_HIP(c, hipStreamSynchronize(c->stream));
-  c->sim_forces = true;
-  return 0;
-}
-
-int bsa_sim_read_forces(bsa_ctx *cc, double *cd0, double *drag, double *thrustratio, double *thrust,
-                        double *fuelflow, double *bank, double *fuel_used) {
-  Ctx *c = (Ctx *)cc;
-  if (!c) return -1;
-  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_read_forces before bsa_sim_init");
-  if (!c->sim_forces) return bsa::fail(c, "no forces: bsa_sim_set_forces is off");
-  BSA_HIP(c, hipSetDevice(c->device));
-  const int64_t n = c->n, rb = c->sim_rb, re = c->sim_re;
-  bsa::HomeBatch down(c, false, rb, re);
-  double *dst[6] = {cd0, drag, thrustratio, thrust, fuelflow, bank};
-  for (int k = 0; k < 6; ++k)
-    if (dst[k] && down.add((const double *)c->s_fout.p + (size_t)k * n, nullptr, dst[k], 8)) return -1;
-  // fuel burnt: the committed steps + the last completed step's share, added
-  // here as the next step's launch will add it (one fp64 add: the same bits)
-  std::vector<double> pend(fuel_used ? (size_t)n : 0, 0.0);
-  if (fuel_used && (down.add(c->s_fused.p, nullptr, fuel_used, 8) || down.add(c->s_fpend.p, nullptr, pend.data(), 8)))
-    return -1;
-  if (down.run()) return -1;
-  for (int64_t h = rb; fuel_used && h < re; ++h) {
-    const unsigned i = c->h2id_h[(size_t)h];
-    fuel_used[i] = fuel_used[i] + pend[i];
-  }
-  return 0;
-}
-
-int bsa_sim_set_fms(bsa_ctx *cc, int64_t nrows, const double *route_rows, const int32_t *rt_off, const int32_t *rt_n,
-                    const int32_t *iactwp, const bsa_fms_state *st, double simt, double t0) {
-  Ctx *c = (Ctx *)cc;
-  if (!c) return -1;
-  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_set_fms before bsa_sim_init");
-  BSA_HIP(c, hipSetDevice(c->device));
-  if (!route_rows) {
-    c->sim_fms = c->sim_recovery = false;
-    bsa::geovec_off(c);  // selspd / selvs live in the FMS arrays
-    return 0;
-  }
-  if (nrows < 0 || nrows > 0x7fffffff / 8) return bsa::fail(c, "bsa_sim_set_fms: bad route row count");
-  if (!rt_off || !rt_n || !iactwp || !st) return bsa::fail(c, "bsa_sim_set_fms: NULL array");
-  const bsa::FmsFields ff = bsa::fms_fields(*st);
-  for (auto q : ff.reals)
-    if (!q) return bsa::fail(c, "bsa_sim_set_fms: NULL array");
-  for (auto q : ff.flags)
-    if (!q) return bsa::fail(c, "bsa_sim_set_fms: NULL array");
-  if (!std::isfinite(simt) || std::isnan(t0)) return bsa::fail(c, "bsa_sim_set_fms: simt / t0 not finite");
-  const int64_t n = c->n;
-  if (bsa::fms_check_routes(c, "bsa_sim_set_fms", n, nrows, rt_off, rt_n, iactwp, st->swlnav)) return -1;
-  c->sim_fms = false;
-  const bool gv_on = c->sim_gv;  // a new FMS state keeps the geovectors; a failed upload leaves both off
-  c->sim_gv = false;
-  const size_t N = (size_t)n;
-  if (!bsa::ensure(c, c->s_fmsr, bsa::kFmsReals * N * 8, "FMS state") || !bsa::ensure(c, c->s_fmsf, bsa::kFmsFlags * N, "FMS flags") ||
-      !bsa::ensure(c, c->s_fmsi, bsa::kFmsInts * N * 4, "route indices") ||
-      !bsa::ensure(c, c->s_fmsrows, (size_t)nrows * 64 + 64, "route table") ||
-      !bsa::ensure(c, c->s_fmsur, bsa::kFmsUndoReals * N * 8, "FMS undo set") || !bsa::ensure(c, c->s_fmsuf, 2 * N, "FMS undo flags") ||
-      !bsa::ensure(c, c->s_fmsui, N * 4, "FMS undo waypoints"))
-    return -1;
-  bsa::HomeBatch up(c, true);
-  const int32_t *ints[bsa::kFmsInts] = {iactwp, rt_off, rt_n};
-  for (int q = 0; q < bsa::kFmsReals; ++q)
-    if (up.add((double *)c->s_fmsr.p + q * N, ff.reals[q], nullptr, 8)) return -1;
-  for (int q = 0; q < bsa::kFmsFlags; ++q)
-    if (up.add((uint8_t *)c->s_fmsf.p + q * N, ff.flags[q], nullptr, 1)) return -1;
-  for (int q = 0; q < bsa::kFmsInts; ++q)
-    if (up.add((int32_t *)c->s_fmsi.p + q * N, ints[q], nullptr, 4)) return -1;
-  if (up.run()) return -1;
-  if (nrows) BSA_HIP(c, hipMemcpyAsync(c->s_fmsrows.p, route_rows, (size_t)nrows * 64, hipMemcpyHostToDevice, c->stream));
-  BSA_HIP(c, hipStreamSynchronize(c->stream));
-  c->fms_simt = simt;
-  c->fms_t0 = t0;
-  c->fms_ticks = 0;
-  c->sim_fms = true;
-  c->sim_gv = gv_on;
-  return 0;
-}
-
-int bsa_sim_set_recovery(bsa_ctx *cc, int on) {
-  Ctx *c = (Ctx *)cc;
-  if (!c) return -1;
-  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_set_recovery before bsa_sim_init");
-  if (on && !c->sim_fms) return bsa::fail(c, "waypoint recovery needs the FMS guidance (bsa_sim_set_fms)");
-  c->sim_recovery = on != 0;
-  return 0;
-}
-
-int bsa_sim_read_dropcount(bsa_ctx *cc, int32_t *count) {
-  Ctx *c = (Ctx *)cc;
-  if (!c || !count) return -1;
-  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_read_dropcount before bsa_sim_init");
-  BSA_HIP(c, hipSetDevice(c->device));
-  bsa::HomeBatch down(c, false, c->sim_rb, c->sim_re);
-  if (down.add(c->s_dropcnt.p, nullptr, count, 4)) return -1;
-  return down.run();
-}
-
-int bsa_sim_read_fms(bsa_ctx *cc, const bsa_fms_state *st, int32_t *iactwp, double *ap_trk, double *ap_tas,
-                     double *ap_alt, double *ap_vs, double *selalt, double *simt, double *t0, int64_t *ticks) {
-  Ctx *c = (Ctx *)cc;
-  if (!c) return -1;
-  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_read_fms before bsa_sim_init");
-  if (!c->sim_fms) return bsa::fail(c, "no FMS state: bsa_sim_set_fms is off");
-  BSA_HIP(c, hipSetDevice(c->device));
-  const size_t N = (size_t)c->n;
-  bsa::HomeBatch down(c, false, c->sim_rb, c->sim_re);
-  if (st) {
-    const bsa::FmsFields ff = bsa::fms_fields(*st);
-    for (int q = 0; q < bsa::kFmsReals; ++q)
-      if (ff.reals[q] && down.add((const double *)c->s_fmsr.p + q * N, nullptr, ff.reals[q], 8)) return -1;
-    for (int q = 0; q < bsa::kFmsFlags; ++q)
-      if (ff.flags[q] && down.add((const uint8_t *)c->s_fmsf.p + q * N, nullptr, ff.flags[q], 1)) return -1;
-  }
-  if (iactwp && down.add(c->s_fmsi.p, nullptr, iactwp, 4)) return -1;
-  double *tg[5] = {ap_trk, ap_tas, ap_alt, ap_vs, selalt};
-  const void *src[5] = {c->s_aptrk.p, c->s_aptas.p, c->s_apalt.p, c->s_apvs.p, c->s_selalt.p};
-  for (int q = 0; q < 5; ++q)
-    if (tg[q] && down.add(src[q], nullptr, tg[q], 8)) return -1;
-  if (down.run()) return -1;
-  if (simt) *simt = c->fms_simt;
-  if (t0) *t0 = c->fms_t0;
-  if (ticks) *ticks = c->fms_ticks;
-  return 0;
 }
 
 int bsa_sim_update(bsa_ctx *cc, const bsa_sim_state *s) {
@@ -1014,7 +820,7 @@ int bsa_sim_read(bsa_ctx *cc, bsa_sim_out *o) {
 int bsa_sim_stats(bsa_ctx *cc, int64_t *out6) {
   Ctx *c = (Ctx *)cc;
   if (!c || !out6) return -1;
-  if (c->sim_cd_calls > 0 && c->counters.p) {  // counts of the last CD step
+  if (c->clk.cd_calls > 0 && c->counters.p) {  // counts of the last CD step
     BSA_HIP(c, hipSetDevice(c->device));
     bsa::Counters h;
     BSA_HIP(c, hipMemcpyAsync(&h, c->counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
@@ -1022,8 +828,8 @@ int bsa_sim_stats(bsa_ctx *cc, int64_t *out6) {
     c->sim_last_conf = (int64_t)h.conf;
     c->sim_last_los = (int64_t)h.los;
   }
-  out6[0] = c->sim_steps;
-  out6[1] = c->sim_cd_calls;
+  out6[0] = c->clk.steps;
+  out6[1] = c->clk.cd_calls;
   out6[2] = c->sim_last_conf;
   out6[3] = c->sim_last_los;
   out6[4] = c->sim_rb;
@@ -1194,6 +1000,7 @@ int bsa_sim_cd(bsa_ctx *cc) {
     bsa::BatchBase base;
     bsa::CdOut cd;
     if (bsa::batch_begin(c, false, &base) || bsa::sim_cd(c, false, false, &cd)) return -1;
+    c->clk.cd_calls++;  // (a CD call outside a step: step_advance counts a step's)
     unsigned long long ctl[5] = {0, 0, 0, 0, 0};
     if (bsa::batch_end(c, ctl)) return -1;
     if ((unsigned)ctl[0] == 0) break;

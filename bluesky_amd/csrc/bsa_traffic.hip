@@ -172,7 +172,7 @@ static int multi_begin(Ctx *c, Multi &m) {
   if (!ensure(c, m.ginc, (size_t)n, "inconf") || !ensure(c, m.gtcp, (size_t)n * 8, "tcpamax")) return -1;
   BSA_HIP(c, hipMemsetAsync(m.ginc.p, 0, (size_t)n, c->stream));
   BSA_HIP(c, hipMemsetAsync(m.gtcp.p, 0, (size_t)n * 8, c->stream));
-  if (nr > 0 && c->inconf.p && c->tcpamax.p && c->sim_cd_calls > 0) {
+  if (nr > 0 && c->inconf.p && c->tcpamax.p && c->clk.cd_calls > 0) {
     BSA_HIP(c, hipMemcpyAsync((char *)m.ginc.p + rb, c->inconf.p, (size_t)nr, hipMemcpyDeviceToDevice, c->stream));
     BSA_HIP(c, hipMemcpyAsync((char *)m.gtcp.p + (size_t)rb * 8, c->tcpamax.p, (size_t)nr * 8, hipMemcpyDeviceToDevice,
                               c->stream));

@@ -107,11 +107,13 @@ int turb_sim_launch(Ctx *c, int64_t rb, int64_t re, const unsigned *sticky, cons
   TurbScale sc;
   if (turb_scale(c, "turbulence", c->simp.simdt, c->turb_sd, &sc)) return -1;
   hipLaunchKernelGGL(k_sim_turb, dim3(turb_grid(re - rb)), dim3(kTurbBlock), 0, c->stream, (int)rb, (int)re, sc,
-                     c->turb_seed, (unsigned long long)c->turb_call, (const unsigned *)c->h2id.p, sticky, trk, lat, lon,
-                     alt);
+                     c->turb_seed, (unsigned long long)c->clk.turb_call, (const unsigned *)c->h2id.p, sticky, trk, lat,
+                     lon, alt);
   BSA_HIP(c, hipGetLastError());
   return 0;
 }
+
+void turb_off(Ctx *c) { c->sim_turb = false, c->clk.turb_call = 0; }
 
 }  // namespace bsa
 
@@ -193,8 +195,8 @@ extern "C" int bsa_sim_turb_call(bsa_ctx *cc, int64_t *call, const int64_t *set_
   if (!c->sim_ready) return bsa::fail(c, "bsa_sim_turb_call before bsa_sim_init");
   if (set_to) {
     if (*set_to < 0) return bsa::fail(c, "bsa_sim_turb_call: negative call number");
-    c->turb_call = *set_to;
+    c->clk.turb_call = *set_to;
   }
-  if (call) *call = c->turb_call;
+  if (call) *call = c->clk.turb_call;
   return 0;
 }

@@ -186,6 +186,54 @@ def test_errors_and_off(ctx, areas):
     sim.step(1)
 
 
+@pytest.mark.parametrize('set_after', [0, 1])
+def test_abort_in_mid_batch_is_exact(ctx, areas, set_after):
+    """A candidate list far too small, CD every 4th step (as tests/test_gpu_turbulence.py forces it): the
+    batch of steps 1-12 completes steps 1-3, aborts at step 4 and re-runs from there.  Cadence 2.  Sectors
+    set before step 0: the passes of the batch follow steps 1 and 3 (completed), then 5, 7 .. (re-run).
+    Set after step 0: they follow step 2 (completed), step 4 (the aborted step: its pass returned behind
+    the sticky word and runs again in the re-run), then 6, 8 ..  Either way every update is counted once:
+    the poll and the state equal those of a twin on its own context that never aborts."""
+    from bluesky_amd import _lib
+    init = resident.initial_state(synth.box(5000, 120.0, seed=149))
+    p = resident.params(simdt=SIMDT, cd_every=4)
+
+    def run(c, batches, small):
+        sim = resident.ResidentSim(init, p, ctx=c)
+        sim.set_areas(areas[1])
+        n_conf = []
+        for k, b in enumerate(batches):
+            if k == set_after:
+                sim.set_sectors(NAMES, 2)
+            if small:
+                c.set_candidate_capacity(16)
+            sim.step(b)
+            n_conf.append(sim.stats()['n_conf'])
+        return sim.ctx.sim_sectors_poll(masks=True), sim.read(), sim.stats(), n_conf
+
+    twin = _lib.Context(0)
+    try:
+        exp, exp_state, exp_stats, n_conf = run(twin, [1, 4, 8], False)
+    finally:
+        twin.close()
+    # the CD step that ends the twin's second batch is step 4: a list of 16 candidates cannot hold it,
+    # so the run below did abort there
+    assert n_conf[1] > 16
+    assert exp['updates'] == 6 and exp['step'] == 12      # 13 or 12 steps since set_sectors
+    assert int(exp['arrived_total'].sum() + exp['left_total'].sum()) > 0     # aircraft did cross sector borders
+    c = _lib.Context(0)
+    try:
+        got, state, stats, _ = run(c, [1, 12], True)
+    finally:
+        c.close()
+    assert sorted(got) == sorted(exp)
+    for k in exp:
+        assert np.array_equal(got[k], exp[k]), k
+    for k in exp_state:
+        assert np.array_equal(state[k], exp_state[k]), k
+    assert stats == exp_stats
+
+
 def test_two_ranks_equal_one(areas, truth, resident_run):
     def fn(rank, c, group):
         sim, ids = make_sim(c, rank, 2, group)
