@@ -245,6 +245,12 @@ SIGNATURES.update({
                        [ctypes.c_uint64, ctypes.c_uint64] + [_c_dp] * 5),
     'bsa_sim_set_turbulence': (ctypes.c_int, [_vp, ctypes.c_int, _c_dp, ctypes.c_uint64]),
     'bsa_sim_turb_call': (ctypes.c_int, [_vp, _c_i64p, _c_i64p]),
+    'bsa_cond_update': (ctypes.c_int, [_vp, ctypes.c_int64, _c_i32p, _c_i32p, _c_dp, _c_dp, ctypes.c_int64, _c_dp, _c_dp,
+                                       _c_i32p, _c_i64p]),
+    'bsa_sim_set_conditions': (ctypes.c_int, [_vp, ctypes.c_int64, _c_i32p, _c_i32p, _c_dp, _c_dp]),
+    'bsa_sim_steps_run': (ctypes.c_int, [_vp, _c_i64p, _c_i64p]),
+    'bsa_sim_cond_poll': (ctypes.c_int, [_vp, ctypes.c_int64, _c_i32p, _c_i64p, _c_i64p]),
+    'bsa_sim_read_conditions': (ctypes.c_int, [_vp, ctypes.c_int64, _c_i32p, _c_i32p, _c_dp, _c_dp, _c_i64p]),
 })
 
 AREA_TYPES = {'LINE': 0, 'BOX': 1, 'CIRCLE': 2, 'POLY': 3}
@@ -1133,8 +1139,65 @@ class Context:
         self._rows = (st['row_begin'], st['row_end'])
 
     def sim_step(self, nsteps=1):
+        """bsa_sim_step; returns the steps run (fewer than ``nsteps`` when a condition fired)."""
         self.gen += 1
         self.check(self.lib.bsa_sim_step(self.h, int(nsteps)), 'bsa_sim_step')
+        if not hasattr(self.lib, 'bsa_sim_steps_run'):   # (an older build loaded for an A/B measurement)
+            return int(nsteps)
+        return self.sim_steps_run()[0]
+
+    def sim_steps_run(self):
+        """bsa_sim_steps_run: (steps of the last sim_step call, the sim's step count)."""
+        last, total = ctypes.c_int64(0), ctypes.c_int64(0)
+        self.check(self.lib.bsa_sim_steps_run(self.h, ctypes.byref(last), ctypes.byref(total)), 'bsa_sim_steps_run')
+        return int(last.value), int(total.value)
+
+    # ---------------------------------------------------------------- conditional commands
+    @staticmethod
+    def _cond_arrays(idx, condtype, target, lastdif):
+        a = (np.ascontiguousarray(idx, dtype=np.int32).ravel(), np.ascontiguousarray(condtype, dtype=np.int32).ravel(),
+             f64(target).ravel(), np.array(lastdif, dtype=np.float64).ravel())
+        if any(len(x) != len(a[0]) for x in a):
+            raise ValueError('condition arrays differ in length')
+        return a
+
+    def cond_update(self, idx, condtype, target, lastdif, alt, cas):
+        """bsa_cond_update: one Condition.update; (fired condition indices ascending, new lastdif)."""
+        idx, typ, target, last = self._cond_arrays(idx, condtype, target, lastdif)
+        alt, cas = f64(alt), f64(cas)
+        if len(alt) != len(cas):
+            raise ValueError('alt and cas differ in length')
+        m = len(idx)
+        fired, count = np.zeros(max(m, 1), np.int32), ctypes.c_int64(0)
+        self.check(self.lib.bsa_cond_update(self.h, m, ptr(idx, _c_i32p), ptr(typ, _c_i32p), ptr(target), ptr(last),
+                                            len(alt), ptr(alt), ptr(cas), ptr(fired, _c_i32p), ctypes.byref(count)),
+                   'bsa_cond_update')
+        return fired[:count.value].astype(np.int64), last
+
+    def sim_set_conditions(self, idx=(), condtype=(), target=(), lastdif=()):
+        """bsa_sim_set_conditions: the table of the step's conditional commands (empty: off)."""
+        idx, typ, target, last = self._cond_arrays(idx, condtype, target, lastdif)
+        self.check(self.lib.bsa_sim_set_conditions(self.h, len(idx), ptr(idx, _c_i32p), ptr(typ, _c_i32p), ptr(target),
+                                                   ptr(last)), 'bsa_sim_set_conditions')
+        self._cond_cap = len(idx)
+
+    def sim_cond_poll(self):
+        """bsa_sim_cond_poll: (fired condition indices of the last stop, ascending; its step count)."""
+        cap = max(getattr(self, '_cond_cap', 0), 1)
+        fired, count, step = np.zeros(cap, np.int32), ctypes.c_int64(0), ctypes.c_int64(0)
+        self.check(self.lib.bsa_sim_cond_poll(self.h, cap, ptr(fired, _c_i32p), ctypes.byref(count), ctypes.byref(step)),
+                   'bsa_sim_cond_poll')
+        return fired[:count.value].astype(np.int64), int(step.value)
+
+    def sim_read_conditions(self):
+        """bsa_sim_read_conditions: dict of idx, condtype, target, lastdif of the live conditions."""
+        cap = max(getattr(self, '_cond_cap', 0), 1)
+        o = dict(idx=np.zeros(cap, np.int32), condtype=np.zeros(cap, np.int32), target=np.zeros(cap), lastdif=np.zeros(cap))
+        count = ctypes.c_int64(0)
+        self.check(self.lib.bsa_sim_read_conditions(self.h, cap, ptr(o['idx'], _c_i32p), ptr(o['condtype'], _c_i32p),
+                                                    ptr(o['target']), ptr(o['lastdif']), ctypes.byref(count)),
+                   'bsa_sim_read_conditions')
+        return {k: v[:count.value].copy() for k, v in o.items()}
 
     def sim_cd(self):
         """bsa_sim_cd: one CD call (detect -> resolver -> bookkeeping) without kinematics."""

@@ -121,6 +121,19 @@ constexpr unsigned long long kGateNonfinite = 1, kGateOverflow = 2, kGateBkOverf
 constexpr int kGateWords = 3;
 constexpr int kSimCtlSticky = 24, kSimCtlSteps = 32, kSimCtlDemand = 40, kSimCtlKdemand = 48, kSimCtlStale = 56;
 // (sim_ctl bytes; [24, 64) are zeroed per batch and read back after it)
+// The sticky word's values: 0 the batch runs; kStickyAborted the step that raised it did not happen (the state is
+// its start: grow, re-run); kStickyStopped the step that raised it is complete and the host has to act before the
+// next one (nothing to re-run).  A stop is raised only while the word is 0, by a stage behind the step's steps_done
+// increment, together with [28, 32): stop_word(stage, tag) -- which stage raised it (StopStage; batch_stopped
+// hands the stop to that stage's host side) and the raising step's tag (its number in the batch + 1, < 2^24).
+// That word, not the sticky value, tells the host the batch stopped: a detect of a later, no-op step may still
+// overflow and store kStickyAborted over the stop
+constexpr unsigned kStickyAborted = 1u, kStickyStopped = 2u;
+enum StopStage : unsigned { kStopNone = 0, kStopCond = 1, kStopCount };  // (the experiment area's exit deletes: the next one)
+constexpr unsigned kStopTagMax = (1u << 24) - 1;
+constexpr unsigned stop_word(unsigned stage, unsigned tag) { return (stage << 24) | tag; }
+constexpr unsigned stop_stage(unsigned w) { return w >> 24; }
+constexpr unsigned stop_tag(unsigned w) { return w & kStopTagMax; }
 constexpr int kHkRing = 16;  // HK: published predictions (pinned host words), slot m % kHkRing
 constexpr unsigned long long kNanBits = 0x7ff8000000000000ull;  // (a quiet NaN)
 
@@ -379,7 +392,8 @@ struct Ctx {
   DevBuf nonfin;
   DevBuf rownf;  // rows of their own (not columns): per row (index order), its position / velocity is not finite
   unsigned long long nf_counter = 0, nf_prep_epoch = 0;  // epochs (K0b: a new one; K4' prep: the next detect's)
-  DevBuf sim_ctl;  // [0,24) gate {abort / non-finite, P, HK prediction}; [24,28) sticky abort; [32,40) steps
+  DevBuf sim_ctl;  // [0,24) gate {abort / non-finite, P, HK prediction}; [24,28) sticky abort / stop; [28,32) the
+                   // stopping step's tag; [32,40) steps
                    // done; [40,48) resopairs demand on a bookkeeping overflow; [48,56) pair-key
                    // block demand (several ranks); [56,64) an HK-kept list went stale in the batch
   // ASAS bookkeeping (bsa_asas.hip, resume_nav = 1): resopairs CSR over own
@@ -467,6 +481,18 @@ struct Ctx {
   bool sim_gv = false;
   int gv_n = 0;
   int64_t gv_every = 1;
+
+  // Conditional commands (bsa_cond.hip).  cond_stage: bsa_cond_update's arrays.  In the resident
+  // step (bsa_sim_set_conditions): the table by aircraft index -- idx / type / target (host mirrors cond_*_h of
+  // every device row), lastdif and a flag byte per row (live / fired at the last stop / dead) on the device only,
+  // cond_ws the ordered compaction's words.  cond_pending: a stop nobody polled yet; cond_stop_step: its step count.
+  // steps_last / steps_total: what bsa_sim_steps_run reports
+  DevBuf cond_stage, cond_idx, cond_type, cond_tgt, cond_last, cond_flag, cond_ws;
+  std::vector<int32_t> cond_idx_h, cond_type_h;
+  std::vector<double> cond_tgt_h;
+  bool sim_cond = false, cond_pending = false;
+  int64_t cond_stop_step = 0;
+  int64_t steps_last = 0, batch_steps0 = 0;  // (the step count at the running batch's begin: StepPlan::cond_tag)
 
   // standalone geo matrices (bsa_geo.hip)
   DevBuf geo_in, geo_pts, geo_out;
@@ -680,6 +706,14 @@ WindField wind_field_pa(const Ctx *c);
 int turb_sim_launch(Ctx *c, int64_t rb, int64_t re, const unsigned *sticky, const double *trk, double *lat,
                     double *lon, double *alt);
 void turb_off(Ctx *c);
+
+// Conditional commands of the step (bsa_cond.hip): k_sim_cond, the step's last launch; tag: the step's number in
+// its batch + 1 (what a stop it raises carries).  cond_note_deleted: Condition.delac for the (sorted) aircraft of
+// a bsa_sim_delete, before anything moves.  cond_off forgets the table
+int cond_sim_launch(Ctx *c, unsigned tag);
+void cond_stopped(Ctx *c);  // batch_stopped: the stop was this stage's (the clocks are already those of the stop)
+int cond_note_deleted(Ctx *c, const std::vector<int64_t> &d);
+void cond_off(Ctx *c);
 
 // Sector occupancy (bsa_area.hip): sect_sim_launch after the last stage of a step whose StepPlan::sect_pass is
 // set (clk.sect_ctr + 1 a multiple of the cadence); sect_note_deleted by bsa_sim_delete before anything moves;

@@ -144,6 +144,7 @@ enum class Change {
   OtherRows,          // bsa_sim_probe_rank
   Traffic,            // bsa_sim_create / bsa_sim_delete (set_n)
   BatchAborted,       // batch_rollback
+  BatchStopped,       // batch_stopped: a stage ended the batch after a completed step
   StepNotEnqueued,    // step_enqueue: its CD call failed
   DetectNotEnqueued,  // detect_enqueue: its first event record failed
   DetectDone,         // detect_finish
@@ -177,6 +178,12 @@ constexpr bool drop = true, stays = false;
 //      prepared records), on several the own-tile K0b checks every record against the list's snapshot.  Switching
 //      it on, off or to other sd / seed drops what was made under the other setting's drift: the prepared
 //      records' budget check and HK's predictions assumed it
+//  (n) the steps enqueued behind the stop became no-ops, but their detects ran -- on the state the stop left, with
+//      the host's later decisions: they re-armed the candidate list, the tile-pair list and its snapshot, the zeroed
+//      counters and the HK history for steps that never happened, and K4' prepared no records for them.  All of it
+//      is over the right state, but the host-side keys (HK's m, the prepared flag, which K2 zeroed what) describe
+//      steps the clocks are rolled back over, so everything BatchAborted drops goes; a firing is rare, the next
+//      detect rebuilds
 //  (?) unexplained
 constexpr Drops kDrops[(int)Change::Count] = {
     //                      order  cands  tiles  prep   zero   hk
@@ -188,6 +195,7 @@ constexpr Drops kDrops[(int)Change::Count] = {
     /* OtherRows         */ {stays, stays, drop, drop, stays, stays},   // p d . . z b
     /* Traffic           */ {drop, drop, drop, drop, stays, stays},     // . . . . z b
     /* BatchAborted      */ {stays, drop, drop, drop, drop, drop},      // p . . . . .
+    /* BatchStopped      */ {stays, drop, drop, drop, drop, drop},      // p n n n n n
     /* StepNotEnqueued   */ {stays, stays, stays, stays, stays, drop},  // p ? ? ? ? .
     /* DetectNotEnqueued */ {stays, drop, stays, stays, stays, stays},  // p . ? c c ?
     /* DetectDone        */ {stays, stays, stays, stays, drop, stays},  // c c c c . c

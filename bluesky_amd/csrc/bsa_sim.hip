@@ -326,6 +326,10 @@ struct StepPlan {
   // step with 64; BSA_K4_BLOCK=128/256 for A/B)
   int k4_block;
   bool sect_pass;  // the sector pass follows this step: clk.sect_ctr + 1 is a multiple of its cadence (3.27)
+  // conditional commands (3.29): k_sim_cond is the step's last launch; cond_tag: the step's number in its batch
+  // + 1, what a stop raised by it carries (no clock: the stage evaluates every step)
+  bool cond;
+  unsigned cond_tag;
 };
 static StepPlan step_decide(const Ctx *c, bool rerun_first) {
   const DetectEnv &env = detect_env();
@@ -343,6 +347,8 @@ static StepPlan step_decide(const Ctx *c, bool rerun_first) {
             !c->sim_turb;  // turbulence moves the aircraft after K4': the next detect makes its own records (K0b)
   sp.k4_block = env.k4_block;  // (PREP: whole waves = whole groups, rb = 0)
   sp.sect_pass = c->sim_sect && (k.sect_ctr + 1) % c->sect_every == 0;
+  sp.cond = c->sim_cond;
+  sp.cond_tag = (unsigned)(k.steps - c->batch_steps0 + 1);
   return sp;
 }
 
@@ -370,6 +376,7 @@ struct BatchBase {
 };
 static int batch_begin(Ctx *c, bool kin, BatchBase *b) {
   *b = BatchBase{kin, c->clk, c->sim_gs_derivable};
+  c->batch_steps0 = c->clk.steps;
   BSA_HIP(c, hipMemsetAsync((char *)c->sim_ctl.p + kSimCtlSticky, 0, 40, c->stream));  // sticky, steps_done, demands, stale
   return 0;
 }
@@ -449,6 +456,32 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long lon
   for (int q = 0; q < kCandShards; ++q) worst = std::max(worst, h.cshard[q][0]);
   if (worst > c->cand_cap / kCandShards)
     c->cand_cap = std::max(2 * c->cand_cap, (unsigned long long)kCandShards * (worst + worst / 4 + 1024));
+  return 0;
+}
+
+// A stopped batch (kStickyStopped, bsa_internal.h): a stage of step `done` (counted from the batch base) raised
+// the stop after that step was complete; every launch of the later steps returned behind the sticky word (the
+// fused K2 + K4' copies its double buffers' halves, so the host's swaps of the no-op steps stay right, as after
+// an abort).  The device state is exactly that after step `done`: nothing is re-run, nothing grown -- whatever a
+// later, no-op step's detect overflowed is found again by the step the host resumes with.  The FMS and geovector
+// undo sets are NOT put back: the step after the stop never executed, its launches returned before they saved
+// anything, so the sets hold an earlier, completed tick's start.  Host state step_enqueue moved for the no-op
+// steps: the clocks are replayed over the completed steps as batch_rollback does; prep.keep / drop and the HK
+// decisions go with Change::BatchStopped; sim_gs_derivable / sim_gathered are those after a completed K4'
+static int batch_stopped(Ctx *c, const BatchBase &base, const unsigned long long *ctl) {
+  const unsigned sw = (unsigned)(ctl[0] >> 32);
+  const int64_t done = (int64_t)ctl[1], tag = (int64_t)stop_tag(sw);
+  if (done < 1 || tag != done || stop_stage(sw) == kStopNone || stop_stage(sw) >= kStopCount)
+    return fail(c, "internal error: batch stopped by stage %u in step %lld with %lld steps done", stop_stage(sw),
+                (long long)tag, (long long)done);
+  invalidate(c, Change::BatchStopped);
+  c->clk = base.clk;
+  for (int64_t k = 0; k < done; ++k) step_advance(c, step_decide(c, false));
+  c->sim_gs_derivable = c->simp.winddim == 0;
+  c->sim_gathered = c->nranks == 1;
+  switch (stop_stage(sw)) {  // the raising stage's host side
+    case kStopCond: cond_stopped(c); break;
+  }
   return 0;
 }
 
@@ -574,6 +607,8 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
     if (turb_sim_launch(c, c->sim_rb, c->sim_re, d.sticky, d.trk, d.lat, d.lon, d.alt)) return -1;
   }
   if (sp.sect_pass && sect_sim_launch(c)) return -1;  // sector occupancy: reads what the step left (sectorcount.py:53-79)
+  // cond.update() (traffic.py:419): reads what the step left; last, so that a stop it raises cuts nothing of this step
+  if (sp.cond && cond_sim_launch(c, sp.cond_tag)) return -1;
   if (sp.prep)
     c->prep.keep({pa.rpz, pa.hpz, pa.tla, (double)pa.mid, c->n});
   else
@@ -588,7 +623,7 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
 }
 
 // every stage with a launch of its own, off (fms_off takes recovery and the geovectors with it): a new sim
-static void stages_off(Ctx *c) { forces_off(c), fms_off(c), turb_off(c), sect_off(c); }
+static void stages_off(Ctx *c) { forces_off(c), fms_off(c), turb_off(c), sect_off(c), cond_off(c); }
 
 }  // namespace bsa
 
@@ -679,8 +714,11 @@ int bsa_sim_step(bsa_ctx *cc, int nsteps) {
   if (c->simp.winddim == 3 && c->wf3_nvec < 1)
     return bsa::fail(c, "winddim 3 needs a 3-D wind field (bsa_set_windfield3d)");
   if (nsteps < 0) return bsa::fail(c, "negative step count");
+  if (c->sim_cond && (unsigned)nsteps > bsa::kStopTagMax)
+    return bsa::fail(c, "at most %u steps per call while a stage that can stop the batch is on", bsa::kStopTagMax);
   BSA_HIP(c, hipSetDevice(c->device));
-  const int64_t target = c->clk.steps + nsteps;
+  const int64_t start = c->clk.steps, target = start + nsteps;
+  c->steps_last = 0;
   for (int attempt = 0; c->clk.steps < target; ++attempt) {
     if (attempt > 6) return bsa::fail(c, "candidate buffer overflow in the resident step (retries exhausted)");
     bsa::BatchBase base;
@@ -692,9 +730,23 @@ int bsa_sim_step(bsa_ctx *cc, int nsteps) {
 #ifdef BSA_PF_TRACE
     if (bsa::pf_trace_dump(c, 0, 0)) return -1;  // (diagnostic builds: the batch's last prefilter)
 #endif
+    if ((ctl[0] >> 32) != 0) {  // stopped: the host has to act before the next step (bsa_sim_steps_run tells how far it got)
+      if (bsa::batch_stopped(c, base, ctl)) return -1;
+      break;
+    }
     if ((unsigned)ctl[0] == 0) break;
     if (bsa::batch_rollback(c, base, ctl)) return -1;
   }
+  c->steps_last = c->clk.steps - start;
+  return 0;
+}
+
+int bsa_sim_steps_run(bsa_ctx *cc, int64_t *last_batch, int64_t *total) {
+  Ctx *c = (Ctx *)cc;
+  if (!c) return -1;
+  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_steps_run before bsa_sim_init");
+  if (last_batch) *last_batch = c->steps_last;
+  if (total) *total = c->clk.steps;
   return 0;
 }
 

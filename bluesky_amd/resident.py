@@ -105,7 +105,34 @@ class ResidentSim:
             self.set_turbulence(**p.turbulence)
 
     def step(self, nsteps=1):
-        self.ctx.sim_step(nsteps)
+        """Advance ``nsteps`` in one batch; returns the steps run -- fewer when a condition
+        of ``set_conditions`` fired: the batch ends after that step (``conditions()``)."""
+        return self.ctx.sim_step(nsteps)
+
+    def set_conditions(self, cond=None, idx=(), condtype=(), target=(), lastdif=()):
+        """Conditional commands (ATALT / ATSPD; conditional.py:25-49) as the last stage of
+        every step (bsa_sim_set_conditions): ``cond`` is a ``bluesky_amd.conditional.Condition``
+        (kept: ``delete`` applies ``delac`` to it as well), or pass the arrays ``idx`` (aircraft
+        index), ``condtype`` (0 altitude, 1 speed), ``target``, ``lastdif``.  A step in which a
+        condition fires completes, then the batch stops: ``step`` returns early, ``conditions()``
+        names the fired ones, and the caller executes their commands before stepping on
+        (``bluesky_amd.conditional.run`` is that loop).  None / empty switches it off.
+        One rank only."""
+        self._cond = cond
+        if cond is not None:
+            idx, condtype, target, lastdif = cond.arrays() if cond.ncond else ((), (), (), ())
+        self.ctx.sim_set_conditions(idx, condtype, target, lastdif)
+
+    def conditions(self):
+        """(indices of the conditions that fired at the last stop, ascending, as rows of the
+        table before this call; the step count at which they fired) -- bsa_sim_cond_poll.  The
+        fired conditions then leave the device table (delcondition); without a stop since
+        the last call the list is empty."""
+        return self.ctx.sim_cond_poll()
+
+    def read_conditions(self):
+        """dict of idx, condtype, target, lastdif of the live conditions (bsa_sim_read_conditions)."""
+        return self.ctx.sim_read_conditions()
 
     def set_params(self, p):
         """New parameters for the running sim (bsa_sim_set_params; e.g. ZONER / DTLOOK)."""
@@ -214,6 +241,13 @@ class ResidentSim:
         the next ``sectors()``."""
         d = np.unique(np.asarray(idx, dtype=np.int64).ravel())
         self.ctx.sim_delete(d)
+        if getattr(self, '_cond', None) is not None:   # Traffic.delete: cond.delac(idx), idx sorted (traffic.py:370-377)
+            self._cond.delac(d)
+            # the reference's sequential delac can leave a condition of the last aircraft pointing past the
+            # new n (it would raise at the next update there); the device table drops it, so does the drop-in
+            past = np.where(np.asarray(self._cond.idx) >= self.ctx.n)[0]
+            if len(past):
+                self._cond.delcondition(past)
         if getattr(self, '_sect_names', None):
             pos, words = self.ctx.sim_sectors_deleted()
             ids = getattr(self, 'ids', None)

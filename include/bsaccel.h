@@ -474,7 +474,13 @@ typedef struct bsa_sim_out {
 
 /* Upload the full state (length n, all ranks pass the same) and parameters. */
 int bsa_sim_init(bsa_ctx *ctx, int64_t n, const bsa_sim_state *s, const bsa_sim_params *p);
-/* Advance nsteps; collective when a communicator is set. */
+/* Advance nsteps; collective when a communicator is set.  With conditional
+ * commands on (bsa_sim_set_conditions) the call returns 0 after fewer steps
+ * when a condition fired: bsa_sim_steps_run says how many ran.  After such a
+ * stopped batch the "last detect" of bsa_sim_stats / bsa_fetch_pairs is one
+ * made on the state the stop left by the steps enqueued behind it (which
+ * changed nothing else) -- with cd_every > 1 possibly at a step count at which
+ * single steps would not have detected. */
 int bsa_sim_step(bsa_ctx *ctx, int nsteps);
 /* Pilot.applylimits with the OpenAP model (pilot.py:65-68 ->
  * performance/openap/perfoap.py:185-209) inside the step, between
@@ -647,6 +653,53 @@ int bsa_sim_set_turbulence(bsa_ctx *ctx, int on, const double *sd3, uint64_t see
 /* The call number of the next step's draws: set from *set_to when not NULL
  * (>= 0; continuing another sim's stream), then stored to *call when not NULL. */
 int bsa_sim_turb_call(bsa_ctx *ctx, int64_t *call, const int64_t *set_to);
+/* ---------------------------------------------------------------- conditional commands
+ * Condition.update (bluesky/traffic/conditional.py:25-49; ATALT / ATSPD).  A
+ * condition is (idx, type, target, lastdif): the aircraft's index, type 0 =
+ * altitude / 1 = speed, the target [m or m/s CAS] and the difference at the
+ * last update.  Per condition, in numpy's order:
+ *   actual  = (type == 0) * alt[idx] + (type == 1) * cas[idx]
+ *   actdif  = target - actual;  fired = actdif * lastdif <= 0;  lastdif = actdif
+ * A condition with lastdif == 0 fires at the next update whatever the state; a
+ * non-finite product never fires.
+ *
+ * bsa_cond_update: one update over host arrays (idx / type / target / lastdif
+ * of ncond conditions, alt / cas of n aircraft).  lastdif is rewritten; fired
+ * (room for ncond) receives the fired conditions' numbers in ascending order
+ * (np.where's), *count how many.  Every idx and type is checked first;
+ * ncond = 0 launches nothing. */
+int bsa_cond_update(bsa_ctx *ctx, int64_t ncond, const int32_t *idx, const int32_t *type, const double *target,
+                    double *lastdif, int64_t n, const double *alt, const double *cas, int32_t *fired,
+                    int64_t *count);
+/* cond.update() as the last stage of every resident step (traffic.py:419; off
+ * by default, ncond = 0 switches it off).  idx is the aircraft index
+ * (bsa_sim_row_ids); speed conditions compare vtas2cas(tas, the altitude before
+ * the step's position update), altitude conditions the altitude the step left
+ * (turbulence included).  A step in which a condition fires is completed, the
+ * fired conditions are dead from then on (delcondition) and the batch STOPS
+ * after it: bsa_sim_step returns 0 having run fewer steps (bsa_sim_steps_run),
+ * and the host executes the commands before it steps on.  One rank only:
+ * refused when a communicator of several ranks is set. */
+int bsa_sim_set_conditions(bsa_ctx *ctx, int64_t ncond, const int32_t *idx, const int32_t *type, const double *target,
+                           const double *lastdif);
+/* Steps the last bsa_sim_step call ran (fewer than asked when a stage stopped
+ * the batch) and the sim's step count; either pointer may be NULL.  After a
+ * stopped batch the last detect's counts and pair lists describe the state
+ * the stop left (see bsa_sim_step), not the last completed step's own detect. */
+int bsa_sim_steps_run(bsa_ctx *ctx, int64_t *last_batch, int64_t *total);
+/* The conditions that fired at the last stop, ascending, as numbers of the table
+ * before this call (as uploaded, or as the last poll / delete left it); *step:
+ * the step count at which they fired.  Then the dead conditions leave the
+ * table, the rest keep their order (delcondition).  *count > cap: nothing is
+ * written or consumed.  Without a stop since the last poll *count = 0. */
+int bsa_sim_cond_poll(bsa_ctx *ctx, int64_t cap, int32_t *fired, int64_t *count, int64_t *step);
+/* The live table, lastdif included (any array may be NULL; *count > cap:
+ * nothing written).  bsa_sim_delete applies Condition.delac to it
+ * (conditional.py:108-128): one deleted aircraft after another in ascending
+ * order, each removing its conditions and shifting the indices above it down;
+ * bsa_sim_create leaves it alone. */
+int bsa_sim_read_conditions(bsa_ctx *ctx, int64_t cap, int32_t *idx, int32_t *type, double *target, double *lastdif,
+                            int64_t *count);
 /* ---------------------------------------------------------------- area filter
  * areafilter.checkInside (bluesky/tools/areafilter.py:29-35) for a table of
  * shapes in one launch.  A shape (areafilter.py:52-104):

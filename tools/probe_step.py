@@ -7,13 +7,14 @@ untimed ones (the device at steady clocks, as bench.py's --settle).  Collectives
 (box all-gather, halo send / recv, gate all-reduce) are excluded: they need
 the 8-GPU node.  Prints every rank's ms per step and the slowest.
 Usage: python tools/probe_step.py [WORKLOAD [R [STEPS [RANK [SETTLE]]]]] [--perf | --forces] [--fms]
-[--resume-nav] [--recover] [--turb]  (RANK:
+[--resume-nav] [--recover] [--turb] [--cond]  (RANK:
 that rank of R only, -1 all; SETTLE default 200; --perf: OpenAP phase / envelope in the step,
 --forces: also its drag / thrust / fuel-flow launch; --fms: Autopilot.update in the
 step, every aircraft on a generated 4-waypoint route; --resume-nav: ASAS.update's
 bookkeeping and ResumeNav in the CD step; --recover: waypoint recovery after ResumeNav, DESIGN.md 3.23
 -- implies --fms and --resume-nav, its cost is --recover against --fms --resume-nav; --turb: Turbulence.Woosh
-as the step's last stage, DESIGN.md 3.25: k_sim_turb and the next detect's own K0b in place of K4''s records)"""
+as the step's last stage, DESIGN.md 3.25: k_sim_turb and the next detect's own K0b in place of K4''s records;
+--cond: 10 000 conditional commands of both types that never fire, DESIGN.md 3.29: k_sim_cond every step)"""
 import json
 import os
 import sys
@@ -48,7 +49,9 @@ def main():
     with_fms = with_fms or recover
     resume_nav = recover or '--resume-nav' in sys.argv
     turb = '--turb' in sys.argv              # Turbulence.Woosh in the step (bsa_sim_set_turbulence)
-    sys.argv = [a for a in sys.argv if a not in ('--forces', '--perf', '--fms', '--recover', '--resume-nav', '--turb')]
+    with_cond = '--cond' in sys.argv         # conditional commands in the step (bsa_sim_set_conditions), none firing
+    sys.argv = [a for a in sys.argv if a not in ('--forces', '--perf', '--fms', '--recover', '--resume-nav', '--turb',
+                                                 '--cond')]
     name = sys.argv[1] if len(sys.argv) > 1 else 'global1m'
     R = int(sys.argv[2]) if len(sys.argv) > 2 else 8
     steps = int(sys.argv[3]) if len(sys.argv) > 3 else 40
@@ -66,12 +69,18 @@ def main():
             sim.set_recovery()
     if turb:
         sim.set_turbulence(True, (0, 0.1, 0.1), seed=5)
+    if with_cond:
+        import numpy as np
+        k = np.random.default_rng(5).integers(0, t.ntraf, 10000)
+        typ = np.arange(10000) % 2
+        target = np.where(typ == 0, init['alt'][k] + 20000.0, 1.0)      # far above / far below: no crossing
+        sim.set_conditions(idx=k, condtype=typ, target=target, lastdif=np.where(typ == 0, 20000.0, -100.0))
     if with_perf:
         table, tidx, ftable, mass = openap_tables(t.ntraf)
         sim.set_perf(table, tidx)
         if forces:
             sim.set_forces(ftable, mass)
-    out = dict(perf=with_perf, forces=forces, fms=with_fms, resume_nav=resume_nav, recover=recover, turb=turb)
+    out = dict(perf=with_perf, forces=forces, fms=with_fms, resume_nav=resume_nav, recover=recover, turb=turb, cond=with_cond)
     for ranks in sorted({1, R}) if only is None else [R]:
         per = []
         for r in range(ranks) if only is None else [only]:
