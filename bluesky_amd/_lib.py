@@ -302,7 +302,19 @@ SIGNATURES.update({
     'bsa_sim_set_sectors': (ctypes.c_int, [_vp, ctypes.c_int64, _c_i32p, ctypes.c_int64]),
     'bsa_sim_sectors_poll': (ctypes.c_int, [_vp] + [_c_u64p] * 5 + [_c_i64p, _c_i64p, _c_u64p, _c_u64p]),
     'bsa_sim_sectors_deleted': (ctypes.c_int, [_vp, ctypes.c_int64, _c_i64p, _c_u64p, _c_i64p]),
+    'bsa_exparea_update': (ctypes.c_int, [_vp, ctypes.c_int64] + [_c_dp] * 10 + [_c_u8p, ctypes.c_double,
+                                          ctypes.POINTER(AreaShape), ctypes.c_int64, _c_dp, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_double, _c_i32p, _c_i64p, _c_i32p, _c_i64p]),
+    'bsa_sim_set_exparea': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int32, ctypes.c_double, ctypes.c_int64,
+                                           ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double]),
+    'bsa_sim_exparea_simt': (ctypes.c_int, [_vp, ctypes.c_double]),
+    'bsa_sim_exparea_poll': (ctypes.c_int, [_vp, ctypes.c_int64, _c_i32p, _c_i64p, _c_i32p, _c_i64p, _c_dp, _c_i64p]),
+    'bsa_sim_read_exparea': (ctypes.c_int, [_vp] + [_c_dp] * 5 + [_c_u8p]),
 })
+
+# one record of bsa_sim_exparea_poll (fp64 words, per exited aircraft)
+EXPAREA_RECORD = ('create_time', 'distance2D', 'distance3D', 'work', 'lat', 'lon', 'alt', 'tas', 'vs', 'hdg', 'active',
+                  'ap_alt', 'ap_tas', 'ap_vs', 'ap_trk', 'asas_alt', 'asas_tas', 'asas_vs', 'asas_trk')
 
 GEOVEC_GSMIN, GEOVEC_GSMAX, GEOVEC_TRK, GEOVEC_VSMIN, GEOVEC_VSMAX = 1, 2, 4, 8, 16
 GEOVEC_MAX = 256
@@ -1198,6 +1210,62 @@ class Context:
                                                     ptr(o['target']), ptr(o['lastdif']), ctypes.byref(count)),
                    'bsa_sim_read_conditions')
         return {k: v[:count.value].copy() for k, v in o.items()}
+
+    # ---------------------------------------------------------------- experiment area
+    def exparea_update(self, gs, vs, alt, lat, lon, thrust, distance2D, distance3D, work, oldalt, inside, dt, area,
+                       active=True, swtaxi=True, swtaxialt=1500 * 0.3048):
+        """bsa_exparea_update: one Area.update (plugins/area.py:112-142).  ``area``: ``(type, coordinates,
+        top, bottom)`` as for ``area_table``, or None (``name`` None: everything is outside).  Returns a dict
+        of the updated distance2D / distance3D / work / oldalt / inside and delidx / delidxalt (ascending)."""
+        ins = [f64(x).ravel() for x in (gs, vs, alt, lat, lon, thrust)]
+        out = [f64(x).ravel().copy() for x in (distance2D, distance3D, work, oldalt)]
+        flag = np.array(inside, dtype=bool).ravel().astype(np.uint8)
+        n = len(ins[0])
+        if any(len(x) != n for x in ins + out + [flag]):
+            raise ValueError('experiment area arrays differ in length')
+        tab, verts = (None, np.zeros((0, 2))) if area is None else area_table([area])
+        l1, l2 = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        c1, c2 = ctypes.c_int64(0), ctypes.c_int64(0)
+        self.check(self.lib.bsa_exparea_update(self.h, n, *[ptr(x) for x in ins + out], ptr(flag, _c_u8p), float(dt), tab,
+                                               len(verts), ptr(verts), int(bool(active)), int(bool(swtaxi)),
+                                               float(swtaxialt), ptr(l1, _c_i32p), ctypes.byref(c1), ptr(l2, _c_i32p),
+                                               ctypes.byref(c2)), 'bsa_exparea_update')
+        return dict(distance2D=out[0], distance3D=out[1], work=out[2], oldalt=out[3], inside=flag.astype(bool),
+                    delidx=l1[:c1.value].astype(np.int64), delidxalt=l2[:c2.value].astype(np.int64))
+
+    def sim_set_exparea(self, on, shape_idx=-1, dt=0.5, every=1, simt=0.0, active=True, swtaxi=True,
+                        swtaxialt=1500 * 0.3048):
+        """bsa_sim_set_exparea: the experiment area as the step's last stage (``shape_idx`` -1: no area)."""
+        self.check(self.lib.bsa_sim_set_exparea(self.h, int(bool(on)), int(shape_idx), float(dt), int(every), float(simt),
+                                                int(bool(active)), int(bool(swtaxi)), float(swtaxialt)),
+                   'bsa_sim_set_exparea')
+
+    def sim_exparea_simt(self, simt):
+        """bsa_sim_exparea_simt: the sim time aircraft created from now on get as create_time."""
+        self.check(self.lib.bsa_sim_exparea_simt(self.h, float(simt)), 'bsa_sim_exparea_simt')
+
+    def sim_exparea_poll(self):
+        """bsa_sim_exparea_poll: dict of delidx, delidxalt (ascending), step and ``records`` -- per exited
+        aircraft a dict over EXPAREA_RECORD -- of the last stop; empty lists without one."""
+        cap = max(self.n, 1)
+        l1, l2 = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        rec = np.zeros((cap, len(EXPAREA_RECORD)))
+        c1, c2, step = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self.check(self.lib.bsa_sim_exparea_poll(self.h, cap, ptr(l1, _c_i32p), ctypes.byref(c1), ptr(l2, _c_i32p),
+                                                 ctypes.byref(c2), ptr(rec), ctypes.byref(step)), 'bsa_sim_exparea_poll')
+        r = rec[:c1.value]
+        return dict(delidx=l1[:c1.value].astype(np.int64), delidxalt=l2[:c2.value].astype(np.int64), step=int(step.value),
+                    records={k: r[:, q].copy() for q, k in enumerate(EXPAREA_RECORD)})
+
+    def sim_read_exparea(self):
+        """bsa_sim_read_exparea: dict of distance2D, distance3D, work, oldalt, create_time, inside (full n)."""
+        keys = ('distance2D', 'distance3D', 'work', 'oldalt', 'create_time')
+        o = {k: np.zeros(self.n) for k in keys}
+        ins = np.zeros(self.n, np.uint8)
+        self.check(self.lib.bsa_sim_read_exparea(self.h, *[ptr(o[k]) for k in keys], ptr(ins, _c_u8p)),
+                   'bsa_sim_read_exparea')
+        o['inside'] = ins.astype(bool)
+        return o
 
     def sim_cd(self):
         """bsa_sim_cd: one CD call (detect -> resolver -> bookkeeping) without kinematics."""

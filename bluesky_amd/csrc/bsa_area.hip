@@ -285,6 +285,7 @@ extern "C" int bsa_sim_set_areas(bsa_ctx *cc, int64_t nshapes, const bsa_area_sh
   BSA_HIP(c, hipStreamSynchronize(c->stream));  // (no pass in flight reads the old table)
   bsa::sect_off(c);  // the sectors named shapes of the old table
   bsa::geovec_off(c);  // ... and so did the geovectors
+  c->xa_has_shape = false;  // ... and the experiment area, which keeps its arrays: bsa_sim_set_exparea names the new shape
   if (!bsa::ensure(c, c->area_verts, (size_t)std::max<int64_t>(nvert, 1) * 16, "area vertices")) return -1;
   if (nvert) BSA_HIP(c, hipMemcpy(c->area_verts.p, verts, (size_t)nvert * 16, hipMemcpyHostToDevice));
   c->area_tab = tab;

@@ -129,7 +129,7 @@ constexpr int kSimCtlSticky = 24, kSimCtlSteps = 32, kSimCtlDemand = 40, kSimCtl
 // That word, not the sticky value, tells the host the batch stopped: a detect of a later, no-op step may still
 // overflow and store kStickyAborted over the stop
 constexpr unsigned kStickyAborted = 1u, kStickyStopped = 2u;
-enum StopStage : unsigned { kStopNone = 0, kStopCond = 1, kStopCount };  // (the experiment area's exit deletes: the next one)
+enum StopStage : unsigned { kStopNone = 0, kStopCond = 1, kStopArea = 2, kStopCount };  // (conditions; the experiment area)
 constexpr unsigned kStopTagMax = (1u << 24) - 1;
 constexpr unsigned stop_word(unsigned stage, unsigned tag) { return (stage << 24) | tag; }
 constexpr unsigned stop_stage(unsigned w) { return w >> 24; }
@@ -220,6 +220,7 @@ struct StepClocks {
   int64_t turb_call = 0;                   // turbulence (3.25): the call number of the next step's draws
   int64_t sect_ctr = 0;                    // sectors (3.27): steps since bsa_sim_set_sectors
   int64_t gv_ctr = 0;                      // geovectors (3.28): steps completed since bsa_sim_set_geovectors
+  int64_t area_ctr = 0;                    // experiment area (3.30): steps since bsa_sim_set_exparea
 };
 
 struct Ctx {
@@ -494,6 +495,19 @@ struct Ctx {
   int64_t cond_stop_step = 0;
   int64_t steps_last = 0, batch_steps0 = 0;  // (the step count at the running batch's begin: StepPlan::cond_tag)
 
+  // The experiment area (bsa_exparea.hip).  xa_stage: bsa_exparea_update's arrays.  In the resident
+  // step (bsa_sim_set_exparea): per aircraft (kSimArrays) the accumulators distance2D / distance3D / work, oldalt,
+  // create_time and a flag byte (inside / exit pending / taxi delete pending); xa_shape: the area (a copy of its
+  // row of area_tab) or none (name None: everything is outside); xa_every: the cadence, in steps of clk.area_ctr;
+  // xa_dt: the plugin's nominal dt; xa_ctl: one u64, the tag of the batch's step whose pass flagged a delete;
+  // xa_ws / xa_rec: the ordered compaction's words and the poll's records.  xa_pending: a stop with deletes nobody
+  // polled yet; xa_stop_step: its step count; xa_now: the simt new aircraft are created at (bsa_sim_exparea_simt)
+  DevBuf xa_stage, s_xd2, s_xd3, s_xwork, s_xoldalt, s_xctime, s_xflag, xa_ctl, xa_ws, xa_rec;
+  bool sim_exparea = false, xa_has_shape = false, xa_active = false, xa_swtaxi = true, xa_pending = false;
+  bsa_area_shape xa_shape{};
+  int64_t xa_every = 1, xa_stop_step = 0;
+  double xa_dt = 0.5, xa_swtaxialt = 0.0, xa_now = 0.0;
+
   // standalone geo matrices (bsa_geo.hip)
   DevBuf geo_in, geo_pts, geo_out;
   hipEvent_t geo_ev[2] = {nullptr, nullptr};
@@ -565,7 +579,7 @@ inline void *ptr_at(const void *strct, int k) { return ((void *const *)strct)[k]
 // it (bsa_traffic.hip: per_aircraft), bsa_sim_init allocates its kSimAlways rows
 // guard: kSimAlways allocated by bsa_sim_init; kSimDetect the last detect's per-row outputs (the detect's to
 // allocate); kSimOnUse once allocated (the reso lists); the others while Ctx::sim_<switch> is on
-enum SimGuard { kSimAlways, kSimDetect, kSimOnUse, kSimLimits, kSimPerf, kSimForces, kSimFms, kSimAtmos, kSimSectors };
+enum SimGuard { kSimAlways, kSimDetect, kSimOnUse, kSimLimits, kSimPerf, kSimForces, kSimFms, kSimAtmos, kSimSectors, kSimExparea };
 struct SimArray {
   BufRef buf;
   int esz, count;  // element size; sub-arrays of length n in the buffer
@@ -600,6 +614,9 @@ inline const SimArray kSimArrays[] = {
     {{&Ctx::s_fmsr}, 8, kFmsReals, false, kSimFms}, {{&Ctx::s_fmsf}, 1, kFmsFlags, false, kSimFms},
     {{&Ctx::s_fmsi}, 4, kFmsInts, false, kSimFms},   {{&Ctx::s_dropcnt}, 4, 1, false, kSimAlways},
     {{&Ctx::s_scur}, 8, 1, false, kSimSectors},      {{&Ctx::s_sprev}, 8, 1, false, kSimSectors},
+    {{&Ctx::s_xd2}, 8, 1, false, kSimExparea},       {{&Ctx::s_xd3}, 8, 1, false, kSimExparea},
+    {{&Ctx::s_xwork}, 8, 1, false, kSimExparea},     {{&Ctx::s_xoldalt}, 8, 1, false, kSimExparea},
+    {{&Ctx::s_xctime}, 8, 1, false, kSimExparea},    {{&Ctx::s_xflag}, 1, 1, false, kSimExparea},
 };
 // is the array part of the sim now (to be carried through a delete / create)?
 inline bool sim_array_on(Ctx *c, const SimArray &a) {
@@ -611,6 +628,7 @@ inline bool sim_array_on(Ctx *c, const SimArray &a) {
     case kSimFms: return c->sim_fms;
     case kSimAtmos: return c->sim_atmos;
     case kSimSectors: return c->sim_sect;
+    case kSimExparea: return c->sim_exparea;
     default: return true;
   }
 }
@@ -714,6 +732,20 @@ int cond_sim_launch(Ctx *c, unsigned tag);
 void cond_stopped(Ctx *c);  // batch_stopped: the stop was this stage's (the clocks are already those of the stop)
 int cond_note_deleted(Ctx *c, const std::vector<int64_t> &d);
 void cond_off(Ctx *c);
+
+// The experiment area of the step (bsa_exparea.hip): k_sim_exparea, the step's last launch (after
+// k_sim_cond) in the steps whose StepPlan::area_pass is set; tag as for cond_sim_launch.  exparea_batch_begin
+// zeroes the batch's "deletes pending" word (stream-ordered); exparea_step_flagged: did the pass of the batch's
+// step `tag` leave deletes pending (batch_stopped, after the batch's synchronisation)?  exparea_stopped: that
+// step's deletes wait for bsa_sim_exparea_poll.  exparea_passes_at: does the step at clk.area_ctr run the pass?
+// exparea_created: Area.create for the m aircraft bsa_sim_create appended after the first n (alt: theirs, host)
+bool exparea_passes_at(const Ctx *c);
+int exparea_sim_launch(Ctx *c, unsigned tag);
+int exparea_batch_begin(Ctx *c);
+int exparea_step_flagged(Ctx *c, unsigned tag, bool *flagged);
+void exparea_stopped(Ctx *c);
+int exparea_created(Ctx *c, int64_t n, int64_t m, const double *alt);
+void exparea_off(Ctx *c);
 
 // Sector occupancy (bsa_area.hip): sect_sim_launch after the last stage of a step whose StepPlan::sect_pass is
 // set (clk.sect_ctr + 1 a multiple of the cadence); sect_note_deleted by bsa_sim_delete before anything moves;

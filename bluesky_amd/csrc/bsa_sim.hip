@@ -211,7 +211,7 @@ void sim_release(Ctx *c) {
   // not per aircraft: staging, control words, tables, the FMS undo set, K2 + K4' double buffers
   DevBuf *rest[] = {&c->red, &c->g_send, &c->g_recv, &c->pg_send, &c->pg_recv, &c->sim_ctl, &c->s_ptab, &c->s_ftab,
                     &c->f_const, &c->s_fmsrows, &c->s_fmsur, &c->s_fmsuf, &c->s_fmsui, &c->gv_tab, &c->gv_shapes, &c->gv_undo,
-                    &c->gv_cnt, &c->xfer_stage, &c->lbyidx,
+                    &c->gv_cnt, &c->xfer_stage, &c->lbyidx, &c->xa_ctl, &c->xa_ws, &c->xa_rec,
                     &c->fetch_stage, &c->tpr_snap, &c->tpr_ctl, &c->nx_alt, &c->nx_vs, &c->nx_gse, &c->nx_gsn};
   for (auto *b : rest) release(*b);
   bk_release(c);
@@ -330,6 +330,9 @@ struct StepPlan {
   // + 1, what a stop raised by it carries (no clock: the stage evaluates every step)
   bool cond;
   unsigned cond_tag;
+  // the experiment area's pass (3.30) follows k_sim_cond: clk.area_ctr + 1 is a multiple of its cadence; a stop it
+  // raises carries cond_tag too
+  bool area_pass;
 };
 static StepPlan step_decide(const Ctx *c, bool rerun_first) {
   const DetectEnv &env = detect_env();
@@ -349,6 +352,7 @@ static StepPlan step_decide(const Ctx *c, bool rerun_first) {
   sp.sect_pass = c->sim_sect && (k.sect_ctr + 1) % c->sect_every == 0;
   sp.cond = c->sim_cond;
   sp.cond_tag = (unsigned)(k.steps - c->batch_steps0 + 1);
+  sp.area_pass = exparea_passes_at(c);
   return sp;
 }
 
@@ -363,6 +367,7 @@ static void step_advance(Ctx *c, const StepPlan &sp) {
   if (sp.cd) k.cd_calls++;
   if (c->sim_turb) k.turb_call++;
   if (c->sim_sect) k.sect_ctr++;
+  if (c->sim_exparea) k.area_ctr++;
   k.steps++;
 }
 
@@ -378,7 +383,7 @@ static int batch_begin(Ctx *c, bool kin, BatchBase *b) {
   *b = BatchBase{kin, c->clk, c->sim_gs_derivable};
   c->batch_steps0 = c->clk.steps;
   BSA_HIP(c, hipMemsetAsync((char *)c->sim_ctl.p + kSimCtlSticky, 0, 40, c->stream));  // sticky, steps_done, demands, stale
-  return 0;
+  return exparea_batch_begin(c);  // (its "deletes pending" word; nothing while the stage is off)
 }
 // the batch's only host synchronisation: ctl = sim_ctl words {sticky, steps
 // done, resopairs demand, key-block demand, stale}
@@ -412,7 +417,10 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long lon
     // Turbulence: the draws are a pure function of (seed, call, index); the completed steps took one call
     // number each, the aborted step's k_sim_turb returned behind the sticky word -- nothing to undo.
     // Sectors: the pass only reads state; the completed steps' updates are counted, the aborted step's pass
-    // returned behind the sticky word like every later one, so the re-run counts each update once
+    // returned behind the sticky word like every later one, so the re-run counts each update once.
+    // Experiment area: the pass writes its accumulators only in steps that complete -- the abort is raised in the
+    // step's detect, before the pass, which then returned behind the sticky word: nothing to undo, and the replayed
+    // clock makes the re-run count the pass once
     const StepPlan sp = step_decide(c, false);
     if (sp.fms_tick && fms_sim_restore(c)) return -1;
     if (sp.gv_apply && geovec_sim_restore(c)) return -1;
@@ -481,7 +489,14 @@ static int batch_stopped(Ctx *c, const BatchBase &base, const unsigned long long
   c->sim_gathered = c->nranks == 1;
   switch (stop_stage(sw)) {  // the raising stage's host side
     case kStopCond: cond_stopped(c); break;
+    case kStopArea: break;  // (asked below, like after any other stage's stop)
   }
+  // the experiment area's pass of the stopping step ran in full whichever stage raised the stop: did it leave deletes?
+  bool flagged = false;
+  if (exparea_step_flagged(c, (unsigned)tag, &flagged)) return -1;
+  if (flagged) exparea_stopped(c);
+  else if (stop_stage(sw) == kStopArea)
+    return fail(c, "internal error: the experiment area stopped the batch in step %lld without a delete", (long long)tag);
   return 0;
 }
 
@@ -609,6 +624,9 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
   if (sp.sect_pass && sect_sim_launch(c)) return -1;  // sector occupancy: reads what the step left (sectorcount.py:53-79)
   // cond.update() (traffic.py:419): reads what the step left; last, so that a stop it raises cuts nothing of this step
   if (sp.cond && cond_sim_launch(c, sp.cond_tag)) return -1;
+  // the AREA plugin's update follows traf.update (simulation.py: plugin.update after traf.update), whose last
+  // statements are cond.update() and an inactive trails.update: the step's last launch
+  if (sp.area_pass && exparea_sim_launch(c, sp.cond_tag)) return -1;
   if (sp.prep)
     c->prep.keep({pa.rpz, pa.hpz, pa.tla, (double)pa.mid, c->n});
   else
@@ -623,7 +641,7 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
 }
 
 // every stage with a launch of its own, off (fms_off takes recovery and the geovectors with it): a new sim
-static void stages_off(Ctx *c) { forces_off(c), fms_off(c), turb_off(c), sect_off(c), cond_off(c); }
+static void stages_off(Ctx *c) { forces_off(c), fms_off(c), turb_off(c), sect_off(c), cond_off(c), exparea_off(c); }
 
 }  // namespace bsa
 
@@ -714,7 +732,7 @@ int bsa_sim_step(bsa_ctx *cc, int nsteps) {
   if (c->simp.winddim == 3 && c->wf3_nvec < 1)
     return bsa::fail(c, "winddim 3 needs a 3-D wind field (bsa_set_windfield3d)");
   if (nsteps < 0) return bsa::fail(c, "negative step count");
-  if (c->sim_cond && (unsigned)nsteps > bsa::kStopTagMax)
+  if ((c->sim_cond || c->sim_exparea) && (unsigned)nsteps > bsa::kStopTagMax)
     return bsa::fail(c, "at most %u steps per call while a stage that can stop the batch is on", bsa::kStopTagMax);
   BSA_HIP(c, hipSetDevice(c->device));
   const int64_t start = c->clk.steps, target = start + nsteps;

@@ -325,6 +325,7 @@ int bsa_sim_delete(bsa_ctx *cc, int64_t k, const int64_t *idx) {
   BSA_HIP(c, hipStreamSynchronize(c->stream));
   if (bsa::sect_note_deleted(c, k, idx)) return -1;  // sector occupancy: they count as left
   if (bsa::cond_note_deleted(c, d)) return -1;       // Condition.delac (traffic.py:377)
+  c->xa_pending = false;  // (the delete lists of an unpolled stop name the old indices)
   bsa::Multi mu;
   if (bsa::multi_begin(c, mu)) return -1;
   // old index -> new index (np.delete keeps the order of the rest), -1 = deleted
@@ -473,6 +474,7 @@ int bsa_sim_create(bsa_ctx *cc, int64_t m, const bsa_sim_state *s) {
       BSA_HIP(c, hipMemsetAsync((char *)pa.b->p + ((size_t)k * nn + n) * pa.esz, 0, (size_t)m * pa.esz, c->stream));
   }
   BSA_HIP(c, hipStreamSynchronize(c->stream));
+  if (bsa::exparea_created(c, n, m, (const double *)bsa::ptr_at(s, 2))) return -1;  // Area.create
   // new aircraft have no resopairs and were in no previous pair set: empty CSR rows
   std::vector<int> ident((size_t)n);
   for (int64_t k = 0; k < n; ++k) ident[(size_t)k] = (int)k;

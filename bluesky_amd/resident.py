@@ -320,6 +320,40 @@ class ResidentSim:
                 out[name].update(inside=c, inside_before=p)
         return out
 
+    def set_exparea(self, shape_name=None, dt=0.5, every=None, simt=0.0, taxi=True, taxialt=1500 * FT, active=None):
+        """The experiment area inside the step (plugins/area.py:107-175; bsa_sim_set_exparea): flight
+        statistics per aircraft (2-D / 3-D distance, work) and the exit and taxi deletes.  ``shape_name``: an
+        area of ``set_areas`` (``Area.name``), None for no area (everything is outside), False switches the
+        stage off.  ``dt``: the plugin's nominal interval, which the accumulators use; the pass runs every
+        ``every`` steps counted from the first call, default ``max(dt, simdt) / simdt``, as the step's last
+        launch.  ``taxi`` / ``taxialt``: ``Area.swtaxi`` / ``swtaxialt`` (taxi False: an aircraft sinking
+        through ``taxialt`` is deleted); ``active``: ``Area.active``, default whether there is an area.
+        The first call starts the arrays as ``Area.create`` would for every aircraft at ``simt`` (``inside``
+        all False); later calls change the parameters only.  A step with an exit or a taxi delete
+        completes, then the batch stops: ``step`` returns early and ``exparea_events()`` lists them
+        (``bluesky_amd.exparea.run`` is that loop).  ``work`` needs ``set_forces``: without it, it stays 0.
+        One rank only."""
+        if shape_name is False:
+            self.ctx.sim_set_exparea(False)
+            return
+        tab = getattr(self, '_area_names', [])
+        if shape_name is not None and shape_name not in tab:
+            raise ValueError('set_exparea: no area %r (set_areas)' % (shape_name,))
+        if every is None:
+            every = max(1, int(round(max(dt, self.params.simdt) / self.params.simdt)))
+        self.ctx.sim_set_exparea(True, -1 if shape_name is None else tab.index(shape_name), dt, every, simt,
+                                 (shape_name is not None) if active is None else active, taxi, taxialt)
+
+    def exparea_events(self):
+        """The deletes of the last stop (bsa_sim_exparea_poll): dict of ``delidx`` (exits) and ``delidxalt``
+        (taxi deletes), aircraft indices ascending as ``np.where`` gives them, ``step``, and ``records`` -- the
+        log columns the device has, per exited aircraft.  Read once; empty without a stop since the last call."""
+        return self.ctx.sim_exparea_poll()
+
+    def read_exparea(self):
+        """dict of distance2D, distance3D, work, oldalt, create_time, inside by aircraft index (bsa_sim_read_exparea)."""
+        return self.ctx.sim_read_exparea()
+
     def set_geovectors(self, geovecs, every=1):
         """Geovectoring inside the step (plugins/geovector.py:76-128; bsa_sim_set_geovectors):
         ``geovecs`` is the plugin's list of ``[area, gsmin, gsmax, trkmin, trkmax, vsmin, vsmax]``

@@ -783,6 +783,58 @@ int bsa_sim_sectors_poll(bsa_ctx *ctx, uint64_t *n_tot, uint64_t *arrived, uint6
  * call with room.  Read it after each bsa_sim_delete: positions of two calls
  * are not told apart. */
 int bsa_sim_sectors_deleted(bsa_ctx *ctx, int64_t cap, int64_t *pos, uint64_t *words, int64_t *count);
+/* ---------------------------------------------------------------- experiment area
+ * The AREA plugin (plugins/area.py:85-220): flight statistics per aircraft and
+ * the deletes at the boundary.  One Area.update over host arrays of n aircraft
+ * (area.py:112-142), in the reference's order, fp64:
+ *   returns at once when swtaxi and not active;
+ *   resultantspd = sqrt(gs*gs + vs*vs);  distance2D += dt*gs;
+ *   distance3D += dt*resultantspd;  work += (thrust*dt)*resultantspd
+ *   (thrust NULL: work stays);
+ *   !swtaxi: delidxalt = where((oldalt >= swtaxialt) * (alt < swtaxialt)), then
+ *   oldalt = alt;
+ *   delidx = where(inside * !inside_now), inside = inside_now, with inside_now
+ *   the area filter's test of `shape` (its polygon ring in verts[nvert][2]);
+ *   shape NULL is Area.name None: everything is outside.
+ * inside: one byte per aircraft (0 / 1), updated like the fp64 arrays.  Both
+ * lists are ascending (np.where's order) and hold at most n entries.  n == 0
+ * launches nothing. */
+int bsa_exparea_update(bsa_ctx *ctx, int64_t n, const double *gs, const double *vs, const double *alt,
+                       const double *lat, const double *lon, const double *thrust, double *distance2D,
+                       double *distance3D, double *work, double *oldalt, uint8_t *inside, double dt,
+                       const bsa_area_shape *shape, int64_t nvert, const double *verts, int active, int swtaxi,
+                       double swtaxialt, int32_t *delidx, int64_t *ndel, int32_t *delidxalt, int64_t *ndelalt);
+/* The same update as the resident step's last stage (after the conditions), in
+ * the steps that bring the count of steps since the first enabling call to a
+ * multiple of `every` (every = max(dt, simdt) / simdt; dt itself is the
+ * plugin's nominal interval, which the accumulators use).  shape_idx: a shape
+ * of bsa_sim_set_areas, or -1 for none.  It reads the state the step left and
+ * the thrust of that step's bsa_sim_set_forces launch (forces off: work stays
+ * 0).  The first call with on != 0 starts the arrays as Area.create does for
+ * every aircraft: accumulators 0, oldalt = alt, create_time = simt, inside all
+ * false -- an aircraft must be seen inside once before it can exit; later calls
+ * change the parameters only; on == 0 switches the stage off.  bsa_sim_delete
+ * and bsa_sim_create carry the arrays (new aircraft: oldalt = their alt,
+ * create_time = the last bsa_sim_exparea_simt); bsa_sim_set_areas forgets the
+ * shape (set it again).  A step in which an aircraft exits or sinks through
+ * swtaxialt completes, then the batch stops as for a fired condition (see
+ * bsa_sim_step / bsa_sim_steps_run); the deletes themselves are the caller's.
+ * While on, bsa_sim_step takes at most 2^24 - 1 steps per call.  One rank only. */
+int bsa_sim_set_exparea(bsa_ctx *ctx, int on, int32_t shape_idx, double dt, int64_t every, double simt, int active,
+                        int swtaxi, double swtaxialt);
+int bsa_sim_exparea_simt(bsa_ctx *ctx, double simt);
+/* The deletes of the last stop: delidx (exits) and delidxalt (taxi deletes),
+ * aircraft indices ascending; *step: the step count of that stop.  records:
+ * 19 doubles per exited aircraft, in delidx's order -- create_time distance2D
+ * distance3D work lat lon alt tas vs hdg asas.active, then ap alt tas vs trk
+ * and asas alt tas vs trk (the pilot's select is the caller's).  A count above
+ * cap: nothing is written or consumed.  Without a stop with deletes since the
+ * last poll both counts are 0. */
+int bsa_sim_exparea_poll(bsa_ctx *ctx, int64_t cap, int32_t *delidx, int64_t *ndel, int32_t *delidxalt,
+                         int64_t *ndelalt, double *records, int64_t *step);
+/* The arrays by aircraft index, n long each (any may be NULL). */
+int bsa_sim_read_exparea(bsa_ctx *ctx, double *distance2D, double *distance3D, double *work, double *oldalt,
+                         double *create_time, uint8_t *inside);
 /* ---------------------------------------------------------------- geovectoring
  * plugins/geovector.py:76-128: per area an allowed interval for ground speed,
  * track and vertical speed.  The geovectors are an ordered list; each is

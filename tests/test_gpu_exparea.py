@@ -1,0 +1,321 @@
+"""GPU: the experiment area (plugins/area.py) -- bsa_exparea_update against the reference's golden, and
+the resident step's stage with the batch stop it raises: the flight golden through ``exparea.run``, the
+stage against tests/exparea_np.py on read-back state, one batch against single steps with conditions
+firing in the same step, stops next to aborts, delete / create, refusals."""
+import os
+
+import numpy as np
+import pytest
+
+from bluesky_amd import _lib, areafilter, conditional, exparea, fms, resident
+from tests import exparea_np, util
+from tests.test_exparea_np import case_of
+from tests.test_gpu_cond import altitudes, climbers, crossing, dress, movers, traf_of
+from tests.test_gpu_multirank import run_ranks
+
+pytestmark = pytest.mark.gpu
+FT = 0.3048
+EVERYWHERE = [-89., -179., 89., 179.]
+
+
+@pytest.fixture(scope='module')
+def upd():
+    return dict(np.load(os.path.join(util.GOLDEN, 'exparea_update.npz')))
+
+
+# ---------------------------------------------------------------- standalone
+@pytest.mark.parametrize('n', [1, 63, 64, 65, 257])
+def test_standalone_update_matches_golden(ctx, upd, n):
+    """Every recorded case at this n: both lists equal (ascending), the arrays bitwise (a NaN as a NaN)."""
+    names = [str(x) for x in upd['names'] if str(x).startswith('n%d_' % n)]
+    assert len(names) == 6
+    for name in names:
+        inp, st, area, swtaxi, active, exp = case_of(upd, name)
+        got = ctx.exparea_update(dt=float(upd['dt']), area=area, active=active, swtaxi=swtaxi,
+                                 swtaxialt=float(upd['swtaxialt']), **inp, **st)
+        assert np.array_equal(got['delidx'], exp['delidx']) and np.array_equal(got['delidxalt'], exp['delidxalt']), name
+        for k in exparea_np.ARRAYS:
+            e = np.asarray(exp[k])
+            num = ~np.isnan(e.astype(np.float64))
+            assert got[k][num].tobytes() == e[num].tobytes(), (name, k)
+            assert np.isnan(got[k][~num].astype(np.float64)).all(), (name, k)
+
+
+def test_standalone_empty_and_refusals(ctx):
+    z = np.zeros(0)
+    got = ctx.exparea_update(z, z, z, z, z, z, z, z, z, z, np.zeros(0, bool), 0.5, ('BOX', EVERYWHERE, 1e9, -1e9))
+    assert len(got['delidx']) == 0 and len(got['delidxalt']) == 0
+    o = np.ones(3)
+    with pytest.raises((_lib.AccelError, ValueError)):
+        ctx.exparea_update(o, o, o, o, o, o, o, o, o, o, np.zeros(3, bool), 0.5, ('BOX', [np.nan, 0., 1., 1.], 1e9, -1e9))
+
+
+# ---------------------------------------------------------------- the flight golden
+def test_resident_follows_the_flight_golden(ctx):
+    """exparea_flight64 (the reference's kinematics and its Area, TAXI OFF) through exparea.run in batches of
+    100: every stop at the recorded step with the recorded lists, the 17 log columns of every row -- ids,
+    create_time, flight time and the accumulators bitwise (the speeds they integrate come from additions and
+    multiplications alone), the state columns within the 1e-9 rule of the resident-step goldens --, the
+    survivors, and the final arrays."""
+    from tests.test_gpu_sim import SCALES
+    g = dict(np.load(os.path.join(util.GOLDEN, 'exparea_flight64.npz')))
+    init = {k[5:]: np.array(v) for k, v in g.items() if k.startswith('init_')}
+    p = resident.params(simdt=float(g['simdt']), cd_every=1000000, rpz=1.0, hpz=1.0, tla=1.0)   # ASAS inactive, as captured
+    sim = resident.ResidentSim({k: init[k] for k in _lib.SIM_STATE_FIELDS}, p, ctx=ctx)
+    areafilter.reset()
+    areafilter.defineArea('EXP', str(g['area_type']), g['area_coords'], float(g['area_levels'][0]), float(g['area_levels'][1]))
+    rows = []
+    area = exparea.Area(logger=lambda *cols: rows.append(cols))
+    area.dt = float(g['dt'])
+    area.attach(sim, ids=[str(x) for x in g['ids']])
+    assert area.every() == int(g['every'])
+    assert area.set_area('EXP')[0]
+    area.set_taxi(False, float(g['swtaxialt']))
+    events, _ = exparea.run(sim, area, int(g['nsteps']), batch=100)
+    areafilter.reset()
+    assert [e['step'] for e in events] == [int(x) for x in g['ev_step']]
+    off, offa = g['ev_off'], g['ev_offalt']
+    for q, e in enumerate(events):
+        assert np.array_equal(e['delidx'], g['ev_delidx'][off[q]:off[q + 1]]), q
+        assert np.array_equal(e['delidxalt'], g['ev_delidxalt'][offa[q]:offa[q + 1]]), q
+        assert e['simt'] == g['ev_simt'][q]
+    assert len(rows) == sum(1 for e in events if len(e['delidx'])) and all(len(r) == 17 for r in rows)
+    for q, name in enumerate(exparea_np.LOG_COLUMNS):
+        got, exp = np.concatenate([r[q] for r in rows]), g['log_' + name]
+        if name == 'id':
+            assert [str(x) for x in got] == [str(x) for x in exp]
+        elif name in ('create_time', 'flight_time', 'distance2D', 'distance3D', 'work', 'asas_active'):
+            print(name, 'max abs difference', np.abs(np.asarray(got, float) - np.asarray(exp, float)).max())
+            assert np.asarray(got, dtype=np.float64).tobytes() == np.asarray(exp, dtype=np.float64).tobytes(), name
+        else:
+            scale = SCALES[name.replace('pilot_', '')] if name.replace('pilot_', '') in SCALES else 1e4
+            ok, msg = util.close(got, exp, scale)
+            assert ok, '%s: %s' % (name, msg)
+    assert area.ids == [str(x) for x in g['survivors']]
+    fin, tr = sim.read_exparea(), sim.read()
+    for k in ('distance2D', 'distance3D', 'work', 'oldalt', 'create_time', 'inside'):
+        e = g['final_' + k]
+        if k == 'oldalt':
+            ok, msg = util.close(fin[k], e, SCALES['alt'])
+            assert ok, msg
+        else:
+            assert np.asarray(fin[k]).tobytes() == np.asarray(e).tobytes(), k
+    for k in ('lat', 'lon', 'alt', 'tas', 'hdg', 'vs'):
+        ok, msg = util.close(tr[k], g['final_' + k], SCALES[k])
+        assert ok, '%s: %s' % (k, msg)
+
+
+# ---------------------------------------------------------------- the resident stage
+@pytest.mark.parametrize('every', [1, 3])
+def test_stage_follows_the_numpy_restatement(ctx, every):
+    """The stage against tests/exparea_np.py one step at a time on read-back state, with FMS, OpenAP forces and
+    turbulence on: gs / vs / alt / lat / lon after the step, thrust of that step's forces launch; arrays
+    bitwise, lists equal; rows are aircraft indices whatever the home order.  TAXI OFF on a circle."""
+    from tests.test_gpu_perf_forces import forces_sim, traffic
+    tr = traffic(700, 23)
+    init = tr['init']
+    sim = forces_sim(tr, resident.params(cd_every=2), ctx)
+    sim.set_fms(*fms.synthetic_routes(init, seed=23))
+    sim.set_turbulence(True, (0.5, 0.5, 0.5), seed=3)
+    circ = ('CIRCLE', [float(np.median(init['lat'])), float(np.median(init['lon'])), 12.0], 1e9, -1e9)
+    sim.set_areas({'C': circ})
+    taxialt = 150.0
+    sim.set_exparea('C', dt=0.5, every=every, simt=3.0, taxi=False, taxialt=taxialt)
+    st = dict(distance2D=np.zeros(700), distance3D=np.zeros(700), work=np.zeros(700), oldalt=init['alt'].copy(),
+              inside=np.zeros(700, bool))
+    nexit = ntaxi = 0
+    for step in range(1, 13):
+        ran = sim.step(1)
+        assert ran == 1
+        r, f = sim.read(), sim.read_forces()
+        ev = sim.exparea_events()
+        if step % every == 0:
+            st, d1, d2 = exparea_np.update(st, r['gs'], r['vs'], r['alt'], r['lat'], r['lon'], f['thrust'], 0.5, circ, True,
+                                           False, taxialt)
+            assert np.array_equal(ev['delidx'], d1) and np.array_equal(ev['delidxalt'], d2), step
+            assert ev['step'] == step or len(d1) + len(d2) == 0
+            for k, col in (('lat', 'lat'), ('alt', 'alt'), ('tas', 'tas'), ('distance2D', 'distance2D')):
+                src = r[k] if k in r else st[k]
+                assert np.array_equal(ev['records'][col], src[d1]), (step, k)
+            nexit, ntaxi = nexit + len(d1), ntaxi + len(d2)
+        else:
+            assert len(ev['delidx']) == 0 and len(ev['delidxalt']) == 0
+        got = sim.read_exparea()
+        for k in exparea_np.ARRAYS:
+            assert np.array_equal(got[k], st[k], equal_nan=True), (step, k)
+        assert (got['create_time'] == 3.0).all()
+    assert st['work'].any() and st['inside'].any() and (nexit > 0 or ntaxi > 0)
+
+
+def band_area(alts, ac, step):
+    """An area everywhere whose top lies between ``ac``'s altitudes before and after ``step`` (a climber): it is
+    inside up to the step before and leaves in that step."""
+    lo, hi = alts[step - 1, ac], alts[step, ac]
+    assert hi > lo
+    return {'BAND': ('BOX', EVERYWHERE, float(0.5 * (lo + hi)), -1e9)}
+
+
+def run_both(ctx, init, p, alts, batches, areas, fmsrt=None, gv=None, bucket=None, bucket_after=None, conds=(), every=1):
+    """exparea.run over ``batches`` with the conditions ``conds`` = [(aircraft, step, command)]; everything read back."""
+    n = len(init['lat'])
+    if bucket is not None:
+        ctx.set_row_bucket(bucket)
+    sim = dress(resident.ResidentSim(init, p, ctx=ctx), fmsrt, None)
+    tab = dict(areas)
+    if gv is not None:
+        tab.update(gv[0])
+    sim.set_areas(tab)
+    if gv is not None:
+        sim.set_geovectors(gv[1], gv[2])
+    cond = None
+    if conds:
+        cond = conditional.Condition(traf_of(init, n), stack=lambda cmd: None)
+        for ac, step, cmd in conds:
+            crossing(cond, alts, ac, step, cmd)
+    area = exparea.Area()
+    area.name, area.active, area.dt = 'BAND', True, p.simdt * every
+    area.sim, area.simt, area.simdt, area.ids = sim, 0.0, p.simdt, ['AC%04d' % k for k in range(n)]
+    sim.set_exparea('BAND', dt=area.dt, every=every, simt=0.0)
+    events, stops, log = [], [], []
+    for q, b in enumerate(batches):
+        if bucket_after is not None and q == bucket_after[0]:
+            ctx.set_row_bucket(bucket_after[1])
+        e, s = exparea.run(sim, area, b, cond=cond, execute=log.append)
+        events += [(x['step'], list(x['delidx']), list(x['delidxalt']), x['deleted_ids'],
+                    {k: np.asarray(v).tolist() for k, v in x['columns'].items()}) for x in e]
+        stops += [(a, list(f), c) for a, f, c in s]
+    return dict(read=sim.read(), area=sim.read_exparea(), events=events, stops=stops, log=log, stats=sim.stats(),
+                table=sim.read_conditions() if conds else None, ids=area.ids,
+                gv=sim.geovector_stats() if gv is not None else None)
+
+
+def assert_same(a, b):
+    for part in ('read', 'area'):
+        for k in a[part]:
+            assert np.array_equal(a[part][k], b[part][k], equal_nan=True), (part, k)
+    assert a['events'] == b['events'] and a['stops'] == b['stops'] and a['log'] == b['log'] and a['ids'] == b['ids']
+    assert a['stats']['steps'] == b['stats']['steps'] and a['gv'] == b['gv']
+    if a['table'] is not None:
+        for k in a['table']:
+            assert a['table'][k].tobytes() == b['table'][k].tobytes(), k
+
+
+def test_one_batch_equals_single_steps(ctx):
+    """step(45) against 45 x step(1), bitwise on state, accumulators and events: 1500 aircraft, CD and MVP every
+    step, FMS on, geovectors every 3rd step, conditions on.  In step 7 a condition fires AND an aircraft exits
+    (another one than the condition's): neither event is lost, the table's lastdif is the same."""
+    init = climbers(1500, 59, 60.0)
+    rt = fms.synthetic_routes(init, seed=59)
+    gv = ({'ALL': ('BOX', EVERYWHERE, 1e9, -1e9)}, [['ALL', None, float(np.median(init['tas'])), None, None, None, None]], 3)
+    p = resident.params(cd_every=1)
+    alts = altitudes(ctx, init, p, 45, rt, gv)
+    m = [k for k in movers(alts) if alts[7, k] > alts[6, k]]
+    assert len(m) >= 2
+    areas = band_area(alts, m[0], 7)
+    conds = [(m[1], 7, 'C7'), (m[1], 20, 'C20')]
+    a = run_both(ctx, init, p, alts, [45], areas, rt, gv, conds=conds)
+    b = run_both(ctx, init, p, alts, [1] * 45, areas, rt, gv, conds=conds)
+    assert_same(a, b)
+    at7 = [e for e in a['events'] if e[0] == 7]
+    assert len(at7) == 1 and 'AC%04d' % m[0] in at7[0][3]                 # the exit of step 7 ...
+    assert [s for s in a['stops'] if s[0] == 7 and s[2] == ['C7']]         # ... and the condition of step 7
+    assert 'C20' in a['log'] and a['stats']['steps'] == 45 and a['stats']['n_conf'] > 0
+    assert len(a['read']['lat']) < 1500 and a['gv']['applies'] > 0
+
+
+@pytest.mark.parametrize('case', ['abort_then_exit', 'exit_then_overflow', 'same_step'])
+def test_stops_and_aborts_together(ctx, case):
+    """K2 row buckets one pair wide overflow at the first CD step they meet.  abort_then_exit: step 0 aborts and
+    re-runs, exits later.  exit_then_overflow: CD every 4th step, an exit of step 2 stops the batch before the
+    overflow of step 4.  same_step: CD every step, so the stop of step 2 sits in a batch whose step 0 aborted and
+    re-ran with its pass (every = 1) counted once.  Each against an undisturbed twin stepped one step at a time: the accumulators
+    bitwise, so no pass ran twice."""
+    init = climbers(1500, 53, 60.0)
+    p = resident.params(cd_every=4 if case == 'exit_then_overflow' else 1)
+    alts = altitudes(ctx, init, p, 12)
+    up = [k for k in movers(alts) if alts[2, k] > alts[1, k]]
+    areas = band_area(alts, up[0], 2)                 # (inside is seeded by the pass of step 1: the first exit is step 2's)
+    twin = run_both(ctx, init, p, alts, [1] * 12, areas)
+    c = _lib.Context(0)
+    try:
+        if case == 'exit_then_overflow':
+            got = run_both(c, init, p, alts, [1, 11], areas, bucket_after=(1, 1))
+        else:
+            got = run_both(c, init, p, alts, [12], areas, bucket=1)
+        assert_same(got, twin)
+    finally:
+        c.close()
+    assert twin['events'] and twin['events'][0][0] == 2 and twin['stats']['n_conf'] > 0
+    assert twin['stats']['steps'] == 12
+    assert np.array_equal(twin['area']['distance2D'] > 0, np.ones(len(twin['ids']), bool))
+
+
+def test_delete_and_create_carry_the_arrays(ctx):
+    init = climbers(600, 7, 30.0)
+    p = resident.params(cd_every=2)
+    sim = resident.ResidentSim(init, p, ctx=ctx)
+    sim.set_areas({'ALL': ('BOX', EVERYWHERE, 1e9, -1e9)})
+    sim.set_exparea('ALL', dt=0.5, every=1, simt=10.0, taxi=False, taxialt=-1e9)
+    assert sim.step(3) == 3
+    before, r = sim.read_exparea(), sim.read()
+    st, d1, d2 = exparea_np.update(dict(distance2D=np.zeros(600), distance3D=np.zeros(600), work=np.zeros(600),
+                                        oldalt=init['alt'], inside=np.zeros(600, bool)), r['gs'], r['vs'], r['alt'],
+                                   r['lat'], r['lon'], None, 0.5, ('BOX', EVERYWHERE, 1e9, -1e9), True, False, -1e9)
+    assert before['inside'].all() and np.array_equal(before['oldalt'], r['alt']) and (before['distance2D'] > 0).all()
+    assert not before['work'].any()                                   # no forces: work stays 0
+    gone = [0, 17, 300, 599]
+    sim.delete(gone)
+    got = sim.read_exparea()
+    for k in before:
+        assert np.array_equal(got[k], np.delete(before[k], gone)), k
+    new = {k: v[:3].copy() for k, v in init.items()}
+    new['alt'] = np.array([1234.0, 2345.0, 3456.0])
+    sim.ctx.sim_exparea_simt(12.5)
+    sim.create(new)
+    got = sim.read_exparea()
+    for k in before:
+        assert np.array_equal(got[k][:596], np.delete(before[k], gone)), k
+    assert list(got['create_time'][596:]) == [12.5] * 3 and list(got['oldalt'][596:]) == [1234.0, 2345.0, 3456.0]
+    assert not got['inside'][596:].any() and not got['distance2D'][596:].any()
+    assert sim.step(2) == 2 and sim.read_exparea()['inside'].all()
+    sim.set_exparea(False)
+    with pytest.raises(_lib.AccelError, match='off'):
+        sim.read_exparea()
+
+
+def test_nothing_is_polled_without_a_stop_and_off_by_default(ctx):
+    init = climbers(600, 7, 30.0)
+    sim = resident.ResidentSim(init, resident.params(cd_every=2), ctx=ctx)
+    ev = sim.exparea_events()
+    assert len(ev['delidx']) == 0 and len(ev['delidxalt']) == 0
+    with pytest.raises(_lib.AccelError, match='off'):
+        sim.read_exparea()
+    sim.set_exparea(None, every=2)                                    # name None, swtaxi and not active: the early return
+    assert sim.step(4) == 4 and not sim.read_exparea()['distance2D'].any()
+
+
+def test_refusals(ctx):
+    init = climbers(600, 7, 30.0)
+    sim = resident.ResidentSim(init, resident.params(), ctx=ctx)
+    sim.set_areas({'ALL': ('BOX', EVERYWHERE, 1e9, -1e9)})
+    with pytest.raises(_lib.AccelError, match='shape 1 of 1'):
+        sim.ctx.sim_set_exparea(True, 1)
+    with pytest.raises(_lib.AccelError, match='shape -2'):
+        sim.ctx.sim_set_exparea(True, -2)
+    with pytest.raises(ValueError, match='no area'):
+        sim.set_exparea('NOPE')
+    with pytest.raises(_lib.AccelError, match='every'):
+        sim.set_exparea('ALL', every=0)
+    sim.set_exparea('ALL')
+    with pytest.raises(_lib.AccelError, match='steps per call'):
+        sim.step(1 << 24)
+    assert sim.step(2) == 2
+
+    def rank(r, c, group):
+        s = resident.ResidentSim(init, resident.params(), ctx=c, rank=r, world=2, group=group)
+        s.set_areas({'ALL': ('BOX', EVERYWHERE, 1e9, -1e9)})
+        with pytest.raises(_lib.AccelError, match='ranks.*not built'):
+            s.set_exparea('ALL')
+        return True
+
+    assert run_ranks(2, rank) == [True, True]
