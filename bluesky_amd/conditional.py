@@ -115,6 +115,29 @@ class Condition:
         self.version += 1
 
 
+def take_stop(sim, cond):
+    """The conditions' half of a stop, before anything is deleted (a delete compacts the device
+    table): poll; if conditions fired, take their commands off ``cond`` in the reference's order
+    (ascending condition index) and refresh ``cond.lastdif`` from the device.  Returns
+    ``(step, fired indices, commands)``, or None when nothing fired."""
+    fired, step = sim.conditions()
+    if len(fired) == 0:
+        return None
+    cmds = [cond.cmd[i] for i in fired]
+    cond.delcondition(fired)
+    cond.lastdif = sim.read_conditions()['lastdif']
+    return step, fired, cmds
+
+
+def execute_stop(sim, cond, cmds, execute):
+    """``execute(cmd)`` for each command of a stop; the table is uploaded again if that changed it."""
+    v = cond.version
+    for c in cmds:
+        execute(c)
+    if cond.version != v:
+        sim.set_conditions(cond)
+
+
 def run(sim, nsteps, cond, execute):
     """Advance ``sim`` (a ``ResidentSim``) by ``nsteps`` with the conditions of ``cond``:
     the table is uploaded, the sim stepped in one batch; when a condition fires the batch
@@ -128,18 +151,10 @@ def run(sim, nsteps, cond, execute):
     events, done = [], 0
     while done < nsteps:
         done += sim.step(nsteps - done)
-        fired, step = sim.conditions()
-        if len(fired) == 0:
-            continue
-        cmds = [cond.cmd[i] for i in fired]
-        cond.delcondition(fired)
-        cond.lastdif = sim.read_conditions()['lastdif']
-        events.append((step, fired, cmds))
-        v = cond.version
-        for c in cmds:
-            execute(c)
-        if cond.version != v:
-            sim.set_conditions(cond)
+        stop = take_stop(sim, cond)
+        if stop is not None:
+            events.append(stop)
+            execute_stop(sim, cond, stop[2], execute)
     if cond.ncond:
         cond.lastdif = sim.read_conditions()['lastdif']
     return events

@@ -2,10 +2,9 @@
 // on the device (math: bsa_cond_math.h).
 //
 // k_cond_update   one update over host-given arrays: lastdif, a fired flag per condition
-// k_cond_count    fired conditions per wave (ballot) -> scan_excl -> k_cond_emit: the fired
-//                 indices in ascending order (np.where's), no atomic cursor
-// k_sim_cond      the resident step's stage: the step's last launch; a firing raises the
-//                 batch's stop (bsa_sim.hip: batch_stopped)
+// k_sim_cond      the resident step's stage: the step's first stopping launch; a firing
+//                 raises the batch's stop (bsa_stop.h; bsa_sim.hip: batch_stopped)
+// The fired indices in ascending order (np.where's): flagged_list (bsa_scan.hip).
 //
 // One lane per condition, gathered loads of the aircraft's values: per condition 24 B of
 // the table read, 8-9 B written, and 8 (standalone: 16) B gathered per aircraft array.
@@ -14,14 +13,14 @@
 
 #include "bsa_cond_math.h"
 #include "bsa_kin_math.h"
-#include "bsa_wave.h"
+#include "bsa_stop.h"
 
 #pragma clang fp contract(off)
 
 namespace bsa {
 
 constexpr int kCondBlock = 256;
-// the flag byte of a condition of the resident table
+// the flag byte of a condition of the resident table; "fired" is flagged_list's mask 1 (a dead row has that bit clear)
 constexpr uint8_t kCondLive = 0, kCondFired = 1, kCondDead = 2;
 
 __global__ __launch_bounds__(kCondBlock) void k_cond_update(int ncond, const int *__restrict__ idx,
@@ -39,27 +38,9 @@ __global__ __launch_bounds__(kCondBlock) void k_cond_update(int ncond, const int
   flag[i] = e.fired ? kCondFired : kCondLive;
 }
 
-// wcnt[w]: the fired conditions of wave w (conditions 64 w .. 64 w + 63); wcnt[nw] = 0, so
-// that the exclusive scan's last word is the total
-__global__ __launch_bounds__(kCondBlock) void k_cond_count(int ncond, const uint8_t *__restrict__ flag,
-                                                             unsigned *__restrict__ wcnt) {
-  const int i = blockIdx.x * kCondBlock + threadIdx.x;
-  const unsigned long long m = __ballot(i < ncond && flag[i] == kCondFired);
-  if ((threadIdx.x & 63) == 0 && i < ncond + 64) wcnt[i >> 6] = i < ncond ? (unsigned)__popcll(m) : 0u;
-}
-__global__ __launch_bounds__(kCondBlock) void k_cond_emit(int ncond, const uint8_t *__restrict__ flag,
-                                                            const unsigned *__restrict__ woff,
-                                                            int *__restrict__ out) {
-  const int i = blockIdx.x * kCondBlock + threadIdx.x;
-  const bool f = i < ncond && flag[i] == kCondFired;
-  const unsigned long long m = __ballot(f);
-  if (f) out[woff[i >> 6] + lane_prefix(m)] = i;  // (woff[w] + rank < total <= ncond)
-}
-
-// Behind the batch's sticky word like every stage -- except behind the stop another block
-// of this very launch raised: word = {sticky (low 32 bits), the raising step's tag (high)},
-// read and raised as one 64-bit word, so every block of the raising launch sees its own tag.
-// Table rows are aircraft indices; the state is in home order (id2h).  traf.cas at
+// Behind the batch's sticky word by stop_runs' rule: no other stage can have raised a stop
+// with this step's tag before this launch, so only another wave of this launch lets it run
+// behind a stop.  Table rows are aircraft indices; the state is in home order (id2h).  traf.cas at
 // cond.update() is vtas2cas(new tas, the altitude before UpdatePosition) (traffic.py:434
 // against :480), untouched by Woosh; alt is what Woosh left
 __global__ __launch_bounds__(kCondBlock) void k_sim_cond(int ncond, const int *__restrict__ idx,
@@ -70,10 +51,9 @@ __global__ __launch_bounds__(kCondBlock) void k_sim_cond(int ncond, const int *_
                                                            const double *__restrict__ alt,
                                                            const double *__restrict__ altprev,
                                                            const double *__restrict__ tas,
-                                                           unsigned long long *__restrict__ word, unsigned tag) {
-  const unsigned mine = stop_word(kStopCond, tag);
-  const unsigned long long w = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if ((unsigned)w != 0u && (unsigned)(w >> 32) != mine) return;
+                                                           unsigned long long *__restrict__ word,
+                                                           unsigned long long *__restrict__ pend, unsigned tag) {
+  if (!stop_runs(word, tag)) return;
   const int i = blockIdx.x * kCondBlock + threadIdx.x;
   bool fired = false;
   if (i < ncond) {
@@ -88,9 +68,7 @@ __global__ __launch_bounds__(kCondBlock) void k_sim_cond(int ncond, const int *_
       fired = e.fired;
     }
   }
-  // the stop: only while the word is 0 (a vector atomic; one lane per wave with a firing)
-  if (__ballot(fired) && (threadIdx.x & 63) == 0)
-    atomicCAS(word, 0ull, ((unsigned long long)mine << 32) | (unsigned long long)kStickyStopped);
+  if (__ballot(fired) && (threadIdx.x & 63) == 0) stop_raise(word, pend, kStopCond, tag);  // one lane per wave
 }
 
 static unsigned cond_grid(int64_t n) { return (unsigned)((n + kCondBlock - 1) / kCondBlock); }
@@ -109,28 +87,6 @@ static int cond_check(Ctx *c, const char *who, int64_t ncond, const int32_t *idx
   return 0;
 }
 
-// the conditions of `flag` == fired in ascending order: wave ballots, one scan, ranks within the wave.
-// scratch: (nw + 1) counts, (nw + 1) offsets, ncond indices, all in `ws` (int / unsigned words)
-static size_t cond_ws_words(int64_t ncond) { return 2 * (size_t)((ncond + 63) / 64 + 1) + (size_t)ncond; }
-static int cond_compact(Ctx *c, int64_t ncond, const uint8_t *flag, unsigned *ws, std::vector<int32_t> *out) {
-  const int nw = (int)((ncond + 63) / 64);
-  unsigned *wcnt = ws, *woff = ws + nw + 1;
-  int *list = (int *)(ws + 2 * (nw + 1));
-  hipLaunchKernelGGL(k_cond_count, dim3(cond_grid(ncond + 64)), dim3(kCondBlock), 0, c->stream, (int)ncond, flag, wcnt);
-  BSA_HIP(c, hipGetLastError());
-  if (scan_excl(c, wcnt, woff, nw + 1)) return -1;
-  hipLaunchKernelGGL(k_cond_emit, dim3(cond_grid(ncond)), dim3(kCondBlock), 0, c->stream, (int)ncond, flag,
-                     (const unsigned *)woff, list);
-  BSA_HIP(c, hipGetLastError());
-  unsigned total = 0;
-  BSA_HIP(c, hipMemcpyAsync(&total, woff + nw, 4, hipMemcpyDeviceToHost, c->stream));
-  BSA_HIP(c, hipStreamSynchronize(c->stream));
-  if (total > (unsigned)ncond) return fail(c, "internal: %u fired of %lld conditions", total, (long long)ncond);
-  out->assign((size_t)total, 0);
-  if (total) BSA_HIP(c, hipMemcpy(out->data(), list, (size_t)total * 4, hipMemcpyDeviceToHost));
-  return 0;
-}
-
 // ---- the resident table: Ctx::cond_* (host mirror of idx / type / target, every row of the device table
 // -- dead ones until the next compaction), lastdif and the flags on the device
 struct CondTable {
@@ -145,7 +101,7 @@ static int cond_push(Ctx *c, const CondTable &t) {
   if (!m) return 0;
   if (!ensure(c, c->cond_idx, m * 4, "condition aircraft") || !ensure(c, c->cond_type, m * 4, "condition types") ||
       !ensure(c, c->cond_tgt, m * 8, "condition targets") || !ensure(c, c->cond_last, m * 8, "condition lastdif") ||
-      !ensure(c, c->cond_flag, m, "condition flags") || !ensure(c, c->cond_ws, cond_ws_words((int64_t)m) * 4, "fired list"))
+      !ensure(c, c->cond_flag, m, "condition flags") || !ensure(c, c->cond_ws, flagged_ws_words((int64_t)m) * 4, "fired list"))
     return -1;
   BSA_HIP(c, hipMemcpyAsync(c->cond_idx.p, t.idx.data(), m * 4, hipMemcpyHostToDevice, c->stream));
   BSA_HIP(c, hipMemcpyAsync(c->cond_type.p, t.type.data(), m * 4, hipMemcpyHostToDevice, c->stream));
@@ -181,18 +137,14 @@ int cond_sim_launch(Ctx *c, unsigned tag) {
                      (const int *)c->cond_type.p, (const double *)c->cond_tgt.p, (double *)c->cond_last.p,
                      (uint8_t *)c->cond_flag.p, (const unsigned *)c->id2h.p, (const double *)c->own[4].p,
                      (const double *)c->s_altprev.p, (const double *)c->s_tas.p,
-                     (unsigned long long *)((char *)c->sim_ctl.p + kSimCtlSticky), tag);
+                     (unsigned long long *)((char *)c->sim_ctl.p + kSimCtlSticky),
+                     (unsigned long long *)((char *)c->sim_ctl.p + kSimCtlPend), tag);
   BSA_HIP(c, hipGetLastError());
   return 0;
 }
 
-void cond_stopped(Ctx *c) {
-  c->cond_pending = true;
-  c->cond_stop_step = c->clk.steps;
-}
-
 void cond_off(Ctx *c) {
-  c->sim_cond = false, c->cond_pending = false;
+  c->sim_cond = false, c->stops[kStopCond].pending = false;
   c->cond_idx_h.clear(), c->cond_type_h.clear(), c->cond_tgt_h.clear();
 }
 
@@ -222,7 +174,7 @@ int cond_note_deleted(Ctx *c, const std::vector<int64_t> &d) {
     u.idx.push_back(t.idx[i]), u.type.push_back(t.type[i]), u.target.push_back(t.target[i]);
     u.lastdif.push_back(t.lastdif[i]);
   }
-  c->cond_pending = false;  // (the fired rows of an unpolled stop are gone with the compaction)
+  c->stops[kStopCond].pending = false;  // (the fired rows of an unpolled stop are gone with the compaction)
   return cond_push(c, u);
 }
 
@@ -246,7 +198,7 @@ int bsa_cond_update(bsa_ctx *cc, int64_t ncond, const int32_t *idx, const int32_
   BSA_HIP(c, hipSetDevice(c->device));
   // stage: idx type (int32) | target lastdif alt cas (fp64) | flags | the compaction's words
   const size_t M = (size_t)ncond, N = (size_t)n, M8 = (M + 7) / 8 * 8;
-  const size_t bytes = 2 * M8 * 4 + 2 * M * 8 + 2 * N * 8 + M8 + bsa::cond_ws_words(ncond) * 4;
+  const size_t bytes = 2 * M8 * 4 + 2 * M * 8 + 2 * N * 8 + M8 + bsa::flagged_ws_words(ncond) * 4;
   if (!bsa::ensure(c, c->cond_stage, bytes, "condition arrays")) return -1;
   char *p = (char *)c->cond_stage.p;
   int *d_idx = (int *)p, *d_type = (int *)(p + M8 * 4);
@@ -265,7 +217,7 @@ int bsa_cond_update(bsa_ctx *cc, int64_t ncond, const int32_t *idx, const int32_
                      (const double *)d_cas, d_flag);
   BSA_HIP(c, hipGetLastError());
   std::vector<int32_t> list;
-  if (bsa::cond_compact(c, ncond, d_flag, d_ws, &list)) return -1;
+  if (bsa::flagged_list(c, ncond, d_flag, nullptr, bsa::kCondFired, d_ws, &list, nullptr)) return -1;
   BSA_HIP(c, hipMemcpy(lastdif, d_last, M * 8, hipMemcpyDeviceToHost));
   std::copy(list.begin(), list.end(), fired);
   *count = (int64_t)list.size();
@@ -289,7 +241,7 @@ int bsa_sim_set_conditions(bsa_ctx *cc, int64_t ncond, const int32_t *idx, const
     t.idx.assign(idx, idx + ncond), t.type.assign(type, type + ncond);
     t.target.assign(target, target + ncond), t.lastdif.assign(lastdif, lastdif + ncond);
   }
-  c->cond_pending = false;
+  c->stops[bsa::kStopCond].pending = false;
   return bsa::cond_push(c, t);
 }
 
@@ -299,12 +251,15 @@ int bsa_sim_cond_poll(bsa_ctx *cc, int64_t cap, int32_t *fired, int64_t *count, 
   if (!c->sim_ready) return bsa::fail(c, "bsa_sim_cond_poll before bsa_sim_init");
   if (!count) return bsa::fail(c, "bsa_sim_cond_poll: NULL count");
   *count = 0;
-  if (step) *step = c->cond_stop_step;
-  if (!c->sim_cond || !c->cond_pending) return 0;
+  bsa::StopSide &stop = c->stops[bsa::kStopCond];
+  if (step) *step = stop.step;
+  if (!c->sim_cond || !stop.pending) return 0;
   BSA_HIP(c, hipSetDevice(c->device));
   const int64_t m = (int64_t)c->cond_idx_h.size();
   std::vector<int32_t> list;
-  if (bsa::cond_compact(c, m, (const uint8_t *)c->cond_flag.p, (unsigned *)c->cond_ws.p, &list)) return -1;
+  if (bsa::flagged_list(c, m, (const uint8_t *)c->cond_flag.p, nullptr, bsa::kCondFired, (unsigned *)c->cond_ws.p, &list,
+                        nullptr))
+    return -1;
   *count = (int64_t)list.size();
   if (*count > cap) return 0;  // (nothing consumed: ask again with room for `count`)
   if (*count > 0 && !fired) return bsa::fail(c, "bsa_sim_cond_poll: NULL buffer");
@@ -312,7 +267,7 @@ int bsa_sim_cond_poll(bsa_ctx *cc, int64_t cap, int32_t *fired, int64_t *count, 
   // delcondition (conditional.py:75-98): the dead rows leave the table, the order of the rest stays
   bsa::CondTable t;
   if (bsa::cond_pull(c, &t)) return -1;
-  c->cond_pending = false;
+  stop.pending = false;
   return bsa::cond_push(c, t);
 }
 

@@ -3,10 +3,9 @@
 //
 // k_exparea_update  one update over host-given arrays: accumulators, oldalt, a flag byte per aircraft
 // k_sim_exparea     the resident step's stage: the step's last launch (after k_sim_cond); an exit or a
-//                   taxi delete raises the batch's stop (bsa_sim.hip: batch_stopped)
-// k_xa_count        flagged aircraft per wave (ballot) -> scan_excl -> k_xa_emit: their indices in
-//                   ascending order (np.where's), no atomic cursor -- as bsa_cond.hip compacts its fired list
+//                   taxi delete raises the batch's stop (bsa_stop.h; bsa_sim.hip: batch_stopped)
 // k_xa_records      the log columns of the exited aircraft the device has
+// The delete lists in ascending index order (np.where's): flagged_list (bsa_scan.hip).
 //
 // One lane per aircraft, one wave per workgroup (a polygon's ring passes through the wave's LDS chunk).
 // Per aircraft and pass: 48 B of state and 33 B of its own arrays read (+ 8 B thrust), 33 B written.
@@ -15,14 +14,14 @@
 
 #include "bsa_area_wave.h"
 #include "bsa_exparea_math.h"
-#include "bsa_wave.h"
+#include "bsa_stop.h"
 #include "bsa_xfer.h"
 
 #pragma clang fp contract(off)
 
 namespace bsa {
 
-constexpr int kXaBlock = 256;  // the compaction's workgroups (the pass itself: kAreaBlock, one wave)
+constexpr int kXaBlock = 256;  // the records' workgroups (the pass itself: kAreaBlock, one wave)
 
 struct XaArgs {
   int rb, re;  // aircraft (home rows) [rb, re) of the arrays
@@ -64,43 +63,14 @@ __global__ __launch_bounds__(kAreaBlock) void k_exparea_update(XaArgs a) {
   xa_row(a, ring);
 }
 
-// Behind the batch's sticky word like every stage -- except behind a stop that carries this very step's tag,
-// whichever stage raised it: k_sim_cond, launched before, may have stopped the batch after this step, and so may
-// another workgroup of this launch; the pass of a stopping step still runs in full.  (An abort carries no tag, a
-// stop of an earlier step an earlier one.)  The word is read once per wave.  pend: the tag of the step whose pass
-// flagged a delete (every writer of a launch stores the same value)
+// Behind the batch's sticky word by stop_runs' rule: k_sim_cond, launched before, may have stopped the batch after
+// this step, and so may another workgroup of this launch; the pass of a stopping step still runs in full
 __global__ __launch_bounds__(kAreaBlock) void k_sim_exparea(XaArgs a, unsigned long long *__restrict__ word,
                                                              unsigned long long *__restrict__ pend, unsigned tag) {
   __shared__ area::Vert ring[kAreaChunk];
-  const unsigned long long w = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)w);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(w >> 32));
-  if (lo != 0u && stop_tag(hi) != tag) return;
+  if (!stop_runs(word, tag)) return;
   const bool flagged = xa_row(a, ring);
-  // the stop: only while the word is 0 (a vector atomic; one lane per wave with a delete)
-  if (__ballot(flagged) && threadIdx.x == 0) {
-    __hip_atomic_store(pend, (unsigned long long)tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    atomicCAS(word, 0ull, ((unsigned long long)stop_word(kStopArea, tag) << 32) | (unsigned long long)kStickyStopped);
-  }
-}
-
-// aircraft i (index order) sits at flag[id2h[i]] (the resident sim's home order), or at flag[i] (id2h NULL).
-// wcnt[w]: the aircraft of wave w with `bit` set; wcnt[nw] = 0, so that the exclusive scan's last word is the total
-__global__ __launch_bounds__(kXaBlock) void k_xa_count(int n, const uint8_t *__restrict__ flag,
-                                                         const unsigned *__restrict__ id2h, unsigned bit,
-                                                         unsigned *__restrict__ wcnt) {
-  const int i = blockIdx.x * kXaBlock + threadIdx.x;
-  const bool f = i < n && (flag[id2h ? id2h[i] : (unsigned)i] & bit) != 0;
-  const unsigned long long m = __ballot(f);
-  if ((threadIdx.x & 63) == 0 && i < n + 64) wcnt[i >> 6] = i < n ? (unsigned)__popcll(m) : 0u;
-}
-__global__ __launch_bounds__(kXaBlock) void k_xa_emit(int n, const uint8_t *__restrict__ flag,
-                                                        const unsigned *__restrict__ id2h, unsigned bit,
-                                                        const unsigned *__restrict__ woff, int *__restrict__ out) {
-  const int i = blockIdx.x * kXaBlock + threadIdx.x;
-  const bool f = i < n && (flag[id2h ? id2h[i] : (unsigned)i] & bit) != 0;
-  const unsigned long long m = __ballot(f);
-  if (f) out[woff[i >> 6] + lane_prefix(m)] = i;  // (woff[w] + rank < total <= n)
+  if (__ballot(flagged) && threadIdx.x == 0) stop_raise(word, pend, kStopArea, tag);  // one lane per wave with a delete
 }
 
 // the reference's log columns the device has, per exited aircraft (exparea::kRecWords fp64 words each)
@@ -130,31 +100,6 @@ static int xa_launch_update(Ctx *c, const XaArgs &a) {
   const unsigned grid = (unsigned)(((int64_t)a.re - a.rb + kAreaBlock - 1) / kAreaBlock);
   hipLaunchKernelGGL(k_exparea_update, dim3(grid), dim3(kAreaBlock), 0, c->stream, a);
   BSA_HIP(c, hipGetLastError());
-  return 0;
-}
-
-// the aircraft with `bit` set in ascending index order: wave ballots, one scan, ranks within the wave.
-// scratch: (nw + 1) counts, (nw + 1) offsets, n indices, all in `ws` (int / unsigned words); the list stays at
-// xa_list(ws, n) on the device
-static size_t xa_ws_words(int64_t n) { return 2 * (size_t)((n + 63) / 64 + 1) + (size_t)n; }
-static int *xa_list(unsigned *ws, int64_t n) { return (int *)(ws + 2 * ((n + 63) / 64 + 1)); }
-static int xa_compact(Ctx *c, int64_t n, const uint8_t *flag, const unsigned *id2h, unsigned bit, unsigned *ws,
-                      std::vector<int32_t> *out) {
-  const int nw = (int)((n + 63) / 64);
-  unsigned *wcnt = ws, *woff = ws + nw + 1;
-  int *list = xa_list(ws, n);
-  hipLaunchKernelGGL(k_xa_count, dim3(xa_grid(n + 64)), dim3(kXaBlock), 0, c->stream, (int)n, flag, id2h, bit, wcnt);
-  BSA_HIP(c, hipGetLastError());
-  if (scan_excl(c, wcnt, woff, nw + 1)) return -1;
-  hipLaunchKernelGGL(k_xa_emit, dim3(xa_grid(n)), dim3(kXaBlock), 0, c->stream, (int)n, flag, id2h, bit,
-                     (const unsigned *)woff, list);
-  BSA_HIP(c, hipGetLastError());
-  unsigned total = 0;
-  BSA_HIP(c, hipMemcpyAsync(&total, woff + nw, 4, hipMemcpyDeviceToHost, c->stream));
-  BSA_HIP(c, hipStreamSynchronize(c->stream));
-  if (total > (unsigned)n) return fail(c, "internal: %u flagged of %lld aircraft", total, (long long)n);
-  out->assign((size_t)total, 0);
-  if (total) BSA_HIP(c, hipMemcpy(out->data(), list, (size_t)total * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -194,28 +139,9 @@ int exparea_sim_launch(Ctx *c, unsigned tag) {
   if (a.re <= a.rb) return 0;
   const unsigned grid = (unsigned)(((int64_t)a.re - a.rb + kAreaBlock - 1) / kAreaBlock);
   hipLaunchKernelGGL(k_sim_exparea, dim3(grid), dim3(kAreaBlock), 0, c->stream, a,
-                     (unsigned long long *)((char *)c->sim_ctl.p + kSimCtlSticky), (unsigned long long *)c->xa_ctl.p, tag);
+                     (unsigned long long *)((char *)c->sim_ctl.p + kSimCtlSticky), (unsigned long long *)((char *)c->sim_ctl.p + kSimCtlPend), tag);
   BSA_HIP(c, hipGetLastError());
   return 0;
-}
-
-int exparea_batch_begin(Ctx *c) {
-  if (c->sim_exparea) BSA_HIP(c, hipMemsetAsync(c->xa_ctl.p, 0, 8, c->stream));
-  return 0;
-}
-
-int exparea_step_flagged(Ctx *c, unsigned tag, bool *flagged) {
-  *flagged = false;
-  if (!c->sim_exparea) return 0;
-  unsigned long long w = 0;
-  BSA_HIP(c, hipMemcpy(&w, c->xa_ctl.p, 8, hipMemcpyDeviceToHost));
-  *flagged = w != 0ull && w == (unsigned long long)tag;
-  return 0;
-}
-
-void exparea_stopped(Ctx *c) {
-  c->xa_pending = true;
-  c->xa_stop_step = c->clk.steps;
 }
 
 int exparea_created(Ctx *c, int64_t n, int64_t m, const double *alt) {
@@ -229,7 +155,7 @@ int exparea_created(Ctx *c, int64_t n, int64_t m, const double *alt) {
 }
 
 void exparea_off(Ctx *c) {
-  c->sim_exparea = false, c->xa_pending = false, c->xa_has_shape = false;
+  c->sim_exparea = false, c->stops[kStopArea].pending = false, c->xa_has_shape = false;
   c->clk.area_ctr = 0;
 }
 
@@ -259,7 +185,7 @@ int bsa_exparea_update(bsa_ctx *cc, int64_t n, const double *gs, const double *v
   BSA_HIP(c, hipSetDevice(c->device));
   // stage: gs vs alt lat lon thrust d2 d3 work oldalt (fp64) | vertices | flags | the compaction's words
   const size_t N = (size_t)n, N8 = (N + 7) / 8 * 8, vb = shape ? (size_t)nvert * 16 : 0;
-  const size_t bytes = 10 * N * 8 + vb + N8 + bsa::xa_ws_words(n) * 4 + 16;
+  const size_t bytes = 10 * N * 8 + vb + N8 + bsa::flagged_ws_words(n) * 4 + 16;
   if (!bsa::ensure(c, c->xa_stage, bytes, "experiment area arrays")) return -1;
   double *d = (double *)c->xa_stage.p;
   bsa::area::Vert *dv = (bsa::area::Vert *)(d + 10 * N);
@@ -285,8 +211,8 @@ int bsa_exparea_update(bsa_ctx *cc, int64_t n, const double *gs, const double *v
   a.verts = dv;
   if (bsa::xa_launch_update(c, a)) return -1;
   std::vector<int32_t> l1, l2;
-  if (bsa::xa_compact(c, n, d_flag, nullptr, bsa::exparea::kExit, d_ws, &l1) ||
-      bsa::xa_compact(c, n, d_flag, nullptr, bsa::exparea::kTaxi, d_ws, &l2))
+  if (bsa::flagged_list(c, n, d_flag, nullptr, bsa::exparea::kExit, d_ws, &l1, nullptr) ||
+      bsa::flagged_list(c, n, d_flag, nullptr, bsa::exparea::kTaxi, d_ws, &l2, nullptr))
     return -1;
   double *out[4] = {distance2D, distance3D, work, oldalt};
   for (int q = 0; q < 4; ++q) BSA_HIP(c, hipMemcpyAsync(out[q], d + (size_t)(6 + q) * N, N * 8, hipMemcpyDeviceToHost, s));
@@ -322,20 +248,18 @@ int bsa_sim_set_exparea(bsa_ctx *cc, int on, int32_t shape_idx, double dt, int64
     bsa::DevBuf *f8[5] = {&c->s_xd2, &c->s_xd3, &c->s_xwork, &c->s_xoldalt, &c->s_xctime};
     for (bsa::DevBuf *b : f8)
       if (!bsa::ensure(c, *b, n * 8, "experiment area arrays")) return -1;
-    if (!bsa::ensure(c, c->s_xflag, n, "experiment area flags") || !bsa::ensure(c, c->xa_ctl, 8, "experiment area word"))
-      return -1;
+    if (!bsa::ensure(c, c->s_xflag, n, "experiment area flags")) return -1;
     hipStream_t s = c->stream;
     BSA_HIP(c, hipMemsetAsync(c->s_xd2.p, 0, n * 8, s));
     BSA_HIP(c, hipMemsetAsync(c->s_xd3.p, 0, n * 8, s));
     BSA_HIP(c, hipMemsetAsync(c->s_xwork.p, 0, n * 8, s));
     BSA_HIP(c, hipMemsetAsync(c->s_xflag.p, 0, n, s));  // inside all False: seen inside once before an exit (area.py:100)
-    BSA_HIP(c, hipMemsetAsync(c->xa_ctl.p, 0, 8, s));
     BSA_HIP(c, hipMemcpyAsync(c->s_xoldalt.p, c->own[4].p, n * 8, hipMemcpyDeviceToDevice, s));
     std::vector<double> t(n, simt);
     BSA_HIP(c, hipMemcpyAsync(c->s_xctime.p, t.data(), n * 8, hipMemcpyHostToDevice, s));
     BSA_HIP(c, hipStreamSynchronize(s));
     c->clk.area_ctr = 0;
-    c->xa_pending = false;
+    c->stops[bsa::kStopArea].pending = false;
     c->xa_now = simt;
   }
   c->xa_has_shape = shape_idx >= 0;
@@ -363,18 +287,20 @@ int bsa_sim_exparea_poll(bsa_ctx *cc, int64_t cap, int32_t *delidx, int64_t *nde
   if (!c->sim_ready) return bsa::fail(c, "bsa_sim_exparea_poll before bsa_sim_init");
   if (!ndel || !ndelalt) return bsa::fail(c, "bsa_sim_exparea_poll: NULL count");
   *ndel = *ndelalt = 0;
-  if (step) *step = c->xa_stop_step;
-  if (!c->sim_exparea || !c->xa_pending) return 0;
+  bsa::StopSide &stop = c->stops[bsa::kStopArea];
+  if (step) *step = stop.step;
+  if (!c->sim_exparea || !stop.pending) return 0;
   BSA_HIP(c, hipSetDevice(c->device));
   const int64_t n = c->n;
-  if (!bsa::ensure(c, c->xa_ws, bsa::xa_ws_words(n) * 4, "delete lists")) return -1;
+  if (!bsa::ensure(c, c->xa_ws, bsa::flagged_ws_words(n) * 4, "delete lists")) return -1;
   const uint8_t *flag = (const uint8_t *)c->s_xflag.p;
   const unsigned *id2h = (const unsigned *)c->id2h.p;
   unsigned *ws = (unsigned *)c->xa_ws.p;
   std::vector<int32_t> l1, l2;
+  const int *exits = nullptr;
   // (the taxi list first: the exit list then stays in the scratch for the records' gather)
-  if (bsa::xa_compact(c, n, flag, id2h, bsa::exparea::kTaxi, ws, &l2) ||
-      bsa::xa_compact(c, n, flag, id2h, bsa::exparea::kExit, ws, &l1))
+  if (bsa::flagged_list(c, n, flag, id2h, bsa::exparea::kTaxi, ws, &l2, nullptr) ||
+      bsa::flagged_list(c, n, flag, id2h, bsa::exparea::kExit, ws, &l1, &exits))
     return -1;
   *ndel = (int64_t)l1.size();
   *ndelalt = (int64_t)l2.size();
@@ -392,14 +318,14 @@ int bsa_sim_exparea_poll(bsa_ctx *cc, int64_t cap, int32_t *delidx, int64_t *nde
                           (const double *)c->s_aalt.p,   (const double *)c->s_atas.p,  (const double *)c->s_avs.p,
                           (const double *)c->s_atrk.p};
     hipLaunchKernelGGL(bsa::k_xa_records, dim3(bsa::xa_grid((int64_t)l1.size())), dim3(bsa::kXaBlock), 0, c->stream,
-                       (int)l1.size(), (const int *)bsa::xa_list(ws, n), id2h, s, (double *)c->xa_rec.p);
+                       (int)l1.size(), exits, id2h, s, (double *)c->xa_rec.p);
     BSA_HIP(c, hipGetLastError());
     BSA_HIP(c, hipMemcpyAsync(records, c->xa_rec.p, rb, hipMemcpyDeviceToHost, c->stream));
     BSA_HIP(c, hipStreamSynchronize(c->stream));
   }
   std::copy(l1.begin(), l1.end(), delidx);
   std::copy(l2.begin(), l2.end(), delidxalt);
-  c->xa_pending = false;
+  stop.pending = false;
   return 0;
 }
 

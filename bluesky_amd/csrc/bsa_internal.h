@@ -120,20 +120,38 @@ constexpr unsigned long long kGateNonfinite = 1, kGateOverflow = 2, kGateBkOverf
 // gate[2]: the HK prediction of this CD call (some rank's records left kHkPredict of their budgets)
 constexpr int kGateWords = 3;
 constexpr int kSimCtlSticky = 24, kSimCtlSteps = 32, kSimCtlDemand = 40, kSimCtlKdemand = 48, kSimCtlStale = 56;
-// (sim_ctl bytes; [24, 64) are zeroed per batch and read back after it)
+constexpr int kSimCtlPend = 64;  // one u64 per StopStage; [24, kSimCtlEnd) are zeroed per batch and read back after it
 // The sticky word's values: 0 the batch runs; kStickyAborted the step that raised it did not happen (the state is
 // its start: grow, re-run); kStickyStopped the step that raised it is complete and the host has to act before the
 // next one (nothing to re-run).  A stop is raised only while the word is 0, by a stage behind the step's steps_done
-// increment, together with [28, 32): stop_word(stage, tag) -- which stage raised it (StopStage; batch_stopped
-// hands the stop to that stage's host side) and the raising step's tag (its number in the batch + 1, < 2^24).
-// That word, not the sticky value, tells the host the batch stopped: a detect of a later, no-op step may still
-// overflow and store kStickyAborted over the stop
+// increment, together with [28, 32): stop_word(stage, tag) -- which stage raised it first and the raising step's
+// tag (its number in the batch + 1, < 2^24).  That word, not the sticky value, tells the host the batch stopped: a
+// detect of a later, no-op step may still overflow and store kStickyAborted over the stop.  Every stopping stage
+// with something for the host stores its step's tag into its pending word (kSimCtlPend + 8 stage), raiser or not:
+// batch_stopped hands the stop to each stage whose word holds the stop's tag (bsa_stop.h)
 constexpr unsigned kStickyAborted = 1u, kStickyStopped = 2u;
 enum StopStage : unsigned { kStopNone = 0, kStopCond = 1, kStopArea = 2, kStopCount };  // (conditions; the experiment area)
 constexpr unsigned kStopTagMax = (1u << 24) - 1;
 constexpr unsigned stop_word(unsigned stage, unsigned tag) { return (stage << 24) | tag; }
 constexpr unsigned stop_stage(unsigned w) { return w >> 24; }
 constexpr unsigned stop_tag(unsigned w) { return w & kStopTagMax; }
+constexpr int kSimCtlEnd = kSimCtlPend + 8 * (int)kStopCount;
+// sim_ctl's per-batch words as batch_end hands them back
+struct BatchCtl {
+  unsigned sticky, stop;  // kSticky*; stop_word(stage, tag) of the first raiser, 0: no stop
+  unsigned long long steps_done, bk_demand, key_demand, stale, pend[kStopCount];
+};
+static_assert(offsetof(BatchCtl, stop) == 4 && offsetof(BatchCtl, steps_done) == kSimCtlSteps - kSimCtlSticky &&
+                  offsetof(BatchCtl, bk_demand) == kSimCtlDemand - kSimCtlSticky &&
+                  offsetof(BatchCtl, key_demand) == kSimCtlKdemand - kSimCtlSticky &&
+                  offsetof(BatchCtl, stale) == kSimCtlStale - kSimCtlSticky &&
+                  offsetof(BatchCtl, pend) == kSimCtlPend - kSimCtlSticky && sizeof(BatchCtl) == kSimCtlEnd - kSimCtlSticky,
+              "BatchCtl mirrors sim_ctl from kSimCtlSticky on");
+// a stopping stage's host side: a stop nobody polled yet, and its step count
+struct StopSide {
+  bool pending = false;
+  int64_t step = 0;
+};
 constexpr int kHkRing = 16;  // HK: published predictions (pinned host words), slot m % kHkRing
 constexpr unsigned long long kNanBits = 0x7ff8000000000000ull;  // (a quiet NaN)
 
@@ -394,9 +412,11 @@ struct Ctx {
   DevBuf rownf;  // rows of their own (not columns): per row (index order), its position / velocity is not finite
   unsigned long long nf_counter = 0, nf_prep_epoch = 0;  // epochs (K0b: a new one; K4' prep: the next detect's)
   DevBuf sim_ctl;  // [0,24) gate {abort / non-finite, P, HK prediction}; [24,28) sticky abort / stop; [28,32) the
-                   // stopping step's tag; [32,40) steps
+                   // stopping stage and step's tag; [32,40) steps
                    // done; [40,48) resopairs demand on a bookkeeping overflow; [48,56) pair-key
-                   // block demand (several ranks); [56,64) an HK-kept list went stale in the batch
+                   // block demand (several ranks); [56,64) an HK-kept list went stale in the batch;
+                   // [64, kSimCtlEnd) the stopping stages' pending words (BatchCtl)
+  StopSide stops[kStopCount];  // the stopping stages' unpolled stops (stage_stopped; the polls consume them)
   // ASAS bookkeeping (bsa_asas.hip, resume_nav = 1): resopairs CSR over own
   // rows (+ next), per-row kept counts, LoS row pointers of the last call,
   // previous call's conflict / LoS CSR (one rank), stats
@@ -486,26 +506,23 @@ struct Ctx {
   // Conditional commands (bsa_cond.hip).  cond_stage: bsa_cond_update's arrays.  In the resident
   // step (bsa_sim_set_conditions): the table by aircraft index -- idx / type / target (host mirrors cond_*_h of
   // every device row), lastdif and a flag byte per row (live / fired at the last stop / dead) on the device only,
-  // cond_ws the ordered compaction's words.  cond_pending: a stop nobody polled yet; cond_stop_step: its step count.
-  // steps_last / steps_total: what bsa_sim_steps_run reports
+  // cond_ws the ordered compaction's words (flagged_list).  steps_last / steps_total: what bsa_sim_steps_run reports
   DevBuf cond_stage, cond_idx, cond_type, cond_tgt, cond_last, cond_flag, cond_ws;
   std::vector<int32_t> cond_idx_h, cond_type_h;
   std::vector<double> cond_tgt_h;
-  bool sim_cond = false, cond_pending = false;
-  int64_t cond_stop_step = 0;
+  bool sim_cond = false;
   int64_t steps_last = 0, batch_steps0 = 0;  // (the step count at the running batch's begin: StepPlan::cond_tag)
 
   // The experiment area (bsa_exparea.hip).  xa_stage: bsa_exparea_update's arrays.  In the resident
   // step (bsa_sim_set_exparea): per aircraft (kSimArrays) the accumulators distance2D / distance3D / work, oldalt,
   // create_time and a flag byte (inside / exit pending / taxi delete pending); xa_shape: the area (a copy of its
   // row of area_tab) or none (name None: everything is outside); xa_every: the cadence, in steps of clk.area_ctr;
-  // xa_dt: the plugin's nominal dt; xa_ctl: one u64, the tag of the batch's step whose pass flagged a delete;
-  // xa_ws / xa_rec: the ordered compaction's words and the poll's records.  xa_pending: a stop with deletes nobody
-  // polled yet; xa_stop_step: its step count; xa_now: the simt new aircraft are created at (bsa_sim_exparea_simt)
-  DevBuf xa_stage, s_xd2, s_xd3, s_xwork, s_xoldalt, s_xctime, s_xflag, xa_ctl, xa_ws, xa_rec;
-  bool sim_exparea = false, xa_has_shape = false, xa_active = false, xa_swtaxi = true, xa_pending = false;
+  // xa_dt: the plugin's nominal dt; xa_ws / xa_rec: the ordered compaction's words (flagged_list) and the poll's
+  // records; xa_now: the simt new aircraft are created at (bsa_sim_exparea_simt)
+  DevBuf xa_stage, s_xd2, s_xd3, s_xwork, s_xoldalt, s_xctime, s_xflag, xa_ws, xa_rec;
+  bool sim_exparea = false, xa_has_shape = false, xa_active = false, xa_swtaxi = true;
   bsa_area_shape xa_shape{};
-  int64_t xa_every = 1, xa_stop_step = 0;
+  int64_t xa_every = 1;
   double xa_dt = 0.5, xa_swtaxialt = 0.0, xa_now = 0.0;
 
   // standalone geo matrices (bsa_geo.hip)
@@ -725,25 +742,22 @@ int turb_sim_launch(Ctx *c, int64_t rb, int64_t re, const unsigned *sticky, cons
                     double *lon, double *alt);
 void turb_off(Ctx *c);
 
-// Conditional commands of the step (bsa_cond.hip): k_sim_cond, the step's last launch; tag: the step's number in
-// its batch + 1 (what a stop it raises carries).  cond_note_deleted: Condition.delac for the (sorted) aircraft of
-// a bsa_sim_delete, before anything moves.  cond_off forgets the table
+// The stopping stages (StopStage; the device side: bsa_stop.h).  stage_stopped: batch_stopped found the stage's
+// pending word at the stop's tag (the clocks are already those of the stop); the stage's poll consumes it
+void stage_stopped(Ctx *c, StopStage s);
+// Conditional commands of the step (bsa_cond.hip): k_sim_cond, the step's first stopping launch; tag: the step's
+// number in its batch + 1 (what a stop it raises carries).  cond_note_deleted: Condition.delac for the (sorted)
+// aircraft of a bsa_sim_delete, before anything moves.  cond_off forgets the table
 int cond_sim_launch(Ctx *c, unsigned tag);
-void cond_stopped(Ctx *c);  // batch_stopped: the stop was this stage's (the clocks are already those of the stop)
 int cond_note_deleted(Ctx *c, const std::vector<int64_t> &d);
 void cond_off(Ctx *c);
 
 // The experiment area of the step (bsa_exparea.hip): k_sim_exparea, the step's last launch (after
-// k_sim_cond) in the steps whose StepPlan::area_pass is set; tag as for cond_sim_launch.  exparea_batch_begin
-// zeroes the batch's "deletes pending" word (stream-ordered); exparea_step_flagged: did the pass of the batch's
-// step `tag` leave deletes pending (batch_stopped, after the batch's synchronisation)?  exparea_stopped: that
-// step's deletes wait for bsa_sim_exparea_poll.  exparea_passes_at: does the step at clk.area_ctr run the pass?
-// exparea_created: Area.create for the m aircraft bsa_sim_create appended after the first n (alt: theirs, host)
+// k_sim_cond) in the steps whose StepPlan::area_pass is set; tag as for cond_sim_launch.  exparea_passes_at: does
+// the step at clk.area_ctr run the pass?  exparea_created: Area.create for the m aircraft bsa_sim_create appended
+// after the first n (alt: theirs, host)
 bool exparea_passes_at(const Ctx *c);
 int exparea_sim_launch(Ctx *c, unsigned tag);
-int exparea_batch_begin(Ctx *c);
-int exparea_step_flagged(Ctx *c, unsigned tag, bool *flagged);
-void exparea_stopped(Ctx *c);
 int exparea_created(Ctx *c, int64_t n, int64_t m, const double *alt);
 void exparea_off(Ctx *c);
 
@@ -839,6 +853,12 @@ bool ensure_col_prep(Ctx *c, int64_t n, bool rec);
 
 // exclusive prefix sum of n words, one launch (bsa_scan.hip)
 int scan_excl(Ctx *c, const unsigned *in, unsigned *out, int n);
+// The i in [0, n) with (flag[id2h ? id2h[i] : i] & mask) != 0 in ascending order (np.where's): wave ballots, one
+// scan_excl, ranks within the wave, no atomic cursor.  ws: flagged_ws_words(n) words of device scratch; the list
+// also stays in it, at *dev_list (or NULL).  Synchronises the stream
+size_t flagged_ws_words(int64_t n);
+int flagged_list(Ctx *c, int64_t n, const uint8_t *flag, const unsigned *id2h, unsigned mask, unsigned *ws,
+                 std::vector<int32_t> *out, const int **dev_list);
 // spatial (home) order of the n aircraft in own[] (bsa_k0.hip): home -> aircraft index
 int home_order(Ctx *c, double tla, std::vector<unsigned> &h2id);
 // the last detect's pair lists and per-row outputs in aircraft-index terms

@@ -1,5 +1,7 @@
 // Exclusive prefix sum of unsigned words in one launch (scan_excl,
 // bsa_internal.h): K2's row offsets at bucket width 0, the halo plan's lists.
+// On top of it the ordered index list of a flag array (flagged_list): the
+// stopping stages' fired conditions and delete lists.
 #include "bsa_internal.h"
 #include "bsa_wave.h"
 
@@ -118,6 +120,53 @@ int scan_excl(Ctx *c, const unsigned *in, unsigned *out, int n) {
                        c->scan_tickets, ws + 1, epoch);
   BSA_HIP(c, hipGetLastError());
   c->scan_tickets += tiles;
+  return 0;
+}
+
+// ------------------------------------------------------------------ ordered index list
+constexpr int kFlagBlock = 256;
+__device__ __forceinline__ bool flag_set(int i, int n, const uint8_t *flag, const unsigned *id2h, unsigned mask) {
+  return i < n && (flag[id2h ? id2h[i] : (unsigned)i] & mask) != 0;
+}
+// wcnt[w]: the flagged of wave w (i in 64 w .. 64 w + 63); wcnt[nw] = 0, so that the exclusive scan's last word is
+// the total
+__global__ __launch_bounds__(kFlagBlock) void k_flag_count(int n, const uint8_t *__restrict__ flag,
+                                                             const unsigned *__restrict__ id2h, unsigned mask,
+                                                             unsigned *__restrict__ wcnt) {
+  const int i = blockIdx.x * kFlagBlock + threadIdx.x;
+  const unsigned long long m = __ballot(flag_set(i, n, flag, id2h, mask));
+  if ((threadIdx.x & 63) == 0 && i < n + 64) wcnt[i >> 6] = i < n ? (unsigned)__popcll(m) : 0u;
+}
+__global__ __launch_bounds__(kFlagBlock) void k_flag_emit(int n, const uint8_t *__restrict__ flag,
+                                                            const unsigned *__restrict__ id2h, unsigned mask,
+                                                            const unsigned *__restrict__ woff, int *__restrict__ out) {
+  const int i = blockIdx.x * kFlagBlock + threadIdx.x;
+  const bool f = flag_set(i, n, flag, id2h, mask);
+  const unsigned long long m = __ballot(f);
+  if (f) out[woff[i >> 6] + lane_prefix(m)] = i;  // (woff[w] + rank < total <= n)
+}
+
+// ws: (nw + 1) counts, (nw + 1) offsets, n indices (int / unsigned words)
+size_t flagged_ws_words(int64_t n) { return 2 * (size_t)((n + 63) / 64 + 1) + (size_t)n; }
+int flagged_list(Ctx *c, int64_t n, const uint8_t *flag, const unsigned *id2h, unsigned mask, unsigned *ws,
+                 std::vector<int32_t> *out, const int **dev_list) {
+  const int nw = (int)((n + 63) / 64);
+  unsigned *wcnt = ws, *woff = ws + nw + 1;
+  int *list = (int *)(ws + 2 * (nw + 1));
+  if (dev_list) *dev_list = list;
+  const auto grid = [](int64_t m) { return dim3((unsigned)((m + kFlagBlock - 1) / kFlagBlock)); };
+  hipLaunchKernelGGL(k_flag_count, grid(n + 64), dim3(kFlagBlock), 0, c->stream, (int)n, flag, id2h, mask, wcnt);
+  BSA_HIP(c, hipGetLastError());
+  if (scan_excl(c, wcnt, woff, nw + 1)) return -1;
+  hipLaunchKernelGGL(k_flag_emit, grid(n), dim3(kFlagBlock), 0, c->stream, (int)n, flag, id2h, mask,
+                     (const unsigned *)woff, list);
+  BSA_HIP(c, hipGetLastError());
+  unsigned total = 0;
+  BSA_HIP(c, hipMemcpyAsync(&total, woff + nw, 4, hipMemcpyDeviceToHost, c->stream));
+  BSA_HIP(c, hipStreamSynchronize(c->stream));
+  if (total > (unsigned)n) return fail(c, "internal: %u flagged of %lld", total, (long long)n);
+  out->assign((size_t)total, 0);
+  if (total) BSA_HIP(c, hipMemcpy(out->data(), list, (size_t)total * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -211,7 +211,7 @@ void sim_release(Ctx *c) {
   // not per aircraft: staging, control words, tables, the FMS undo set, K2 + K4' double buffers
   DevBuf *rest[] = {&c->red, &c->g_send, &c->g_recv, &c->pg_send, &c->pg_recv, &c->sim_ctl, &c->s_ptab, &c->s_ftab,
                     &c->f_const, &c->s_fmsrows, &c->s_fmsur, &c->s_fmsuf, &c->s_fmsui, &c->gv_tab, &c->gv_shapes, &c->gv_undo,
-                    &c->gv_cnt, &c->xfer_stage, &c->lbyidx, &c->xa_ctl, &c->xa_ws, &c->xa_rec,
+                    &c->gv_cnt, &c->xfer_stage, &c->lbyidx, &c->xa_ws, &c->xa_rec,
                     &c->fetch_stage, &c->tpr_snap, &c->tpr_ctl, &c->nx_alt, &c->nx_vs, &c->nx_gse, &c->nx_gsn};
   for (auto *b : rest) release(*b);
   bk_release(c);
@@ -382,27 +382,26 @@ struct BatchBase {
 static int batch_begin(Ctx *c, bool kin, BatchBase *b) {
   *b = BatchBase{kin, c->clk, c->sim_gs_derivable};
   c->batch_steps0 = c->clk.steps;
-  BSA_HIP(c, hipMemsetAsync((char *)c->sim_ctl.p + kSimCtlSticky, 0, 40, c->stream));  // sticky, steps_done, demands, stale
-  return exparea_batch_begin(c);  // (its "deletes pending" word; nothing while the stage is off)
+  BSA_HIP(c, hipMemsetAsync((char *)c->sim_ctl.p + kSimCtlSticky, 0, sizeof(BatchCtl), c->stream));
+  return 0;
 }
-// the batch's only host synchronisation: ctl = sim_ctl words {sticky, steps
-// done, resopairs demand, key-block demand, stale}
-static int batch_end(Ctx *c, unsigned long long ctl[5]) {
-  BSA_HIP(c, hipMemcpyAsync(ctl, (char *)c->sim_ctl.p + kSimCtlSticky, 40, hipMemcpyDeviceToHost, c->stream));
+// the batch's only host synchronisation
+static int batch_end(Ctx *c, BatchCtl *ctl) {
+  BSA_HIP(c, hipMemcpyAsync(ctl, (char *)c->sim_ctl.p + kSimCtlSticky, sizeof(BatchCtl), hipMemcpyDeviceToHost, c->stream));
   BSA_HIP(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 
 // An aborted batch: the state is that of the aborted step's start (step
-// base.clk.steps + ctl[1]).  The gate is all-reduced, so every rank aborted at the
+// base.clk.steps + ctl.steps_done).  The gate is all-reduced, so every rank aborted at the
 // same step; each rank grows only what overflowed on IT (another rank's
 // overflow re-runs the step here with unchanged buffers) and all ranks re-run it
-static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long long *ctl) {
+static int batch_rollback(Ctx *c, const BatchBase &base, const BatchCtl &ctl) {
   // the re-run rebuilds the candidate list and the tile-pair list / halo plan (every rank aborted alike) and zeroes
   // every per-detect buffer (an aborted K2 wrote no inconf / tcpamax); an aborted K4' prepared nothing, and the HK
   // decisions of the aborted steps never took effect
   invalidate(c, Change::BatchAborted);
-  const int64_t done = (int64_t)ctl[1];
+  const int64_t done = (int64_t)ctl.steps_done;
   // the clocks of the completed steps, replayed from the batch base with each step's own plan (a CD call alone
   // completes no step: its count goes back to the base, the re-run counts it)
   c->clk = base.clk;
@@ -432,15 +431,15 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long lon
     return fail(c, "internal error: the halo exchange and the tile-pair cull disagree (rank %d)", c->rank);
   // several ranks: every rank takes part in the capacity agreement (collective)
   if (c->halo_mode == 1 && halo_grow(c)) return -1;
-  if (ctl[2] > 0)  // this rank's resopairs outgrew their buffer
-    c->bk_cap = std::max(2 * c->bk_cap, ctl[2] + ctl[2] / 4 + 1024);
+  if (ctl.bk_demand > 0)  // this rank's resopairs outgrew their buffer
+    c->bk_cap = std::max(2 * c->bk_cap, ctl.bk_demand + ctl.bk_demand / 4 + 1024);
   // pair keys outgrew their all-gather block on some rank: the block width is
   // part of the all-gather's layout, so every rank grows to the same width
   // (max-all-reduced demand; collective, every rank aborted at this step)
   // (with HK's stale flag: the device-decided stretch after a stale abort must
   // be the same on every rank -- the kept and the rebuilt plans issue
   // different collectives)
-  double agree[2] = {(double)ctl[3], ctl[4] ? 1.0 : 0.0};
+  double agree[2] = {(double)ctl.key_demand, ctl.stale ? 1.0 : 0.0};
   if (comm_multi(c) && comm_allreduce_host(c, agree, 2, true)) return -1;
   const double kdem = agree[0];
   if (agree[1] > 0.0) {  // an HK-kept list no longer covered some rank's records: device-decided for a while
@@ -452,7 +451,7 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long lon
     c->bk_kw = std::max<unsigned long long>(2 * c->bk_kw, (unsigned long long)kdem + (unsigned long long)kdem / 4 + 1024);
   if (detect_env().hk_trace)  // (diagnostics)
     fprintf(stderr, "[bsa hk] rank %d abort at step %lld: stale %d k2 %llu fuse %llu halo %llu/%llu\n", c->rank,
-            (long long)c->clk.steps, ctl[4] ? 1 : 0, h.k2_demand, h.fuse_ovf, h.halo_ovf, h.halo_miss);
+            (long long)c->clk.steps, ctl.stale ? 1 : 0, h.k2_demand, h.fuse_ovf, h.halo_ovf, h.halo_miss);
   if (h.k2_demand) grow_k2_bucket(c, h.k2_demand);  // a K2 row bucket was full on this rank
   if (h.fuse_ovf) {  // fused K1b out of flush records: the re-run's detect unfused
     c->fuse_skip = true;
@@ -475,28 +474,24 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const unsigned long lon
 // undo sets are NOT put back: the step after the stop never executed, its launches returned before they saved
 // anything, so the sets hold an earlier, completed tick's start.  Host state step_enqueue moved for the no-op
 // steps: the clocks are replayed over the completed steps as batch_rollback does; prep.keep / drop and the HK
-// decisions go with Change::BatchStopped; sim_gs_derivable / sim_gathered are those after a completed K4'
-static int batch_stopped(Ctx *c, const BatchBase &base, const unsigned long long *ctl) {
-  const unsigned sw = (unsigned)(ctl[0] >> 32);
-  const int64_t done = (int64_t)ctl[1], tag = (int64_t)stop_tag(sw);
-  if (done < 1 || tag != done || stop_stage(sw) == kStopNone || stop_stage(sw) >= kStopCount)
-    return fail(c, "internal error: batch stopped by stage %u in step %lld with %lld steps done", stop_stage(sw),
-                (long long)tag, (long long)done);
+// decisions go with Change::BatchStopped; sim_gs_derivable / sim_gathered are those after a completed K4'.
+// Every stopping stage with something for the host stored the step's tag into its pending word, the raiser too:
+// each of them is told (stage_stopped), and its poll delivers
+void stage_stopped(Ctx *c, StopStage s) { c->stops[s] = StopSide{true, c->clk.steps}; }
+
+static int batch_stopped(Ctx *c, const BatchBase &base, const BatchCtl &ctl) {
+  const unsigned stage = stop_stage(ctl.stop);
+  const int64_t done = (int64_t)ctl.steps_done, tag = (int64_t)stop_tag(ctl.stop);
+  if (done < 1 || tag != done || stage == kStopNone || stage >= kStopCount || ctl.pend[stage] != (unsigned long long)tag)
+    return fail(c, "internal error: batch stopped by stage %u in step %lld with %lld steps done", stage, (long long)tag,
+                (long long)done);
   invalidate(c, Change::BatchStopped);
   c->clk = base.clk;
   for (int64_t k = 0; k < done; ++k) step_advance(c, step_decide(c, false));
   c->sim_gs_derivable = c->simp.winddim == 0;
   c->sim_gathered = c->nranks == 1;
-  switch (stop_stage(sw)) {  // the raising stage's host side
-    case kStopCond: cond_stopped(c); break;
-    case kStopArea: break;  // (asked below, like after any other stage's stop)
-  }
-  // the experiment area's pass of the stopping step ran in full whichever stage raised the stop: did it leave deletes?
-  bool flagged = false;
-  if (exparea_step_flagged(c, (unsigned)tag, &flagged)) return -1;
-  if (flagged) exparea_stopped(c);
-  else if (stop_stage(sw) == kStopArea)
-    return fail(c, "internal error: the experiment area stopped the batch in step %lld without a delete", (long long)tag);
+  for (unsigned s = kStopNone + 1; s < kStopCount; ++s)
+    if (ctl.pend[s] == (unsigned long long)tag) stage_stopped(c, (StopStage)s);
   return 0;
 }
 
@@ -689,8 +684,8 @@ int bsa_sim_init(bsa_ctx *cc, int64_t n, const bsa_sim_state *s, const bsa_sim_p
       return -1;
   }
   if (up.run()) return -1;
-  if (!bsa::ensure(c, c->sim_ctl, 64, "sim control words")) return -1;
-  BSA_HIP(c, hipMemsetAsync(c->sim_ctl.p, 0, 64, c->stream));
+  if (!bsa::ensure(c, c->sim_ctl, bsa::kSimCtlEnd, "sim control words")) return -1;
+  BSA_HIP(c, hipMemsetAsync(c->sim_ctl.p, 0, bsa::kSimCtlEnd, c->stream));
   BSA_HIP(c, hipStreamSynchronize(c->stream));
   c->simp = *p;
   c->bk_ready = false;  // empty resopairs / previous pair sets
@@ -743,16 +738,16 @@ int bsa_sim_step(bsa_ctx *cc, int nsteps) {
     if (bsa::batch_begin(c, true, &base)) return -1;
     while (c->clk.steps < target)
       if (bsa::step_enqueue(c, bsa::step_decide(c, attempt > 0 && c->clk.steps == base.clk.steps))) return -1;
-    unsigned long long ctl[5] = {0, 0, 0, 0, 0};
-    if (bsa::batch_end(c, ctl)) return -1;  // did every step complete?
+    bsa::BatchCtl ctl{};
+    if (bsa::batch_end(c, &ctl)) return -1;  // did every step complete?
 #ifdef BSA_PF_TRACE
     if (bsa::pf_trace_dump(c, 0, 0)) return -1;  // (diagnostic builds: the batch's last prefilter)
 #endif
-    if ((ctl[0] >> 32) != 0) {  // stopped: the host has to act before the next step (bsa_sim_steps_run tells how far it got)
+    if (ctl.stop != 0) {  // stopped: the host has to act before the next step (bsa_sim_steps_run tells how far it got)
       if (bsa::batch_stopped(c, base, ctl)) return -1;
       break;
     }
-    if ((unsigned)ctl[0] == 0) break;
+    if (ctl.sticky == 0) break;
     if (bsa::batch_rollback(c, base, ctl)) return -1;
   }
   c->steps_last = c->clk.steps - start;
@@ -1071,9 +1066,9 @@ int bsa_sim_cd(bsa_ctx *cc) {
     bsa::CdOut cd;
     if (bsa::batch_begin(c, false, &base) || bsa::sim_cd(c, false, false, &cd)) return -1;
     c->clk.cd_calls++;  // (a CD call outside a step: step_advance counts a step's)
-    unsigned long long ctl[5] = {0, 0, 0, 0, 0};
-    if (bsa::batch_end(c, ctl)) return -1;
-    if ((unsigned)ctl[0] == 0) break;
+    bsa::BatchCtl ctl{};
+    if (bsa::batch_end(c, &ctl)) return -1;
+    if (ctl.sticky == 0) break;
     // aborted: nothing persistent was written (the state did not move, so
     // the replicas stay consistent); grow and re-run
     if (bsa::batch_rollback(c, base, ctl)) return -1;

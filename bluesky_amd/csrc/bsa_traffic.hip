@@ -325,7 +325,7 @@ int bsa_sim_delete(bsa_ctx *cc, int64_t k, const int64_t *idx) {
   BSA_HIP(c, hipStreamSynchronize(c->stream));
   if (bsa::sect_note_deleted(c, k, idx)) return -1;  // sector occupancy: they count as left
   if (bsa::cond_note_deleted(c, d)) return -1;       // Condition.delac (traffic.py:377)
-  c->xa_pending = false;  // (the delete lists of an unpolled stop name the old indices)
+  c->stops[bsa::kStopArea].pending = false;  // (the delete lists of an unpolled stop name the old indices)
   bsa::Multi mu;
   if (bsa::multi_begin(c, mu)) return -1;
   // old index -> new index (np.delete keeps the order of the rest), -1 = deleted

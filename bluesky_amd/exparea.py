@@ -17,7 +17,7 @@ active``; the accumulators use the nominal ``dt``, whatever time passed.
 """
 import numpy as np
 
-from . import _lib, areafilter
+from . import _lib, areafilter, conditional
 
 ft = 0.3048
 LOG_COLUMNS = ('id', 'create_time', 'flight_time', 'distance2D', 'distance3D', 'work', 'lat', 'lon', 'alt', 'tas', 'vs',
@@ -182,14 +182,9 @@ def run(sim, area, nsteps, cond=None, execute=None, batch=None):
         for _ in range(ran):
             last, area.simt = area.simt, area.simt + area.simdt
         sim.ctx.sim_exparea_simt(area.simt)
-        cmds = None
-        if cond is not None:                    # (before any delete: a delete compacts the device table)
-            fired, step = sim.conditions()
-            if len(fired):
-                cmds = [cond.cmd[i] for i in fired]
-                cond.delcondition(fired)
-                cond.lastdif = sim.read_conditions()['lastdif']
-                stops.append((step, fired, cmds))
+        stop = conditional.take_stop(sim, cond) if cond is not None else None   # (before any delete)
+        if stop is not None:
+            stops.append(stop)
         ev = sim.exparea_events()
         delidx, delidxalt = ev['delidx'], ev['delidxalt']
         if len(delidx) or len(delidxalt):
@@ -215,12 +210,8 @@ def run(sim, area, nsteps, cond=None, execute=None, batch=None):
                 dead = set(lst)
                 area.ids = [x for k, x in enumerate(area.ids) if k not in dead]
             events.append(dict(step=ev['step'], simt=last, delidx=delidx, delidxalt=delidxalt, deleted_ids=gone, columns=cols))
-        if cmds is not None:
-            v = cond.version
-            for c in cmds:
-                execute(c)
-            if cond.version != v:
-                sim.set_conditions(cond)
+        if stop is not None:
+            conditional.execute_stop(sim, cond, stop[2], execute)
     if cond is not None and cond.ncond:
         cond.lastdif = sim.read_conditions()['lastdif']
     return events, stops

@@ -120,6 +120,75 @@ def test_dropin_bookkeeping_matches_the_reference(dac):
     assert np.array_equal(c.lastdif, np.delete(newdif, fired)) and c.cmd == [x for i, x in enumerate(before['cmd']) if i not in set(fired)]
 
 
+class ScriptedSim:
+    """A stand-in for ResidentSim: recorded answers of ``step`` and ``conditions``; ``read_conditions`` answers a
+    lastdif that tells the calls apart; every ``set_conditions`` is noted with the table's version and commands."""
+
+    def __init__(self, steps, polls):
+        self.steps, self.polls, self.uploads, self.reads = list(steps), list(polls), [], 0
+        self.ctx = types.SimpleNamespace(sim_exparea_simt=lambda simt: None, n=8)
+
+    def set_conditions(self, cond):
+        self.cond = cond
+        self.uploads.append((cond.version, list(cond.cmd)))
+
+    def step(self, nsteps):
+        return self.steps.pop(0)
+
+    def conditions(self):
+        return self.polls.pop(0)
+
+    def read_conditions(self):
+        self.reads += 1
+        return dict(lastdif=np.full(self.cond.ncond, float(self.reads)))
+
+    def exparea_events(self):
+        return dict(delidx=np.zeros(0, np.int32), delidxalt=np.zeros(0, np.int32), step=0, records=None)
+
+
+def test_both_run_loops_handle_a_conditions_stop_alike():
+    """conditional.run and the conditions' half of exparea.run over the same recorded sim answers -- 10 steps in
+    batches that end after 3, 7, 9 and 10, conditions fired at the first two: ``execute`` sees the same commands in
+    the same order, the returned stops are equal, and the table goes up again exactly when ``cond.version`` moved
+    while a stop's commands ran (the first stop's 'ADD' appends a condition; the second changes nothing)."""
+    from bluesky_amd import exparea
+    none = np.zeros(0, np.int32)
+    script = dict(steps=[3, 4, 2, 1], polls=[(np.array([0, 2], np.int32), 3), (np.array([1], np.int32), 7), (none, 7), (none, 7)])
+
+    def drive(loop):
+        traf = types.SimpleNamespace(id=['AC%d' % k for k in range(8)], alt=np.arange(8.) * 100., tas=np.full(8, 150.),
+                                     cas=np.full(8, 140.))
+        cond = conditional.Condition(traf, stack=lambda cmd: None)
+        for k, cmd in enumerate(['A', 'B', 'ADD', 'D', 'E']):
+            cond.ataltcmd(k, 5000. + k, cmd)
+        sim, log = ScriptedSim(**script), []
+
+        def execute(cmd):
+            log.append((cmd, cond.version, list(cond.cmd)))
+            if cmd == 'ADD':
+                cond.atspdcmd(7, 99., 'F')
+
+        if loop == 'conditional':
+            stops = conditional.run(sim, 10, cond, execute)
+        else:
+            area = exparea.Area()
+            area.sim, area.simt, area.simdt, area.ids = sim, 0.0, 0.05, list(traf.id)
+            events, stops = exparea.run(sim, area, 10, cond=cond, execute=execute)
+            assert events == []
+        assert sim.steps == [] and sim.polls == []
+        return dict(log=log, stops=[(s, list(f), c) for s, f, c in stops], uploads=sim.uploads, cmd=list(cond.cmd),
+                    lastdif=list(cond.lastdif), reads=sim.reads)
+
+    a, b = drive('conditional'), drive('exparea')
+    assert a == b
+    assert [x[0] for x in a['log']] == ['A', 'ADD', 'D']           # ascending condition index within a stop
+    assert a['stops'] == [(3, [0, 2], ['A', 'ADD']), (7, [1], ['D'])]
+    assert a['log'][0][2] == ['B', 'D', 'E']                       # the fired rows left the table before execute ran
+    v0, v1 = a['uploads'][0][0], a['log'][1][1]
+    assert a['uploads'] == [(v0, ['A', 'B', 'ADD', 'D', 'E']), (v1 + 1, ['B', 'D', 'E', 'F'])]   # not after the second stop
+    assert a['cmd'] == ['B', 'E', 'F'] and a['lastdif'] == [3.0] * 3 and a['reads'] == 3
+
+
 def test_c_entries_refuse_without_a_context():
     lib = _lib.load()
     count = ctypes.c_int64(7)

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from bluesky_amd import _lib, areafilter, conditional, exparea, fms, resident
-from tests import exparea_np, util
+from tests import cond_np, exparea_np, util
 from tests.test_exparea_np import case_of
 from tests.test_gpu_cond import altitudes, climbers, crossing, dress, movers, traf_of
 from tests.test_gpu_multirank import run_ranks
@@ -248,6 +248,82 @@ def test_stops_and_aborts_together(ctx, case):
     assert twin['events'] and twin['events'][0][0] == 2 and twin['stats']['n_conf'] > 0
     assert twin['stats']['steps'] == 12
     assert np.array_equal(twin['area']['distance2D'] > 0, np.ones(len(twin['ids']), bool))
+
+
+def test_each_stage_takes_only_its_own_stop(ctx):
+    """The per-stage pending words: 65 aircraft, no CD, the pass every 2nd step.  A condition fires in step 3 (no
+    pass), an aircraft exits in step 6 (a pass): at the first stop only the conditions' poll has something, at
+    the second only the area's.  Both steps are known before the device runs, from the oracle's kinematics with
+    tests/cond_np.py and tests/exparea_np.py: each threshold lies midway between the aircraft's altitudes around
+    its step, >= 5 mm from both, against the 1e-9 rule's 1e-5 m at these altitudes.  step(8) against 8 x step(1):
+    the same polls, state and accumulators bitwise."""
+    from oracle import step as ostep
+    from oracle.kinematics import vtas2cas
+    n, nsteps, every = 65, 8, 2
+    init = climbers(n, 31, 30.0)
+    p = resident.params(cd_every=1000000, rpz=1.0, hpz=1.0, tla=1.0)
+    op = dict(simdt=p.simdt, rpz=1.0, hpz=1.0, tla=1.0, reso=False, wind=None, mvp=None)
+    traj = [dict(init, asas_trk=init['trk'].copy(), asas_tas=init['tas'].copy(), asas_vs=np.zeros(n), active=np.zeros(n, bool))]
+    for _ in range(nsteps):
+        traj.append(ostep.sim_step(traj[-1], op, do_cd=False))
+    alts = np.array([t['alt'] for t in traj])
+    up = [k for k in movers(alts) if alts[6, k] > alts[5, k]]
+    cac, xac = [k for k in movers(alts) if k != up[0]][0], up[0]
+    areas = band_area(alts, xac, 6)
+
+    def table():
+        cond = conditional.Condition(traf_of(init, n), stack=lambda cmd: None)
+        crossing(cond, alts, cac, 3, 'C3')
+        cond.ataltcmd(n - 1, float(init['alt'][n - 1] + 5000.0), 'NEVER')      # (k_sim_cond still runs at the second stop)
+        return cond
+
+    # the CPU's prediction (no CD: the aircraft move independently, a delete just drops a column): the condition at
+    # step 3 alone, the exit at step 6 alone
+    cond, gone = table(), []
+    tab = cond_np.table(cond.idx, cond.condtype, cond.target, cond.lastdif)
+    st = dict(distance2D=np.zeros(n), distance3D=np.zeros(n), work=np.zeros(n), oldalt=init['alt'].copy(), inside=np.zeros(n, bool))
+    want = []
+    for k in range(1, nsteps + 1):
+        t = {f: np.delete(traj[k][f], gone) for f in ('gs', 'vs', 'alt', 'lat', 'lon', 'tas')}
+        fired, tab['lastdif'] = cond_np.update(tab['idx'], tab['condtype'], tab['target'], tab['lastdif'], t['alt'],
+                                               vtas2cas(t['tas'], np.delete(alts[k - 1], gone)))
+        tab = cond_np.delcondition(tab, fired)
+        d1 = []
+        if k % every == 0:
+            st, d1, d2 = exparea_np.update(st, t['gs'], t['vs'], t['alt'], t['lat'], t['lon'], None, every * p.simdt, areas['BAND'])
+            assert len(d2) == 0
+        if len(fired) or len(d1):
+            want.append((k, [int(x) for x in fired], [int(x) for x in d1]))
+        if len(d1):
+            gone, st, tab = gone + list(d1), {f: np.delete(v, d1) for f, v in st.items()}, cond_np.delac(tab, np.sort(d1))
+    assert want == [(3, [0], []), (6, [], [xac])] and len(gone) == 1 and list(tab['idx']) == [n - 2]
+
+    def drive(chunk):
+        sim = resident.ResidentSim(init, p, ctx=ctx)
+        sim.set_areas(areas)
+        sim.set_conditions(table())
+        sim.set_exparea('BAND', dt=every * p.simdt, every=every, simt=0.0)
+        polls, done = [], 0
+        while done < nsteps:
+            done += sim.step(min(chunk, nsteps - done))
+            fired, cstep = sim.conditions()
+            ev = sim.exparea_events()
+            assert len(ev['delidxalt']) == 0
+            if len(fired) or len(ev['delidx']):
+                assert (len(fired) == 0 or cstep == done) and (len(ev['delidx']) == 0 or ev['step'] == done)
+                polls.append((done, [int(x) for x in fired], [int(x) for x in ev['delidx']]))
+            if len(ev['delidx']):
+                sim.delete(ev['delidx'])
+        return dict(polls=polls, read=sim.read(), area=sim.read_exparea(), table=sim.read_conditions(), steps=sim.stats()['steps'])
+
+    a, b = drive(nsteps), drive(1)
+    assert a['polls'] == want and b['polls'] == want and a['steps'] == b['steps'] == nsteps
+    for part in ('read', 'area'):
+        for k in a[part]:
+            assert len(a[part][k]) == n - 1 and np.array_equal(a[part][k], b[part][k], equal_nan=True), (part, k)
+    for k in a['table']:
+        assert a['table'][k].tobytes() == b['table'][k].tobytes(), k
+    assert list(a['table']['idx']) == [n - 2] and a['area']['distance2D'].all() and a['area']['inside'].any()
 
 
 def test_delete_and_create_carry_the_arrays(ctx):
