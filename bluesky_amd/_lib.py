@@ -346,6 +346,14 @@ SIGNATURES.update({
     'bsa_sim_geovec_stats': (ctypes.c_int, [_vp, _c_i64p, _c_u64p]),
 })
 
+# the tests' entries to the device scan and the ordered index list
+_c_u32p = ctypes.POINTER(ctypes.c_uint32)
+SIGNATURES.update({
+    'bsa_scan_excl': (ctypes.c_int, [_vp, ctypes.c_int64, _c_u32p, _c_u32p]),
+    'bsa_flagged_list': (ctypes.c_int, [_vp, ctypes.c_int64, _c_u8p, _c_u32p, ctypes.c_uint32, ctypes.c_int64, _c_i32p,
+                                        _c_i64p]),
+})
+
 UNIQUE_ID_BYTES = 128
 
 _lib = None
@@ -1317,6 +1325,34 @@ class Context:
     def set_row_bucket(self, width):
         """bsa_set_row_bucket: K2's per-row bucket width (0 = scatter into segments)."""
         self.check(self.lib.bsa_set_row_bucket(self.h, int(width)), 'bsa_set_row_bucket')
+
+    # ---------------------------------------------------------------- test seams (bsa_scan.hip)
+    def scan_excl(self, x):
+        """bsa_scan_excl: the device's exclusive prefix sum (mod 2^32) of the uint32 words ``x``."""
+        x = np.ascontiguousarray(x, dtype=np.uint32).ravel()
+        out = np.empty_like(x)
+        self.check(self.lib.bsa_scan_excl(self.h, len(x), ptr(x, _c_u32p), ptr(out, _c_u32p)), 'bsa_scan_excl')
+        return out
+
+    def flagged_list(self, flag, id2h=None, mask=1, cap=None):
+        """bsa_flagged_list: the indices i with ``flag[id2h[i]] & mask`` (``id2h`` None: ``flag[i]``),
+        ascending.  ``cap``: the room offered (default: len(flag)); a longer list raises AccelError
+        whose ``count`` is the list's true length."""
+        flag = np.ascontiguousarray(flag, dtype=np.uint8).ravel()
+        n = len(flag)
+        if id2h is not None:
+            id2h = np.ascontiguousarray(id2h, dtype=np.uint32).ravel()
+            if len(id2h) != n:
+                raise ValueError('flag and id2h differ in length')
+        cap = n if cap is None else int(cap)
+        out, count = np.zeros(max(cap, 1), np.int32), ctypes.c_int64(-1)
+        try:
+            self.check(self.lib.bsa_flagged_list(self.h, n, ptr(flag, _c_u8p), ptr(id2h, _c_u32p), int(mask), cap,
+                                                 ptr(out, _c_i32p), ctypes.byref(count)), 'bsa_flagged_list')
+        except AccelError as e:
+            e.count = count.value
+            raise
+        return out[:count.value].astype(np.int64)
 
     def sim_row_ids(self):
         """Aircraft indices of this rank's rows, ascending (bsa_sim_row_ids): the

@@ -499,7 +499,7 @@ void bsa_destroy(bsa_ctx *c) {
                         &c->key_c, &c->idx_c, &c->key_c2, &c->perm_c, &c->tbox_r, &c->tbox_c,
                         &c->gbox_r, &c->gbox_c, &c->sbox_c, &c->workq, &c->workq2, &c->counters2, &c->rowcnt, &c->rowoff,
                         &c->cflag, &c->stats,
-                        &c->tilepairs, &c->scan_ws, &c->snap_build, &c->snap_cur, &c->reuse_ctl, &c->reuse_use,
+                        &c->tilepairs, &c->scan_ws, &c->scan_stage, &c->snap_build, &c->snap_cur, &c->reuse_ctl, &c->reuse_use,
                         &c->geo_in, &c->geo_pts, &c->geo_out, &c->wfield, &c->wfield3, &c->wind_pa, &c->wind_stage, &c->turb_stage, &c->area_stage, &c->gv_stage, &c->area_verts, &c->sect_tab, &c->sect_cnt,
                         &c->hv_cost, &c->hv_flag, &c->hv_list[0], &c->hv_list[1], &c->hv_list[2], &c->hv_list[3],
                         &c->hv_cnt, &c->nonfin, &c->rownf};

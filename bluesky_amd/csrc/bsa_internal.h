@@ -262,6 +262,7 @@ struct Ctx {
   bool scan_ready = false;
   unsigned long long scan_tickets = 0;
   unsigned scan_epoch = 0;
+  DevBuf scan_stage;             // bsa_scan_excl / bsa_flagged_list's arrays (the tests' entries)
   // what a detect keeps from earlier calls (bsa_kept.h); dropped through invalidate() below
   KeptOrder order;
   KeptCands cands;

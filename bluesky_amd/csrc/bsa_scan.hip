@@ -1,7 +1,10 @@
 // Exclusive prefix sum of unsigned words in one launch (scan_excl,
 // bsa_internal.h): K2's row offsets at bucket width 0, the halo plan's lists.
 // On top of it the ordered index list of a flag array (flagged_list): the
-// stopping stages' fired conditions and delete lists.
+// stopping stages' fired conditions and delete lists.  Both also as C entries
+// over host arrays, for the tests (bsa_scan_excl, bsa_flagged_list).
+#include <algorithm>
+
 #include "bsa_internal.h"
 #include "bsa_wave.h"
 
@@ -100,7 +103,7 @@ int scan_excl(Ctx *c, const unsigned *in, unsigned *out, int n) {
   if (n <= 0) return 0;
   const bool small = n <= (1 << 19);
   const int kScanTile = small ? 512 * 4 : 1024 * 8;
-  const unsigned tiles = (unsigned)((n + kScanTile - 1) / kScanTile);
+  const unsigned tiles = ((unsigned)n + kScanTile - 1) / kScanTile;  // (unsigned: n + tile - 1 may pass 2^31)
   const size_t had = c->scan_ws.bytes;
   if (!ensure_keep(c, c->scan_ws, 8 * (size_t)(1 + tiles), "scan tile status")) return -1;
   if (c->scan_ws.bytes != had) c->scan_ready = false;  // grown: the new words are uninitialised
@@ -171,3 +174,55 @@ int flagged_list(Ctx *c, int64_t n, const uint8_t *flag, const unsigned *id2h, u
 }
 
 }  // namespace bsa
+
+// ------------------------------------------------------------------ test seams
+// The two primitives over host arrays (tests/test_gpu_scan.py): staged into device scratch, run by the functions
+// above on the context's stream -- the context's scan_ws, tickets and epoch are the ones every other caller uses
+extern "C" int bsa_scan_excl(bsa_ctx *cc, int64_t n, const uint32_t *in, uint32_t *out) {
+  bsa::Ctx *c = (bsa::Ctx *)cc;
+  if (!c) return -1;
+  if (n < 0 || n > 0x7fffffff) return bsa::fail(c, "bsa_scan_excl: bad n");
+  if (n == 0) return 0;
+  if (!in || !out) return bsa::fail(c, "bsa_scan_excl: NULL array");
+  BSA_HIP(c, hipSetDevice(c->device));
+  const size_t N = (size_t)n;
+  if (!bsa::ensure(c, c->scan_stage, 2 * N * 4, "scan arrays")) return -1;
+  unsigned *d_in = (unsigned *)c->scan_stage.p, *d_out = d_in + N;
+  hipStream_t s = c->stream;
+  BSA_HIP(c, hipMemcpyAsync(d_in, in, N * 4, hipMemcpyHostToDevice, s));
+  if (bsa::scan_excl(c, d_in, d_out, (int)n)) return -1;
+  BSA_HIP(c, hipMemcpyAsync(out, d_out, N * 4, hipMemcpyDeviceToHost, s));
+  BSA_HIP(c, hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int bsa_flagged_list(bsa_ctx *cc, int64_t n, const uint8_t *flag, const uint32_t *id2h, uint32_t mask,
+                                int64_t cap, int32_t *out, int64_t *count) {
+  bsa::Ctx *c = (bsa::Ctx *)cc;
+  if (!c) return -1;
+  if (!count) return bsa::fail(c, "bsa_flagged_list: NULL count");
+  *count = 0;
+  if (n < 0 || n > 0x7fffffff - 64 || cap < 0) return bsa::fail(c, "bsa_flagged_list: bad n or cap");
+  if (n == 0) return 0;  // nothing is launched
+  if (!flag) return bsa::fail(c, "bsa_flagged_list: NULL flags");
+  if (id2h)
+    for (int64_t k = 0; k < n; ++k)
+      if (id2h[k] >= (uint64_t)n)
+        return bsa::fail(c, "bsa_flagged_list: id2h[%lld] = %u of %lld", (long long)k, id2h[k], (long long)n);
+  BSA_HIP(c, hipSetDevice(c->device));
+  // stage: id2h | the compaction's words | flags
+  const size_t N = (size_t)n, W = bsa::flagged_ws_words(n);
+  if (!bsa::ensure(c, c->scan_stage, (N + W) * 4 + N, "flag list arrays")) return -1;
+  unsigned *d_id = (unsigned *)c->scan_stage.p, *d_ws = d_id + N;
+  uint8_t *d_flag = (uint8_t *)(d_ws + W);
+  hipStream_t s = c->stream;
+  if (id2h) BSA_HIP(c, hipMemcpyAsync(d_id, id2h, N * 4, hipMemcpyHostToDevice, s));
+  BSA_HIP(c, hipMemcpyAsync(d_flag, flag, N, hipMemcpyHostToDevice, s));
+  std::vector<int32_t> list;
+  if (bsa::flagged_list(c, n, d_flag, id2h ? d_id : (const unsigned *)nullptr, mask, d_ws, &list, nullptr)) return -1;
+  *count = (int64_t)list.size();
+  if (*count > cap) return bsa::fail(c, "bsa_flagged_list: %lld flagged, room for %lld", (long long)*count, (long long)cap);
+  if (*count > 0 && !out) return bsa::fail(c, "bsa_flagged_list: NULL list");
+  std::copy(list.begin(), list.end(), out);
+  return 0;
+}

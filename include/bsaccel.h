@@ -36,6 +36,8 @@
  *       bluesky/simulation/qtgl/screenio.py:194-239  send_aircraft_data (ACDATA stream fields)
  *   bsa_sim_*     GPU-resident chain of the above, no reference equivalent
  *   bsa_comm_*    RCCL row-sharded multi-GPU mode, no reference equivalent
+ *   bsa_scan_excl, bsa_flagged_list
+ *       test seams of the device's exclusive scan and ordered index list, no reference equivalent
  *
  * Threading: a context is bound to one HIP device and one stream and is not
  * thread-safe; use one context per host thread (the BlueSky sim loop is
@@ -1059,6 +1061,24 @@ typedef struct bsa_acdata {
 } bsa_acdata;
 int bsa_sim_acdata_request(bsa_ctx *ctx);
 int bsa_sim_acdata_poll(bsa_ctx *ctx, int wait, bsa_acdata *out);
+
+/* ---------------------------------------------------------------- test seams
+ * The two device primitives under the detect's row offsets, the bookkeeping's
+ * CSR, the halo plan and the stopping stages' lists, over host arrays.  The
+ * arrays are staged into device scratch and the library's own functions run on
+ * the context's stream, with the context's scan state (tile status words,
+ * ticket counter, epoch) -- the state every other caller's scans use.  Their
+ * callers are the tests.
+ *
+ * bsa_scan_excl: out[i] = (in[0] + ... + in[i-1]) mod 2^32, out[0] = 0.
+ * n == 0 writes nothing; n > INT32_MAX is refused. */
+int bsa_scan_excl(bsa_ctx *ctx, int64_t n, const uint32_t *in, uint32_t *out);
+/* bsa_flagged_list: the i in [0, n) with flag[id2h ? id2h[i] : i] & mask != 0,
+ * ascending (np.flatnonzero's), into out (room for cap); *count = how many,
+ * written also when count > cap, which is an error.  Every id2h[i] must be
+ * below n.  n == 0 launches nothing. */
+int bsa_flagged_list(bsa_ctx *ctx, int64_t n, const uint8_t *flag, const uint32_t *id2h, uint32_t mask, int64_t cap,
+                     int32_t *out, int64_t *count);
 
 #ifdef __cplusplus
 }
