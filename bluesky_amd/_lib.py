@@ -310,6 +310,12 @@ SIGNATURES.update({
     'bsa_sim_exparea_simt': (ctypes.c_int, [_vp, ctypes.c_double]),
     'bsa_sim_exparea_poll': (ctypes.c_int, [_vp, ctypes.c_int64, _c_i32p, _c_i64p, _c_i32p, _c_i64p, _c_dp, _c_i64p]),
     'bsa_sim_read_exparea': (ctypes.c_int, [_vp] + [_c_dp] * 5 + [_c_u8p]),
+    'bsa_trails_update': (ctypes.c_int, [_vp, ctypes.c_int64] + [_c_dp] * 5 + [ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                         ctypes.c_int64] + [_c_dp] * 5 + [_c_i32p, _c_i64p]),
+    'bsa_sim_set_trails': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _c_dp,
+                                          ctypes.c_int64]),
+    'bsa_sim_trails_drain': (ctypes.c_int, [_vp, ctypes.c_int64] + [_c_dp] * 5 + [_c_i32p, _c_i64p, _c_dp, _c_dp]),
+    'bsa_sim_read_trails': (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_i64p]),
 })
 
 # one record of bsa_sim_exparea_poll (fp64 words, per exited aircraft)
@@ -1273,6 +1279,69 @@ class Context:
         self.check(self.lib.bsa_sim_read_exparea(self.h, *[ptr(o[k]) for k in keys], ptr(ins, _c_u8p)),
                    'bsa_sim_read_exparea')
         o['inside'] = ins.astype(bool)
+        return o
+
+    # ---------------------------------------------------------------- trails
+    def trails_update(self, lat, lon, lastlat, lastlon, lasttim, t, dt, active=True, cap=None):
+        """bsa_trails_update: one Trails.update(t) (traffic/trails.py:71-135).  Returns a dict of the updated
+        lastlat / lastlon / lasttim and the segments lat0, lon0, lat1, lon1, time, idx in emission order.
+        ``cap``: the room offered (default: n); more segments raise AccelError whose ``count`` is their number."""
+        ins = [f64(x).ravel() for x in (lat, lon)]
+        st = [f64(x).ravel().copy() for x in (lastlat, lastlon, lasttim)]
+        n = len(ins[0])
+        if any(len(x) != n for x in ins + st):
+            raise ValueError('trail arrays differ in length')
+        cap = n if cap is None else int(cap)
+        seg = [np.zeros(max(cap, 1)) for _ in range(5)]
+        idx, count = np.zeros(max(cap, 1), np.int32), ctypes.c_int64(-1)
+        try:
+            self.check(self.lib.bsa_trails_update(self.h, n, *[ptr(x) for x in ins + st], float(t), float(dt),
+                                                  int(bool(active)), cap, *[ptr(x) for x in seg], ptr(idx, _c_i32p),
+                                                  ctypes.byref(count)), 'bsa_trails_update')
+        except AccelError as e:
+            e.count = count.value
+            raise
+        m = count.value
+        out = dict(lastlat=st[0], lastlon=st[1], lasttim=st[2], idx=idx[:m].astype(np.int64))
+        out.update({k: v[:m].copy() for k, v in zip(('lat0', 'lon0', 'lat1', 'lon1', 'time'), seg)})
+        return out
+
+    def sim_set_trails(self, on, active=True, dt=10.0, simt=0.0, lasttim=0.0, max_segments=1 << 24):
+        """bsa_sim_set_trails: Trails.update as a stage of every step.  ``lasttim``: a scalar or n values."""
+        last = np.ascontiguousarray(np.broadcast_to(f64(lasttim), (self.n,))).copy() if on else None
+        self.check(self.lib.bsa_sim_set_trails(self.h, int(bool(on)), int(bool(active)), float(dt), float(simt), ptr(last),
+                                               int(max_segments)), 'bsa_sim_set_trails')
+
+    def sim_trails_drain(self, last=True):
+        """bsa_sim_trails_drain: dict of lat0, lon0, lat1, lon1, time, idx of the segments since the last drain, in
+        emission order, and with ``last`` lastlat / lastlon by aircraft index."""
+        cap = max(self.sim_read_trails(arrays=False)['undrained'], 1)
+        ll = [np.zeros(self.n), np.zeros(self.n)] if last else [None, None]
+        while True:
+            seg = [np.zeros(cap) for _ in range(5)]
+            idx, count = np.zeros(cap, np.int32), ctypes.c_int64(0)
+            self.check(self.lib.bsa_sim_trails_drain(self.h, cap, *[ptr(x) for x in seg], ptr(idx, _c_i32p),
+                                                     ctypes.byref(count), ptr(ll[0]), ptr(ll[1])), 'bsa_sim_trails_drain')
+            if count.value <= cap:
+                break
+            cap = count.value
+        m = count.value
+        out = {k: v[:m].copy() for k, v in zip(('lat0', 'lon0', 'lat1', 'lon1', 'time'), seg)}
+        out['idx'] = idx[:m].astype(np.int64)
+        if last:
+            out.update(lastlat=ll[0], lastlon=ll[1])
+        return out
+
+    def sim_read_trails(self, arrays=True):
+        """bsa_sim_read_trails: dict of lastlat, lastlon, lasttim by aircraft index (with ``arrays``), ``simt`` (the
+        t of the next step's update), ``last_t`` (the last step's) and ``undrained`` (segments on the device as of
+        the last batch or drain)."""
+        o = {k: np.zeros(self.n) for k in ('lastlat', 'lastlon', 'lasttim')} if arrays else {}
+        simt, last_t, und = ctypes.c_double(0.0), ctypes.c_double(0.0), ctypes.c_int64(0)
+        self.check(self.lib.bsa_sim_read_trails(self.h, *[ptr(o.get(k)) for k in ('lastlat', 'lastlon', 'lasttim')],
+                                                ctypes.byref(simt), ctypes.byref(last_t), ctypes.byref(und)),
+                   'bsa_sim_read_trails')
+        o.update(simt=simt.value, last_t=last_t.value, undrained=int(und.value))
         return o
 
     def sim_cd(self):

@@ -136,6 +136,9 @@ constexpr unsigned stop_word(unsigned stage, unsigned tag) { return (stage << 24
 constexpr unsigned stop_stage(unsigned w) { return w >> 24; }
 constexpr unsigned stop_tag(unsigned w) { return w & kStopTagMax; }
 constexpr int kSimCtlEnd = kSimCtlPend + 8 * (int)kStopCount;
+// behind the per-batch words, never zeroed by a batch: the trail stage's running total of undrained segments and
+// its demand word (u32 each; bsa_trails.hip), read back with the batch's words
+constexpr int kSimCtlTrail = kSimCtlEnd, kSimCtlAll = kSimCtlTrail + 8;
 // sim_ctl's per-batch words as batch_end hands them back
 struct BatchCtl {
   unsigned sticky, stop;  // kSticky*; stop_word(stage, tag) of the first raiser, 0: no stop
@@ -239,6 +242,8 @@ struct StepClocks {
   int64_t sect_ctr = 0;                    // sectors (3.27): steps since bsa_sim_set_sectors
   int64_t gv_ctr = 0;                      // geovectors (3.28): steps completed since bsa_sim_set_geovectors
   int64_t area_ctr = 0;                    // experiment area (3.30): steps since bsa_sim_set_exparea
+  double trail_simt = 0.0, trail_last = 0.0;  // trails (3.31): the simt the next step's traf.update is called with,
+                                              // ... and the one the last step's was
 };
 
 struct Ctx {
@@ -526,6 +531,16 @@ struct Ctx {
   int64_t xa_every = 1;
   double xa_dt = 0.5, xa_swtaxialt = 0.0, xa_now = 0.0;
 
+  // Trails (bsa_trails.hip).  tr_stage: bsa_trails_update's arrays.  In the resident step
+  // (bsa_sim_set_trails): per aircraft (kSimArrays) lastlat / lastlon / lasttim; the segment buffers tr_seg (5 fp64
+  // arrays of tr_cap, then int32 idx) the pass appends to at the running total (sim_ctl, kSimCtlTrail); tr_ws the
+  // compaction's words; tr_max the most tr_cap may grow to; tr_undrained / tr_demand: the total and the demand
+  // word as the last batch's read-back (or drain) left them.  Its clock: clk.trail_simt
+  DevBuf tr_stage, s_tlat, s_tlon, s_ttim, tr_seg, tr_ws;
+  bool sim_trails = false, tr_active = false;
+  double tr_dt = 10.0;
+  int64_t tr_cap = 0, tr_max = 0, tr_undrained = 0, tr_demand = 0;
+
   // standalone geo matrices (bsa_geo.hip)
   DevBuf geo_in, geo_pts, geo_out;
   hipEvent_t geo_ev[2] = {nullptr, nullptr};
@@ -597,7 +612,7 @@ inline void *ptr_at(const void *strct, int k) { return ((void *const *)strct)[k]
 // it (bsa_traffic.hip: per_aircraft), bsa_sim_init allocates its kSimAlways rows
 // guard: kSimAlways allocated by bsa_sim_init; kSimDetect the last detect's per-row outputs (the detect's to
 // allocate); kSimOnUse once allocated (the reso lists); the others while Ctx::sim_<switch> is on
-enum SimGuard { kSimAlways, kSimDetect, kSimOnUse, kSimLimits, kSimPerf, kSimForces, kSimFms, kSimAtmos, kSimSectors, kSimExparea };
+enum SimGuard { kSimAlways, kSimDetect, kSimOnUse, kSimLimits, kSimPerf, kSimForces, kSimFms, kSimAtmos, kSimSectors, kSimExparea, kSimTrails };
 struct SimArray {
   BufRef buf;
   int esz, count;  // element size; sub-arrays of length n in the buffer
@@ -635,6 +650,8 @@ inline const SimArray kSimArrays[] = {
     {{&Ctx::s_xd2}, 8, 1, false, kSimExparea},       {{&Ctx::s_xd3}, 8, 1, false, kSimExparea},
     {{&Ctx::s_xwork}, 8, 1, false, kSimExparea},     {{&Ctx::s_xoldalt}, 8, 1, false, kSimExparea},
     {{&Ctx::s_xctime}, 8, 1, false, kSimExparea},    {{&Ctx::s_xflag}, 1, 1, false, kSimExparea},
+    {{&Ctx::s_tlat}, 8, 1, false, kSimTrails},       {{&Ctx::s_tlon}, 8, 1, false, kSimTrails},
+    {{&Ctx::s_ttim}, 8, 1, false, kSimTrails},
 };
 // is the array part of the sim now (to be carried through a delete / create)?
 inline bool sim_array_on(Ctx *c, const SimArray &a) {
@@ -647,6 +664,7 @@ inline bool sim_array_on(Ctx *c, const SimArray &a) {
     case kSimAtmos: return c->sim_atmos;
     case kSimSectors: return c->sim_sect;
     case kSimExparea: return c->sim_exparea;
+    case kSimTrails: return c->sim_trails;
     default: return true;
   }
 }
@@ -761,6 +779,16 @@ bool exparea_passes_at(const Ctx *c);
 int exparea_sim_launch(Ctx *c, unsigned tag);
 int exparea_created(Ctx *c, int64_t n, int64_t m, const double *alt);
 void exparea_off(Ctx *c);
+
+// Trails of the step (bsa_trails.hip): Trails.update(simt) on what the step left, after k_sim_cond
+// and before the experiment area's pass; t: clk.trail_simt before the step's advance; tag as for cond_sim_launch.
+// trails_reserve: the segment buffers sized for nsteps more steps, before a batch is enqueued (refuses a batch
+// whose bound exceeds tr_max).  trails_created: Trails.create for the m aircraft bsa_sim_create appended after the
+// first n (lat / lon: theirs, host)
+int trails_sim_launch(Ctx *c, double t, unsigned tag);
+int trails_reserve(Ctx *c, int64_t nsteps);
+int trails_created(Ctx *c, int64_t n, int64_t m, const double *lat, const double *lon);
+void trails_off(Ctx *c);
 
 // Sector occupancy (bsa_area.hip): sect_sim_launch after the last stage of a step whose StepPlan::sect_pass is
 // set (clk.sect_ctr + 1 a multiple of the cadence); sect_note_deleted by bsa_sim_delete before anything moves;

@@ -211,7 +211,7 @@ void sim_release(Ctx *c) {
   // not per aircraft: staging, control words, tables, the FMS undo set, K2 + K4' double buffers
   DevBuf *rest[] = {&c->red, &c->g_send, &c->g_recv, &c->pg_send, &c->pg_recv, &c->sim_ctl, &c->s_ptab, &c->s_ftab,
                     &c->f_const, &c->s_fmsrows, &c->s_fmsur, &c->s_fmsuf, &c->s_fmsui, &c->gv_tab, &c->gv_shapes, &c->gv_undo,
-                    &c->gv_cnt, &c->xfer_stage, &c->lbyidx, &c->xa_ws, &c->xa_rec,
+                    &c->gv_cnt, &c->xfer_stage, &c->lbyidx, &c->xa_ws, &c->xa_rec, &c->tr_stage, &c->tr_seg, &c->tr_ws,
                     &c->fetch_stage, &c->tpr_snap, &c->tpr_ctl, &c->nx_alt, &c->nx_vs, &c->nx_gse, &c->nx_gsn};
   for (auto *b : rest) release(*b);
   bk_release(c);
@@ -333,6 +333,10 @@ struct StepPlan {
   // the experiment area's pass (3.30) follows k_sim_cond: clk.area_ctr + 1 is a multiple of its cadence; a stop it
   // raises carries cond_tag too
   bool area_pass;
+  // trails (3.31): Trails.update(trail_t) between k_sim_cond and the area's pass, behind the sticky word by
+  // cond_tag; trail_t: clk.trail_simt at the step's start, the simt traf.update was called with
+  bool trails;
+  double trail_t;
 };
 static StepPlan step_decide(const Ctx *c, bool rerun_first) {
   const DetectEnv &env = detect_env();
@@ -353,6 +357,8 @@ static StepPlan step_decide(const Ctx *c, bool rerun_first) {
   sp.cond = c->sim_cond;
   sp.cond_tag = (unsigned)(k.steps - c->batch_steps0 + 1);
   sp.area_pass = exparea_passes_at(c);
+  sp.trails = c->sim_trails;
+  sp.trail_t = k.trail_simt;
   return sp;
 }
 
@@ -368,6 +374,7 @@ static void step_advance(Ctx *c, const StepPlan &sp) {
   if (c->sim_turb) k.turb_call++;
   if (c->sim_sect) k.sect_ctr++;
   if (c->sim_exparea) k.area_ctr++;
+  if (c->sim_trails) k.trail_last = k.trail_simt, k.trail_simt += c->simp.simdt;  // simt += simdt (simulation.py), accumulated as there
   k.steps++;
 }
 
@@ -385,10 +392,18 @@ static int batch_begin(Ctx *c, bool kin, BatchBase *b) {
   BSA_HIP(c, hipMemsetAsync((char *)c->sim_ctl.p + kSimCtlSticky, 0, sizeof(BatchCtl), c->stream));
   return 0;
 }
-// the batch's only host synchronisation
+// the batch's only host synchronisation; the trail stage's words {total, demand} lie right behind the batch's and
+// come back in the same copy
 static int batch_end(Ctx *c, BatchCtl *ctl) {
-  BSA_HIP(c, hipMemcpyAsync(ctl, (char *)c->sim_ctl.p + kSimCtlSticky, sizeof(BatchCtl), hipMemcpyDeviceToHost, c->stream));
+  struct {
+    BatchCtl ctl;
+    unsigned trail[2];
+  } h{};
+  static_assert(sizeof(h) == kSimCtlAll - kSimCtlSticky, "the trail words follow BatchCtl");
+  BSA_HIP(c, hipMemcpyAsync(&h, (char *)c->sim_ctl.p + kSimCtlSticky, sizeof(h), hipMemcpyDeviceToHost, c->stream));
   BSA_HIP(c, hipStreamSynchronize(c->stream));
+  *ctl = h.ctl;
+  if (c->sim_trails) c->tr_undrained = h.trail[0], c->tr_demand = h.trail[1];
   return 0;
 }
 
@@ -419,7 +434,10 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const BatchCtl &ctl) {
     // returned behind the sticky word like every later one, so the re-run counts each update once.
     // Experiment area: the pass writes its accumulators only in steps that complete -- the abort is raised in the
     // step's detect, before the pass, which then returned behind the sticky word: nothing to undo, and the replayed
-    // clock makes the re-run count the pass once
+    // clock makes the re-run count the pass once.
+    // Trails: an aborted step's pass wrote nothing, since the abort is raised in the step's detect -- its count
+    // and emit launches returned behind the sticky word and left the running total as it was: nothing to undo,
+    // and the replayed trail_simt hands the re-run the same t
     const StepPlan sp = step_decide(c, false);
     if (sp.fms_tick && fms_sim_restore(c)) return -1;
     if (sp.gv_apply && geovec_sim_restore(c)) return -1;
@@ -619,8 +637,10 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
   if (sp.sect_pass && sect_sim_launch(c)) return -1;  // sector occupancy: reads what the step left (sectorcount.py:53-79)
   // cond.update() (traffic.py:419): reads what the step left; last, so that a stop it raises cuts nothing of this step
   if (sp.cond && cond_sim_launch(c, sp.cond_tag)) return -1;
+  // trails.update(simt), the last statement of Traffic.update (traffic.py:422): on the positions the step left
+  if (sp.trails && trails_sim_launch(c, sp.trail_t, sp.cond_tag)) return -1;
   // the AREA plugin's update follows traf.update (simulation.py: plugin.update after traf.update), whose last
-  // statements are cond.update() and an inactive trails.update: the step's last launch
+  // statements are cond.update() and trails.update: the step's last launch
   if (sp.area_pass && exparea_sim_launch(c, sp.cond_tag)) return -1;
   if (sp.prep)
     c->prep.keep({pa.rpz, pa.hpz, pa.tla, (double)pa.mid, c->n});
@@ -636,7 +656,7 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
 }
 
 // every stage with a launch of its own, off (fms_off takes recovery and the geovectors with it): a new sim
-static void stages_off(Ctx *c) { forces_off(c), fms_off(c), turb_off(c), sect_off(c), cond_off(c), exparea_off(c); }
+static void stages_off(Ctx *c) { forces_off(c), fms_off(c), turb_off(c), sect_off(c), cond_off(c), exparea_off(c), trails_off(c); }
 
 }  // namespace bsa
 
@@ -684,8 +704,8 @@ int bsa_sim_init(bsa_ctx *cc, int64_t n, const bsa_sim_state *s, const bsa_sim_p
       return -1;
   }
   if (up.run()) return -1;
-  if (!bsa::ensure(c, c->sim_ctl, bsa::kSimCtlEnd, "sim control words")) return -1;
-  BSA_HIP(c, hipMemsetAsync(c->sim_ctl.p, 0, bsa::kSimCtlEnd, c->stream));
+  if (!bsa::ensure(c, c->sim_ctl, bsa::kSimCtlAll, "sim control words")) return -1;
+  BSA_HIP(c, hipMemsetAsync(c->sim_ctl.p, 0, bsa::kSimCtlAll, c->stream));
   BSA_HIP(c, hipStreamSynchronize(c->stream));
   c->simp = *p;
   c->bk_ready = false;  // empty resopairs / previous pair sets
@@ -730,6 +750,7 @@ int bsa_sim_step(bsa_ctx *cc, int nsteps) {
   if ((c->sim_cond || c->sim_exparea) && (unsigned)nsteps > bsa::kStopTagMax)
     return bsa::fail(c, "at most %u steps per call while a stage that can stop the batch is on", bsa::kStopTagMax);
   BSA_HIP(c, hipSetDevice(c->device));
+  if (bsa::trails_reserve(c, nsteps)) return -1;  // (before anything is enqueued: a refused batch runs no step)
   const int64_t start = c->clk.steps, target = start + nsteps;
   c->steps_last = 0;
   for (int attempt = 0; c->clk.steps < target; ++attempt) {
@@ -740,6 +761,8 @@ int bsa_sim_step(bsa_ctx *cc, int nsteps) {
       if (bsa::step_enqueue(c, bsa::step_decide(c, attempt > 0 && c->clk.steps == base.clk.steps))) return -1;
     bsa::BatchCtl ctl{};
     if (bsa::batch_end(c, &ctl)) return -1;  // did every step complete?
+    if (c->sim_trails && c->tr_demand)
+      return bsa::fail(c, "internal error: %lld trail segments did not fit the buffers sized for the batch", (long long)c->tr_demand);
 #ifdef BSA_PF_TRACE
     if (bsa::pf_trace_dump(c, 0, 0)) return -1;  // (diagnostic builds: the batch's last prefilter)
 #endif

@@ -354,6 +354,41 @@ class ResidentSim:
         """dict of distance2D, distance3D, work, oldalt, create_time, inside by aircraft index (bsa_sim_read_exparea)."""
         return self.ctx.sim_read_exparea()
 
+    def set_trails(self, on=True, active=True, dt=10.0, simt=0.0, lasttim=None, max_segments=1 << 24):
+        """Trails.update (traffic/trails.py:71-135) as a stage of every step, after the conditions
+        (bsa_sim_set_trails): while ``active`` every aircraft whose last segment is more than ``dt`` old emits
+        the segment from its last to its current position, in ascending index order, into buffers on the
+        device; ``trails()`` drains them.  ``simt``: the sim time of the next step (the stage's clock then
+        accumulates ``simdt`` as the reference's does).  The first call starts ``lastlat`` / ``lastlon`` at
+        the current positions and ``lasttim`` at ``lasttim`` (a scalar or one value per aircraft), default
+        ``simt - simdt``: the time of the update that preceded a TRAIL ON typed between two steps.  Later
+        calls change ``active`` / ``dt`` / ``max_segments`` only; ``active=False`` after True drops the
+        undrained segments, as ``setTrails(False)`` does.  A ``step(k)`` that could emit more than
+        ``max_segments`` (undrained + n * min(k, k * simdt // dt + 1)) is refused before it runs: drain, or
+        step less.  ``on=False`` switches the stage off.  One rank only."""
+        if lasttim is None:
+            lasttim = simt - self.params.simdt
+        self.ctx.sim_set_trails(on, active, dt, simt, lasttim, max_segments)
+        self._trails_active = bool(on) and bool(active)
+
+    def trails(self, last=True):
+        """The trail part of ScreenIO's ACDATA (screenio.py:217-226) since the last call, which it clears
+        (``clearnew``): dict of ``swtrails``, ``traillat0`` / ``traillon0`` / ``traillat1`` / ``traillon1``
+        in emission order, with ``last`` ``traillastlat`` / ``traillastlon`` by aircraft index, plus
+        ``trailtime`` (the ``t`` of each segment's update) and ``trailidx`` (the aircraft's index when it
+        emitted).  Synchronises (bsa_sim_trails_drain)."""
+        r = self.ctx.sim_trails_drain(last)
+        out = dict(swtrails=getattr(self, '_trails_active', False), traillat0=r['lat0'], traillon0=r['lon0'],
+                   traillat1=r['lat1'], traillon1=r['lon1'], trailtime=r['time'], trailidx=r['idx'])
+        if last:
+            out.update(traillastlat=r['lastlat'], traillastlon=r['lastlon'])
+        return out
+
+    def read_trails(self):
+        """dict of lastlat, lastlon, lasttim by aircraft index, ``simt`` (the next step's), ``last_t`` (the last
+        step's) and ``undrained`` (bsa_sim_read_trails)."""
+        return self.ctx.sim_read_trails()
+
     def set_geovectors(self, geovecs, every=1):
         """Geovectoring inside the step (plugins/geovector.py:76-128; bsa_sim_set_geovectors):
         ``geovecs`` is the plugin's list of ``[area, gsmin, gsmax, trkmin, trkmax, vsmin, vsmax]``

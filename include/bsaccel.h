@@ -837,6 +837,51 @@ int bsa_sim_exparea_poll(bsa_ctx *ctx, int64_t cap, int32_t *delidx, int64_t *nd
 /* The arrays by aircraft index, n long each (any may be NULL). */
 int bsa_sim_read_exparea(bsa_ctx *ctx, double *distance2D, double *distance3D, double *work, double *oldalt,
                          double *create_time, uint8_t *inside);
+/* ---------------------------------------------------------------- trails
+ * traffic/trails.py: Trails.update(t).  While active, every aircraft i (in
+ * ascending index order, np.where's) with t - lasttim[i] > dt -- strict; a NaN
+ * delta selects nothing -- emits the segment (lastlat[i], lastlon[i], lat[i],
+ * lon[i], t) and then takes lat[i], lon[i], t as lastlat / lastlon / lasttim.
+ * While inactive lastlat / lastlon take the positions and lasttim takes t;
+ * nothing is emitted.  Every number of a segment is a copy.
+ * bsa_trails_update: one update over host arrays; lastlat, lastlon and lasttim
+ * are updated in place.  The segments go to lat0 .. time and idx (the emitting
+ * aircraft), cap entries each, *count of them.  n == 0 launches nothing; a
+ * count above cap is an error that names both numbers (the arrays are then
+ * left as they were). */
+int bsa_trails_update(bsa_ctx *ctx, int64_t n, const double *lat, const double *lon, double *lastlat,
+                      double *lastlon, double *lasttim, double t, double dt, int active, int64_t cap, double *lat0,
+                      double *lon0, double *lat1, double *lon1, double *time, int32_t *idx, int64_t *count);
+/* The same update as a stage of every resident step, after the conditions and
+ * before the experiment area: trails.update(simt) is the last statement of
+ * Traffic.update.  t is the simt the step started at (the stage's own clock:
+ * `simt` here, + simdt per step, accumulated in fp64 as simulation.py does);
+ * the positions are those the step leaves.  The segments collect on the device
+ * in emission order until bsa_sim_trails_drain; a batch neither synchronises
+ * nor copies for them.  The first call with on != 0 starts lastlat / lastlon at
+ * the current positions and lasttim at lasttim[] (n values by aircraft index:
+ * the time of the update that preceded a TRAIL ON is simt - simdt); later calls
+ * change active / dt / max_segments only, and active = 0 after active = 1 drops
+ * the undrained segments as setTrails(False) does.  on == 0 switches the stage
+ * off.  bsa_sim_delete and bsa_sim_create carry the arrays; of m new aircraft
+ * only the LAST starts at its position, the others at (0, 0), all at lasttim 0
+ * (Trails.create).  bsa_sim_step sizes the segment buffers before it enqueues:
+ * undrained + n * min(k, floor(k * simdt / dt) + 1) for k steps, and refuses
+ * the call, running nothing, when that exceeds max_segments (drain, or step
+ * less).  One rank only. */
+int bsa_sim_set_trails(bsa_ctx *ctx, int on, int active, double dt, double simt, const double *lasttim,
+                       int64_t max_segments);
+/* The segments since the last drain, in emission order (idx: the aircraft's
+ * index when it emitted), and optionally lastlat / lastlon by aircraft index (n
+ * long; may be NULL).  *count above cap: nothing is written or consumed.
+ * Resets the device's total (clearnew()).  Synchronises. */
+int bsa_sim_trails_drain(bsa_ctx *ctx, int64_t cap, double *lat0, double *lon0, double *lat1, double *lon1,
+                         double *time, int32_t *idx, int64_t *count, double *lastlat, double *lastlon);
+/* The arrays by aircraft index (n long each; any may be NULL), the stage's
+ * clock (*simt: the t of the next step's update, *last_t: that of the last
+ * step's) and the undrained segment count as of the last batch or drain. */
+int bsa_sim_read_trails(bsa_ctx *ctx, double *lastlat, double *lastlon, double *lasttim, double *simt,
+                        double *last_t, int64_t *undrained);
 /* ---------------------------------------------------------------- geovectoring
  * plugins/geovector.py:76-128: per area an allowed interval for ground speed,
  * track and vertical speed.  The geovectors are an ordered list; each is
