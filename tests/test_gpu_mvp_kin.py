@@ -72,25 +72,11 @@ def test_mvp_after_gpu_detect(ctx):
 @pytest.mark.parametrize('path', KIN, ids=[util.case_name(p) for p in KIN])
 def test_kinematics_matches_reference_golden(ctx, path):
     z = dict(np.load(path, allow_pickle=False))
-    state = {k: np.ascontiguousarray(z[k], dtype=np.float64).copy()
-             for k in ('tas', 'hdg', 'alt', 'vs', 'lat', 'lon')}
-    inputs = {k: z[k] for k in ('ptas', 'phdg', 'palt', 'pvs', 'bank', 'eps', 'accel')}
-    wd = int(z['winddim'])
-    if wd == 2:   # 2-D wind field (bsa_set_windfield), the reference's getdata pinned by the fixture
-        ctx.set_windfield(z['wlat'], z['wlon'], z['wvnorth'], z['wveast'])
-        o = ctx.kinematics(float(z['dt']), state, inputs, 2, 0.0, 0.0)
-        ctx.set_windfield()
-    else:
-        o = ctx.kinematics(float(z['dt']), state, inputs, wd, float(z['windnorth']), float(z['windeast']))
-    o.update(state)
-    o['M'] = o.pop('mach')
-    scales = dict(ax=1.0, delspd=100.0, tas=300.0, cas=300.0, M=1.0, hdg=360.0, az=1.0, vs=20.0,
-                  gsnorth=300.0, gseast=300.0, gs=300.0, trk=360.0, alt=1e4, lat=90.0, lon=180.0,
-                  coslat=1.0)
-    for k, s in scales.items():
+    o = util.run_kinematics(ctx, z)
+    for k, s in util.KIN_SCALES.items():
         ok, msg = util.close(o[k], z['out_' + k], s)
         assert ok, '%s: %s' % (k, msg)
-    for k in ('swhdgsel', 'swaltsel'):
+    for k in util.KIN_FLAGS:
         assert np.array_equal(o[k], z['out_' + k].astype(bool)), k
 
 
@@ -160,11 +146,8 @@ def test_kinematics_dropin_install_matches_reference_golden(ctx, path):
     traf.UpdatePosition(dt)
     if wd == 2:
         ctx.set_windfield()
-    scales = dict(ax=1.0, delspd=100.0, tas=300.0, cas=300.0, M=1.0, hdg=360.0, az=1.0, vs=20.0,
-                  gsnorth=300.0, gseast=300.0, gs=300.0, trk=360.0, alt=1e4, lat=90.0, lon=180.0,
-                  coslat=1.0)
-    for k, s in scales.items():
+    for k, s in util.KIN_SCALES.items():
         ok, msg = util.close(getattr(traf, k), z['out_' + k], s)
         assert ok, '%s: %s' % (k, msg)
-    for k in ('swhdgsel', 'swaltsel'):
+    for k in util.KIN_FLAGS:
         assert np.array_equal(getattr(traf, k), z['out_' + k].astype(bool)), k

@@ -48,6 +48,33 @@ def close(got, exp, scale, rtol=RTOL):
     return True, ''
 
 
+# bsa_kinematics against a kin_*.npz fixture: the 13 inputs, the outputs with
+# their parity scales and the two flags (tools/make_golden.py's run_kin keys)
+KIN_INPUTS = ('tas', 'hdg', 'alt', 'vs', 'lat', 'lon', 'ptas', 'phdg', 'palt', 'pvs', 'bank', 'eps', 'accel')
+KIN_SCALES = dict(ax=1.0, delspd=100.0, tas=300.0, cas=300.0, M=1.0, hdg=360.0, az=1.0, vs=20.0,
+                  gsnorth=300.0, gseast=300.0, gs=300.0, trk=360.0, alt=1e4, lat=90.0, lon=180.0,
+                  coslat=1.0)
+KIN_FLAGS = ('swhdgsel', 'swaltsel')
+
+
+def run_kinematics(ctx, z):
+    """Context.kinematics on a loaded kin fixture ``z``; returns its outputs
+    under the fixture's names (state after the step included, ``M`` for mach)."""
+    state = {k: np.ascontiguousarray(z[k], dtype=np.float64).copy()
+             for k in ('tas', 'hdg', 'alt', 'vs', 'lat', 'lon')}
+    inputs = {k: z[k] for k in ('ptas', 'phdg', 'palt', 'pvs', 'bank', 'eps', 'accel')}
+    wd = int(z['winddim'])
+    if wd == 2:   # 2-D wind field (bsa_set_windfield), the reference's getdata pinned by the fixture
+        ctx.set_windfield(z['wlat'], z['wlon'], z['wvnorth'], z['wveast'])
+        o = ctx.kinematics(float(z['dt']), state, inputs, 2, 0.0, 0.0)
+        ctx.set_windfield()
+    else:
+        o = ctx.kinematics(float(z['dt']), state, inputs, wd, float(z['windnorth']), float(z['windeast']))
+    o.update(state)
+    o['M'] = o.pop('mach')
+    return o
+
+
 def assert_detect_equal(got, exp, rpz, tla, rows=None):
     """Pair sets/orders exact, inconf exact, reals within RTOL."""
     for k in ('ci', 'cj', 'li', 'lj'):

@@ -10,6 +10,13 @@ and outputs as small ``.npz`` files under ``tests/golden/``:
 * ``mvp_<case>.npz``  -- ``MVP.resolve`` (MVP.py:14-143) for several switch sets
 * ``kin_<case>.npz``  -- ``Traffic.UpdateAirSpeed/GroundSpeed/Position``
                          (traffic.py:425-483)
+* ``kin_edge_<case>.npz`` -- the same on hand-made rows, one per threshold, sign, wrap and
+                         non-finite input (``kin_edge_rows``), at dt 0.05 / 1 / 0, with a
+                         constant wind and with the 2-D field; ``kinx_edge_illcond.npz``
+                         holds the rows set aside as ill-conditioned
+                         (``--kin-edge-only`` writes only these)
+* ``mvp_synth.npz``   -- ``MVP.resolve`` on a hand-made pair payload (``mvp_synth_case``)
+                         (``--mvp-synth-only`` writes only this)
 * ``wind3d_<case>.npz`` -- ``Windfield.getdata`` of a field with altitude profiles
                          (windfield.py:158-202), one call per position, and
                          ``kin3d_wind1500.npz``, the kinematics over such a field
@@ -44,6 +51,7 @@ The reference never leaves this container; only the vectors are committed.
 
 Usage:  python tools/make_golden.py   (takes ~1 min)
 """
+import contextlib
 import os
 import sys
 import types
@@ -87,6 +95,12 @@ from oracle import kinematics as okin                        # noqa: E402
 RPZ = 5.0 * nm
 HPZ = 1000.0 * ft
 TLA = 300.0
+
+
+def quiet(handmade):
+    """numpy's floating-point warnings off for hand-made non-finite inputs; the
+    captures from random traffic run under numpy's defaults."""
+    return np.errstate(all='ignore') if handmade else contextlib.nullcontext()
 
 
 def T(lat, lon, alt, trk, gs, vs):
@@ -272,33 +286,41 @@ def mvp_inputs(traf, seed):
     return dict(gseast=gseast, gsnorth=gsnorth, selalt=selalt, apvs=apvs, asasalt=asasalt)
 
 
-def run_mvp(name, traf, cdres, mar=1.05):
+def run_mvp(name, traf, cdres, mar=1.05, extra=None, noreso_idx=None, resooff_idx=None):
+    """``extra`` / ``noreso_idx`` / ``resooff_idx``: hand-made (run_mvp_synth) instead of
+    mvp_inputs' draws and every 7th / 11th aircraft."""
     confpairs, lospairs, inconf, tcpamax, qdr, dist, tcpa, tin = cdres
-    extra = mvp_inputs(traf, seed=zlib.crc32(name.encode()) % 1000)
+    synthetic = extra is not None
+    if extra is None:
+        extra = mvp_inputs(traf, seed=zlib.crc32(name.encode()) % 1000)
     ids = list(traf.id)
     idmap = {k: i for i, k in enumerate(ids)}
     ci, cj = ids_to_idx(confpairs, idmap)
-    noresolst = ids[::7]
-    resoofflst = ids[3::11]
+    noreso_idx = np.arange(0, len(ids), 7) if noreso_idx is None else np.asarray(noreso_idx, dtype=np.int64)
+    resooff_idx = np.arange(3, len(ids), 11) if resooff_idx is None else np.asarray(resooff_idx, dtype=np.int64)
+    noresolst = [ids[k] for k in noreso_idx]
+    resoofflst = [ids[k] for k in resooff_idx]
     out = dict(ci=ci, cj=cj, qdr=np.asarray(qdr), dist=np.asarray(dist),
                tcpa=np.asarray(tcpa), tLOS=np.asarray(tin),
                lat=traf.lat, lon=traf.lon, alt=traf.alt, trk=traf.trk, gs=traf.gs,
                vs=traf.vs, mar=mar, rpz=RPZ, hpz=HPZ, tla=TLA,
-               noreso_idx=np.arange(0, len(ids), 7), resooff_idx=np.arange(3, len(ids), 11),
+               noreso_idx=noreso_idx, resooff_idx=resooff_idx,
                **extra)
     for mode, sw in MVP_MODES.items():
         asas, tr = make_ref_asas(traf, extra, confpairs, qdr, dist, tcpa, tin, mar, sw,
                                  noresolst, resoofflst)
-        MVP.resolve(asas, tr)
+        with quiet(synthetic):
+            MVP.resolve(asas, tr)
         # oracle must agree bitwise
-        o = omvp.resolve_arrays(
-            ci, cj, np.asarray(qdr), np.asarray(dist), np.asarray(tcpa), np.asarray(tin),
-            gseast=extra['gseast'], gsnorth=extra['gsnorth'], vs=traf.vs, alt=traf.alt,
-            trk=traf.trk, gs=traf.gs, selalt=extra['selalt'], apvs=extra['apvs'],
-            asasalt=extra['asasalt'].copy(), params=omvp.params_from_settings(
-                RPZ, HPZ, TLA, mar, *sw[:6]),
-            noreso=np.isin(np.arange(len(ids)), out['noreso_idx']) if sw[6] else None,
-            resooff=np.isin(np.arange(len(ids)), out['resooff_idx']) if sw[7] else None)
+        with quiet(synthetic):
+            o = omvp.resolve_arrays(
+                ci, cj, np.asarray(qdr), np.asarray(dist), np.asarray(tcpa), np.asarray(tin),
+                gseast=extra['gseast'], gsnorth=extra['gsnorth'], vs=traf.vs, alt=traf.alt,
+                trk=traf.trk, gs=traf.gs, selalt=extra['selalt'], apvs=extra['apvs'],
+                asasalt=extra['asasalt'].copy(), params=omvp.params_from_settings(
+                    RPZ, HPZ, TLA, mar, *sw[:6]),
+                noreso=np.isin(np.arange(len(ids)), out['noreso_idx']) if sw[6] else None,
+                resooff=np.isin(np.arange(len(ids)), out['resooff_idx']) if sw[7] else None)
         for k in ('trk', 'tas', 'vs', 'alt', 'asase', 'asasn'):
             ref = np.asarray(getattr(asas, k))
             assert np.array_equal(o[k], ref, equal_nan=True), \
@@ -343,6 +365,107 @@ def make_ref_asas(traf, extra, confpairs, qdr, dist, tcpa, tin, mar, sw,
     return asas, tr
 
 
+def mvp_synth_case(mar=1.05):
+    """A hand-made pair payload for MVP.resolve, which takes confpairs / qdr / dist /
+    tcpa / tLOS as given: the arms of MVP.MVP and prioRules that a real detect's
+    pairs do not reach, each on an ownship of its own so that one non-finite dv
+    does not hide the other rows.  Returns (traf, extra, cdres, noreso_idx, resooff_idx)."""
+    up = lambda x: float(np.nextafter(x, np.inf))        # noqa: E731
+    dn = lambda x: float(np.nextafter(x, -np.inf))       # noqa: E731
+    Rm = RPZ * mar
+    vmin, vmax = 200.0 * nm / 3600., 500.0 * nm / 3600.
+    ac, pairs = [], []
+
+    def aircraft(gse=0.0, gsn=200.0, vs=0.0, alt=8000.0, selalt=None, apvs=1500.0 * fpm, asasalt=None, gs=None):
+        ac.append(dict(gseast=gse, gsnorth=gsn, vs=vs, alt=alt, selalt=alt if selalt is None else selalt, apvs=apvs,
+                       asasalt=alt if asasalt is None else asasalt,
+                       gs=float(np.sqrt(gse * gse + gsn * gsn)) if gs is None else gs))
+        return len(ac) - 1
+
+    def pair(own, intr, qdr=30.0, dist=15000.0, tcpa=100.0, tlos=60.0):
+        pairs.append((own, intr, qdr, dist, tcpa, tlos))
+
+    # a pool of intruders: converging, level and climbing, above and below
+    pool = [aircraft(gse=-50.0 + 9.0 * k, gsn=120.0 - 7.0 * k, vs=(0.0, 4.0, -6.0, 0.0)[k % 4],
+                     alt=8000.0 + (0.0, 150.0, -200.0, 50.0, 900.0)[k % 5]) for k in range(13)]
+    intr = pool[0]                                      # gseast -50, gsnorth 120, level at 8000 m
+    noreso_idx = [pool[3], pool[8]]
+    # Rm < dist and dabsH >= dist: the second clause that skips the erratum
+    pair(aircraft(), intr, qdr=0.0, dist=20000.0, tcpa=-100.0)
+    pair(aircraft(), intr, qdr=0.0, dist=20000.0, tcpa=100.0)          # (both clauses hold: erratum)
+    # dist == Rm and one above
+    pair(aircraft(), intr, dist=Rm)
+    pair(aircraft(), intr, dist=up(Rm))
+    # tsolV == dtlookahead (|300 / 1|) and one above (300 / prev(1))
+    pair(aircraft(), aircraft(gse=-50.0, gsn=120.0, vs=1.0, alt=8300.0))
+    pair(aircraft(), aircraft(gse=-50.0, gsn=120.0, vs=dn(1.0), alt=8300.0))
+    pair(aircraft(vs=-1.0), aircraft(gse=-50.0, gsn=120.0, vs=0.0, alt=7700.0))
+    # vrel_z == 0 with |drel_z| above and below dhm
+    pair(aircraft(), aircraft(gse=-50.0, gsn=120.0, alt=8400.0))
+    pair(aircraft(), aircraft(gse=-50.0, gsn=120.0, alt=8100.0))
+    pair(aircraft(vs=3.0), aircraft(gse=-50.0, gsn=120.0, vs=3.0, alt=7600.0))
+    # dabsH == 10 exactly and one above (qdr 90: sin = 1; vrel = (-10, 0), tcpa = 1)
+    pair(aircraft(), aircraft(gse=-10.0, gsn=200.0), qdr=90.0, dist=20.0, tcpa=1.0)
+    pair(aircraft(), aircraft(gse=-10.0, gsn=200.0), qdr=90.0, dist=up(20.0), tcpa=1.0)
+    # |vs| == 0.1 and its neighbours in the priority rules, as ownship (c1 / c2's vs1) and as intruder (vs2)
+    climber, level = aircraft(gse=-50.0, gsn=120.0, vs=5.0, alt=8100.0), aircraft(gse=-50.0, gsn=120.0, alt=8100.0)
+    for v in (0.1, dn(0.1), up(0.1), -0.1, -dn(0.1), -up(0.1)):
+        a = aircraft(vs=v)
+        pair(a, climber)
+        pair(a, level)
+        b = aircraft(gse=-30.0, gsn=150.0, vs=v, alt=7900.0)
+        pair(aircraft(vs=5.0), b)
+        pair(aircraft(), b)
+    # tcpa = 0, -0.0, NaN, inf; tLOS = NaN, inf where tsolV takes it (vrel_z == 0, or tsolV > dtlookahead)
+    for t in (0.0, -0.0, np.nan, np.inf, -np.inf):
+        pair(aircraft(), intr, tcpa=t)
+    far_above = aircraft(gse=-50.0, gsn=120.0, vs=1.0, alt=9000.0)
+    for t in (np.nan, np.inf, 0.0):
+        pair(aircraft(), intr, tlos=t)
+        pair(aircraft(), far_above, tlos=t)
+    # a new ground speed exactly on vmin / vmax (no pairs: dv = 0, sqrt(v * v) = v)
+    aircraft(gse=vmin, gsn=0.0, gs=vmin)
+    aircraft(gse=0.0, gsn=-vmax, gs=vmax)
+    aircraft(gse=0.0, gsn=dn(vmin), gs=dn(vmin))
+    aircraft(gse=up(vmax), gsn=0.0, gs=up(vmax))
+    # signdvs == 0: level on its selected altitude; climbing at ap.vs towards it
+    pair(aircraft(vs=0.0), intr)
+    pair(aircraft(vs=1500.0 * fpm, selalt=9000.0), intr)
+    pair(aircraft(vs=-1500.0 * fpm, selalt=7000.0, asasalt=7500.0), intr)
+    # 9 and 13 pairs on one ownship: mvp_fold's remainder (9 = 2 x 4 + 1) and more than two trips
+    own9, own13 = aircraft(gse=20.0, gsn=180.0, alt=8050.0), aircraft(gse=-15.0, gsn=210.0, vs=2.0, alt=7950.0)
+    for k in range(9):
+        pair(own9, pool[k], qdr=20.0 * k, dist=12000.0 + 700.0 * k, tcpa=80.0 + 9.0 * k, tlos=40.0 + 3.0 * k)
+    for k in range(13):
+        pair(own13, pool[12 - k], qdr=355.0 - 25.0 * k, dist=11000.0 + 500.0 * k, tcpa=70.0 + 11.0 * k,
+             tlos=35.0 + 4.0 * k)
+    # ownships in resoofflst with pairs (one at vmax), one of them also meeting a noreso intruder
+    off1, off2 = aircraft(gse=0.0, gsn=vmax, gs=vmax), aircraft(gse=150.0, gsn=100.0, vs=-2.0)
+    pair(off1, intr)
+    pair(off1, pool[3])
+    pair(off2, pool[8])
+    pair(pool[3], off1, qdr=210.0)                      # a noreso aircraft avoids the others
+    resooff_idx = [off1, off2]
+
+    n = len(ac)
+    col = lambda k: np.array([a[k] for a in ac], dtype=np.float64)    # noqa: E731
+    gse, gsn = col('gseast'), col('gsnorth')
+    lat = 52.0 + 0.05 * (np.arange(n) // 8)
+    lon = 4.0 + 0.08 * (np.arange(n) % 8)
+    traf = T(lat, lon, col('alt'), np.degrees(np.arctan2(gse, gsn)) % 360.0, col('gs'), col('vs'))
+    extra = dict(gseast=gse, gsnorth=gsn, selalt=col('selalt'), apvs=col('apvs'), asasalt=col('asasalt'))
+    pairs.sort(key=lambda p: p[0])                      # row-major (stable: a row keeps its order)
+    ids = list(traf.id)
+    confpairs = [(ids[p[0]], ids[p[1]]) for p in pairs]
+    qdr, dist, tcpa, tlos = (np.array([p[k] for p in pairs], dtype=np.float64) for k in (2, 3, 4, 5))
+    return traf, extra, (confpairs, [], None, None, qdr, dist, tcpa, tlos), noreso_idx, resooff_idx
+
+
+def run_mvp_synth():
+    traf, extra, cdres, noreso_idx, resooff_idx = mvp_synth_case()
+    run_mvp('synth', traf, cdres, extra=extra, noreso_idx=noreso_idx, resooff_idx=resooff_idx)
+
+
 # ---------------------------------------------------------------- kinematics
 def kin_state(n, seed):
     rng = np.random.default_rng(seed)
@@ -369,8 +492,11 @@ def kin_state(n, seed):
     return s
 
 
-def run_kin(name, n, seed, dt, wind=None):
-    s = kin_state(n, seed)
+def run_kin(name, n, seed, dt, wind=None, state=None, prefix='kin_'):
+    """``state``: a hand-made input dict (kin_edge_state) instead of kin_state(n, seed)."""
+    s = kin_state(n, seed) if state is None else dict(state)
+    rownames = s.pop('row_name', None)
+    n = len(s['tas'])
     fake = types.SimpleNamespace()
     fake.pilot = types.SimpleNamespace(tas=s['ptas'].copy(), hdg=s['phdg'].copy(),
                                        alt=s['palt'].copy(), vs=s['pvs'].copy())
@@ -391,9 +517,10 @@ def run_kin(name, n, seed, dt, wind=None):
                      wvnorth=np.array(fake.wind.vnorth[0, :]), wveast=np.array(fake.wind.veast[0, :]))
     elif wind is not None:
         fake.wind.addpoint(52.0, 4.0, wind[0], wind[1])
-    RefTraffic.UpdateAirSpeed(fake, dt, 0.0)
-    RefTraffic.UpdateGroundSpeed(fake, dt)
-    RefTraffic.UpdatePosition(fake, dt)
+    with quiet(state is not None):
+        RefTraffic.UpdateAirSpeed(fake, dt, 0.0)
+        RefTraffic.UpdateGroundSpeed(fake, dt)
+        RefTraffic.UpdatePosition(fake, dt)
     keys = ('ax', 'delspd', 'tas', 'cas', 'M', 'hdg', 'swhdgsel', 'swaltsel', 'az', 'vs',
             'gsnorth', 'gseast', 'gs', 'trk', 'alt', 'lat', 'lon', 'coslat')
     ref = {k: np.asarray(getattr(fake, k)) for k in keys}
@@ -403,19 +530,140 @@ def run_kin(name, n, seed, dt, wind=None):
         vn, ve = fake.wind.getdata(s['lat'].copy(), s['lon'].copy(), s['alt'].copy())
         ovn, ove = okin.windfield_2d(s['lat'], s['lon'], field['wlat'], field['wlon'],
                                      field['wvnorth'], field['wveast'])
-        assert np.array_equal(ovn, vn) and np.array_equal(ove, ve), 'oracle != reference windfield'
+        assert np.array_equal(ovn, vn, equal_nan=True) and np.array_equal(ove, ve, equal_nan=True), \
+            'oracle != reference windfield'
     elif wind is not None:
         vn_, ve_ = fake.wind.getdata(np.array([0.0]), np.array([0.0]), np.array([0.0]))
         vn, ve = float(vn_[0]), float(ve_[0])
-    o = okin.step(s, dt, winddim=0 if wind is None else 1, windnorth=vn, windeast=ve)
+    with quiet(state is not None):
+        o = okin.step(s, dt, winddim=0 if wind is None else 1, windnorth=vn, windeast=ve)
     for k in keys:
         assert np.array_equal(o[k], ref[k], equal_nan=True), 'oracle != reference kin %s/%s' % (name, k)
+        if state is not None and ref[k].dtype == np.float64:   # the signs of zero as well
+            z0 = ref[k] == 0
+            assert np.array_equal(np.signbit(np.asarray(o[k])[z0]), np.signbit(ref[k][z0])), \
+                'oracle != reference kin %s/%s: sign of zero' % (name, k)
     out = dict(dt=dt, winddim=0 if wind is None else (2 if field else 1), windnorth=vn, windeast=ve, **s)
     if field is not None:
         out.update(field)
     out.update({'out_' + k: v for k, v in ref.items()})
-    np.savez_compressed(os.path.join(OUT, 'kin_%s.npz' % name), **out)
-    print('kin_%-17s N=%5d dt=%g wind=%s' % (name, n, dt, wind))
+    if rownames is not None:
+        out['row_name'] = np.array(rownames)
+    np.savez_compressed(os.path.join(OUT, '%s%s.npz' % (prefix, name)), **out)
+    print('%s%-17s N=%5d dt=%g wind=%s' % (prefix, name, n, dt, wind))
+
+
+# ---------------------------------------------------------------- kinematics, edge rows
+from tests.util import KIN_INPUTS                            # noqa: E402
+# rows whose reference output amplifies a 1-ulp difference of a library function
+# beyond the parity tolerance (DESIGN.md 3.6): they go to kinx_edge_illcond.npz
+KIN_ILLCOND = ('tas^2 overflows', '-tas^2 overflows')
+
+
+def kin_edge_rows(dt):
+    """[(name, {input: value})]: a base aircraft (52N 4E, 8000 m, 200 m/s, on its
+    targets) with one thing changed per row.  Threshold rows come in pairs -- on
+    the threshold (branch not taken) and one nextafter beyond it (taken) -- with
+    operands whose difference is exact."""
+    up = lambda x: float(np.nextafter(x, np.inf))        # noqa: E731
+    dn = lambda x: float(np.nextafter(x, -np.inf))       # noqa: E731
+    rows = [('base', {})]
+    add = lambda name, **kw: rows.append((name, kw))     # noqa: E731
+    # |delta_spd| > kts (traffic.py:428)
+    add('dspd == +kts', tas=0.0, ptas=kts)
+    add('dspd == +next(kts)', tas=0.0, ptas=up(kts))
+    add('dspd == -kts', tas=kts, ptas=0.0)
+    add('dspd == -next(kts)', tas=up(kts), ptas=0.0)
+    add('dspd small negative (ax = -0.0)', ptas=199.875)
+    add('dspd large', ptas=230.0)
+    add('dspd large negative', ptas=170.0)
+    # |delta_alt| > max(10 ft, |2 dt |vs||) (traffic.py:447): the 10 ft term
+    add('dalt == +10ft', alt=0.0, palt=10 * ft, pvs=5.0)
+    add('dalt == +next(10ft)', alt=0.0, palt=up(10 * ft), pvs=5.0)
+    add('dalt == -10ft', alt=10 * ft, palt=0.0, pvs=5.0)
+    add('dalt == -next(10ft)', alt=up(10 * ft), palt=0.0, pvs=5.0)
+    add('dalt small negative (vs = -0.0)', palt=7999.0, pvs=5.0)
+    # ... the vs term (vs = 64: 6.4 m at dt 0.05, 128 m at dt 1; at dt 0 the 10 ft term again)
+    for vs in (64.0, -64.0):
+        thr = float(np.maximum(10 * ft, np.abs(2 * dt * np.abs(vs))))
+        add('dalt == +2dt|vs|, vs %+g' % vs, alt=0.0, palt=thr, vs=vs, pvs=5.0)
+        add('dalt == +next(2dt|vs|), vs %+g' % vs, alt=0.0, palt=up(thr), vs=vs, pvs=5.0)
+        add('dalt == -2dt|vs|, vs %+g' % vs, alt=thr, palt=0.0, vs=vs, pvs=5.0)
+        add('dalt == -next(2dt|vs|), vs %+g' % vs, alt=up(thr), palt=0.0, vs=vs, pvs=5.0)
+    add('dalt +5: beyond 10ft, inside 2dt|vs| (dt 0.05)', palt=8005.0, vs=64.0, pvs=5.0)
+    add('dalt -5: beyond 10ft, inside 2dt|vs| (dt 0.05)', palt=7995.0, vs=-64.0, pvs=5.0)
+    # |delta_vs| > 300 fpm (traffic.py:451), vs = 0: delta_vs = +-|pvs|
+    add('dvs == +300fpm', palt=9000.0, pvs=300 * fpm)
+    add('dvs == +next(300fpm)', palt=9000.0, pvs=up(300 * fpm))
+    add('dvs == -300fpm', palt=7000.0, pvs=300 * fpm)
+    add('dvs == -next(300fpm)', palt=7000.0, pvs=up(300 * fpm))
+    add('dvs small negative (az = -0.0)', vs=0.5)
+    add('dvs small positive', vs=-0.5)
+    add('climb commanded', palt=9000.0, pvs=12.0)
+    add('descent commanded', palt=7000.0, pvs=-12.0, vs=-3.0)
+    # alt > 50 ft, the wind gate (traffic.py:466)
+    add('alt == 50ft', alt=50 * ft, palt=50 * ft)
+    add('alt == next(50ft)', alt=up(50 * ft), palt=up(50 * ft))
+    add('alt == 0', alt=0.0, palt=0.0)
+    add('alt negative', alt=-100.0, palt=-100.0)
+    # the tropopause of vatmos (aero.py:62-74)
+    for name, a in (('11000', 11000.0), ('prev(11000)', dn(11000.0)), ('next(11000)', up(11000.0)),
+                    ('20000', 20000.0)):
+        add('alt == ' + name, alt=a, palt=a)
+    # speed
+    add('tas < 0', tas=-50.0, ptas=-50.0)
+    add('0 < tas < eps', tas=0.005, ptas=0.005)
+    add('tas == eps', tas=0.01, ptas=0.01)
+    add('tas == 0, eps == 0', tas=0.0, ptas=0.0, eps=0.0)
+    add('tas == 0, eps == 0, turning', tas=0.0, ptas=0.0, eps=0.0, phdg=100.0)
+    add('bank == 0', bank=0.0, phdg=100.0)
+    add('tas subnormal', tas=5e-310, ptas=5e-310)
+    add('tas^2 overflows', tas=1e200, ptas=1e200)
+    add('-tas^2 overflows', tas=-1e200, ptas=-1e200)
+    # heading (hdg, phdg)
+    for h, ph in ((359.99, 0.01), (0.0, 180.0), (180.0, 0.0), (0.0, 360.0), (-0.0, 0.0), (720.5, 1.0),
+                  (-370.0, 350.0), (1e6 + 0.5, 0.0), (360.0 * 2 ** 30 + 90.5, 90.5), (360.0 * 2 ** 30 + 90.5, 0.0),
+                  (-(360.0 * 2 ** 31), 10.0), (45.0, 45.0 + 1e-9), (45.0, 50.0), (45.0, 40.0), (360.0, 0.0)):
+        add('hdg %r -> %r' % (h, ph), hdg=h, phdg=ph)
+    # position
+    for la in (90.0, -90.0, 89.9999999, up(90.0), 80.0, up(80.0), -85.0):
+        add('lat %r' % la, lat=la)
+    add('lon just below 180, eastbound', lon=dn(180.0), hdg=90.0, phdg=90.0)
+    add('lon == -180, westbound', lon=-180.0, hdg=270.0, phdg=270.0)
+    add('lon == 180, northbound', lon=180.0, hdg=0.0, phdg=0.0)
+    # the 2-D wind field: on a definition point (the 1 / eps weight), between points
+    add('on wind point 1', lat=WIND_FIELD[1][0], lon=WIND_FIELD[1][1])
+    add('on wind point 3', lat=WIND_FIELD[3][0], lon=WIND_FIELD[3][1])
+    add('between wind points', lat=52.5, lon=4.5)
+    # non-finite: one input at a time
+    for k in KIN_INPUTS:
+        for v in (np.nan, np.inf, -np.inf):
+            add('%s = %r' % (k, v), **{k: v})
+    add('pvs = inf, climb commanded', palt=9000.0, pvs=np.inf)          # target_vs inf: the isfinite(vs) arm
+    add('pvs = inf, vs = inf, climb commanded', palt=9000.0, pvs=np.inf, vs=np.inf)
+    add('pvs = inf, on altitude', pvs=np.inf)                           # 0 * inf
+    return rows
+
+
+def kin_edge_state(dt, illcond=False):
+    """The edge rows as run_kin's input dict (plus ``row_name``); ``illcond``
+    picks the KIN_ILLCOND rows instead of all the others."""
+    base = dict(tas=200.0, hdg=45.0, alt=8000.0, vs=0.0, lat=52.0, lon=4.0, ptas=200.0, phdg=45.0, palt=8000.0,
+                pvs=0.0, bank=float(np.radians(25.0)), eps=0.01, accel=0.5)
+    rows = [(nm_, kw) for nm_, kw in kin_edge_rows(dt) if (nm_ in KIN_ILLCOND) == illcond]
+    s = {k: np.array([kw.get(k, base[k]) for _, kw in rows], dtype=np.float64) for k in KIN_INPUTS}
+    s['row_name'] = [nm_ for nm_, _ in rows]
+    return s
+
+
+def run_kin_edge():
+    run_kin('edge_nowind', 0, 0, 0.05, state=kin_edge_state(0.05))
+    run_kin('edge_dt1', 0, 0, 1.0, state=kin_edge_state(1.0))
+    run_kin('edge_dt0', 0, 0, 0.0, state=kin_edge_state(0.0))
+    run_kin('edge_wind', 0, 0, 0.05, wind=(270.0, 25.0 * kts), state=kin_edge_state(0.05))
+    run_kin('edge_windfield', 0, 0, 0.05, wind=WIND_FIELD, state=kin_edge_state(0.05))
+    run_kin('edge_illcond', 0, 0, 0.05, wind=(270.0, 25.0 * kts), state=kin_edge_state(0.05, illcond=True),
+            prefix='kinx_')
 
 
 # ---------------------------------------------------------------- 3-D wind field
@@ -1790,6 +2038,12 @@ def main():
     if '--windfield-only' in sys.argv:
         run_kin('windfield1500', 1500, 34, 0.05, wind=WIND_FIELD)
         return
+    if '--kin-edge-only' in sys.argv:
+        run_kin_edge()
+        return
+    if '--mvp-synth-only' in sys.argv:
+        run_mvp_synth()
+        return
     if '--wind3d-only' in sys.argv:
         run_wind3d_all()
         return
@@ -1819,6 +2073,8 @@ def main():
     run_kin('nowind_dt1', 500, 32, 1.0)
     run_kin('wind1000', 1000, 33, 0.05, wind=(270.0, 25.0 * kts))
     run_kin('windfield1500', 1500, 34, 0.05, wind=WIND_FIELD)
+    run_kin_edge()
+    run_mvp_synth()
     run_wind3d_all()
     run_limits('openap2000', 2000, 71)
     run_perf('openap3000', 3000, 73)
