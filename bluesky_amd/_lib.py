@@ -316,7 +316,20 @@ SIGNATURES.update({
                                           ctypes.c_int64]),
     'bsa_sim_trails_drain': (ctypes.c_int, [_vp, ctypes.c_int64] + [_c_dp] * 5 + [_c_i32p, _c_i64p, _c_dp, _c_dp]),
     'bsa_sim_read_trails': (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_i64p]),
+    'bsa_adsb_draws': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
+                                      _c_u64p, _c_dp, _c_dp]),
+    'bsa_adsb_update': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_int, _c_dp,
+                                       ctypes.c_int, _c_dp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64] + [_c_dp] * 15),
+    'bsa_sim_set_adsb': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _c_dp, ctypes.c_double, ctypes.c_uint64,
+                                        ctypes.c_int, ctypes.c_double, _c_dp]),
+    'bsa_sim_read_adsb': (ctypes.c_int, [_vp] + [_c_dp] * 9 + [_c_i64p]),
+    'bsa_sim_adsb_call': (ctypes.c_int, [_vp, _c_i64p, _c_i64p]),
+    'bsa_sim_aborts': (ctypes.c_int, [_vp, _c_i64p]),
 })
+
+# the ADS-B picture's arrays beside lastupdate (adsbmodel.py:16-23), and bsa_adsb_update's draw modes
+ADSB_FIELDS = ('lat', 'lon', 'alt', 'trk', 'tas', 'gs', 'vs')
+ADSB_DRAWS = ('shared', 'per_aircraft')
 
 # one record of bsa_sim_exparea_poll (fp64 words, per exited aircraft)
 EXPAREA_RECORD = ('create_time', 'distance2D', 'distance3D', 'work', 'lat', 'lon', 'alt', 'tas', 'vs', 'hdg', 'active',
@@ -1344,6 +1357,79 @@ class Context:
         o.update(simt=simt.value, last_t=last_t.value, undrained=int(und.value))
         return o
 
+    # ---------------------------------------------------------------- ADS-B model
+    @staticmethod
+    def _adsb_mode(draws):
+        if draws not in ADSB_DRAWS:
+            raise ValueError("draws: 'shared' or 'per_aircraft'")
+        return ADSB_DRAWS.index(draws)
+
+    def adsb_draws(self, n, seed=0, call=0, first_index=0, stream=1, raw=True):
+        """bsa_adsb_draws: (Philox words (n, 4) uint64 or None, unit normals (n, 3), uniforms (n,)) of the indices
+        ``first_index .. first_index + n - 1`` of call ``call``; ``stream`` 1: the update's, 2: create's."""
+        n = int(n)
+        words = np.empty((n, 4), dtype=np.uint64) if raw else None
+        z, u = np.empty((n, 3)), np.empty(n)
+        self.check(self.lib.bsa_adsb_draws(self.h, n, int(seed), int(call), int(first_index), int(stream),
+                                           ptr(words, _c_u64p), ptr(z), ptr(u)), 'bsa_adsb_draws')
+        return words, z, u
+
+    def adsb_update(self, time, traf, picture, trunctime=0.0, noise=False, transerror=(1e-4, 100 * 0.3048),
+                    draws='shared', given=None, seed=0, call=0, first_index=0):
+        """bsa_adsb_update: one ADSB.update(time).  ``traf``: dict of ADSB_FIELDS (the traffic's), ``picture``: dict
+        of ``lastupdate`` and ADSB_FIELDS (the ADS-B object's).  ``given``: the unit normals to apply -- three values
+        (shared) or (3, n) lat / lon / alt (per aircraft) -- or None for those of (seed, call, index).  Returns the
+        new picture dict."""
+        st = [f64(traf[k]).ravel() for k in ADSB_FIELDS]
+        out = {k: f64(picture[k]).ravel().copy() for k in ('lastupdate',) + ADSB_FIELDS}
+        n = len(st[0])
+        if any(len(x) != n for x in st + list(out.values())):
+            raise ValueError('ADS-B arrays differ in length')
+        mode = self._adsb_mode(draws)
+        te = f64(transerror).ravel()
+        if len(te) != 2:
+            raise ValueError('transerror: [lat / lon degrees, altitude metres]')
+        z = None
+        if given is not None:
+            z = f64(given).ravel()
+            if len(z) != (3 * n if mode else 3):
+                raise ValueError('given draws: 3 values (shared) or 3 x n (per aircraft)')
+        self.check(self.lib.bsa_adsb_update(self.h, n, float(time), float(trunctime), int(bool(noise)), ptr(te), mode,
+                                            ptr(z), int(seed), int(call), int(first_index), *[ptr(x) for x in st],
+                                            ptr(out['lastupdate']), *[ptr(out[k]) for k in ADSB_FIELDS]),
+                   'bsa_adsb_update')
+        return out
+
+    def sim_set_adsb(self, on=True, noise=False, transerror=(1e-4, 100 * 0.3048), trunctime=0.0, seed=0,
+                     draws='shared', simt=0.0, lastupdate=None):
+        """bsa_sim_set_adsb: ADSB.update as a stage of every resident step.  ``lastupdate``: a scalar or n values
+        (None: 0), read when the stage is switched on."""
+        te = f64(transerror).ravel()
+        if len(te) != 2:
+            raise ValueError('transerror: [lat / lon degrees, altitude metres]')
+        last = None
+        if on:
+            last = np.ascontiguousarray(np.broadcast_to(f64(0.0 if lastupdate is None else lastupdate), (self.n,))).copy()
+        self.check(self.lib.bsa_sim_set_adsb(self.h, int(bool(on)), int(bool(noise)), ptr(te), float(trunctime), int(seed),
+                                             self._adsb_mode(draws), float(simt), ptr(last)), 'bsa_sim_set_adsb')
+
+    def sim_read_adsb(self):
+        """bsa_sim_read_adsb: dict of ``lastupdate`` and ADSB_FIELDS of this rank's rows (full-n arrays, other rows 0),
+        ``simt`` (the time of the next step's update) and ``call``."""
+        o = {k: np.zeros(self.n) for k in ('lastupdate',) + ADSB_FIELDS}
+        simt, call = ctypes.c_double(0.0), ctypes.c_int64(0)
+        self.check(self.lib.bsa_sim_read_adsb(self.h, *[ptr(o[k]) for k in ('lastupdate',) + ADSB_FIELDS],
+                                              ctypes.byref(simt), ctypes.byref(call)), 'bsa_sim_read_adsb')
+        o.update(simt=simt.value, call=int(call.value))
+        return o
+
+    def sim_adsb_call(self, set_to=None):
+        """bsa_sim_adsb_call: the call number of the next noisy update (after setting it, if given)."""
+        out = ctypes.c_int64(0)
+        new = None if set_to is None else ctypes.byref(ctypes.c_int64(int(set_to)))
+        self.check(self.lib.bsa_sim_adsb_call(self.h, ctypes.byref(out), new), 'bsa_sim_adsb_call')
+        return out.value
+
     def sim_cd(self):
         """bsa_sim_cd: one CD call (detect -> resolver -> bookkeeping) without kinematics."""
         self.gen += 1
@@ -1390,6 +1476,12 @@ class Context:
         self.check(self.lib.bsa_sim_stats(self.h, ptr(v, _c_i64p)), 'bsa_sim_stats')
         return dict(steps=int(v[0]), cd_calls=int(v[1]), n_conf=int(v[2]), n_los=int(v[3]),
                     row_begin=int(v[4]), row_end=int(v[5]))
+
+    def sim_aborts(self):
+        """bsa_sim_aborts: batches aborted and re-run since sim_init."""
+        out = ctypes.c_int64(0)
+        self.check(self.lib.bsa_sim_aborts(self.h, ctypes.byref(out)), 'bsa_sim_aborts')
+        return out.value
 
     def set_row_bucket(self, width):
         """bsa_set_row_bucket: K2's per-row bucket width (0 = scatter into segments)."""

@@ -244,6 +244,9 @@ struct StepClocks {
   int64_t area_ctr = 0;                    // experiment area (3.30): steps since bsa_sim_set_exparea
   double trail_simt = 0.0, trail_last = 0.0;  // trails (3.31): the simt the next step's traf.update is called with,
                                               // ... and the one the last step's was
+  double adsb_simt = 0.0;                  // ADS-B (3.32): the simt the next step's adsb.update is called with,
+  int64_t adsb_call = 0;                   // ... the call number of its draws (+ 1 per step with noise on),
+  int adsb_cur = 0;                        // ... and which lastupdate buffer it reads (it writes the other)
 };
 
 struct Ctx {
@@ -517,6 +520,7 @@ struct Ctx {
   std::vector<int32_t> cond_idx_h, cond_type_h;
   std::vector<double> cond_tgt_h;
   bool sim_cond = false;
+  int64_t sim_aborts = 0;  // batches aborted and re-run since bsa_sim_init (batch_rollback; bsa_sim_aborts)
   int64_t steps_last = 0, batch_steps0 = 0;  // (the step count at the running batch's begin: StepPlan::cond_tag)
 
   // The experiment area (bsa_exparea.hip).  xa_stage: bsa_exparea_update's arrays.  In the resident
@@ -540,6 +544,16 @@ struct Ctx {
   bool sim_trails = false, tr_active = false;
   double tr_dt = 10.0;
   int64_t tr_cap = 0, tr_max = 0, tr_undrained = 0, tr_demand = 0;
+
+  // The ADS-B model (bsa_adsb.hip).  adsb_stage: bsa_adsb_update's / bsa_adsb_draws' arrays.  In the
+  // resident step (bsa_sim_set_adsb): per aircraft (kSimArrays) the picture lat lon alt trk tas gs vs and two
+  // lastupdate buffers -- a step reads s_adlast<clk.adsb_cur> and writes the other for all its rows, so an aborted
+  // step leaves the one it read as it was.  Its clocks: clk.adsb_*
+  DevBuf ad_shared;  // the step's shared draw: three unit normals, written by a one-lane launch in front of k_adsb
+  DevBuf adsb_stage, s_adlast0, s_adlast1, s_adlat, s_adlon, s_adalt, s_adtrk, s_adtas, s_adgs, s_advs;
+  bool sim_adsb = false, ad_noise = false, ad_per_ac = false;
+  double ad_sigma[2] = {1e-4, 30.48}, ad_trunc = 0.0;
+  unsigned long long ad_seed = 0;
 
   // standalone geo matrices (bsa_geo.hip)
   DevBuf geo_in, geo_pts, geo_out;
@@ -612,7 +626,7 @@ inline void *ptr_at(const void *strct, int k) { return ((void *const *)strct)[k]
 // it (bsa_traffic.hip: per_aircraft), bsa_sim_init allocates its kSimAlways rows
 // guard: kSimAlways allocated by bsa_sim_init; kSimDetect the last detect's per-row outputs (the detect's to
 // allocate); kSimOnUse once allocated (the reso lists); the others while Ctx::sim_<switch> is on
-enum SimGuard { kSimAlways, kSimDetect, kSimOnUse, kSimLimits, kSimPerf, kSimForces, kSimFms, kSimAtmos, kSimSectors, kSimExparea, kSimTrails };
+enum SimGuard { kSimAlways, kSimDetect, kSimOnUse, kSimLimits, kSimPerf, kSimForces, kSimFms, kSimAtmos, kSimSectors, kSimExparea, kSimTrails, kSimAdsb };
 struct SimArray {
   BufRef buf;
   int esz, count;  // element size; sub-arrays of length n in the buffer
@@ -652,6 +666,11 @@ inline const SimArray kSimArrays[] = {
     {{&Ctx::s_xctime}, 8, 1, false, kSimExparea},    {{&Ctx::s_xflag}, 1, 1, false, kSimExparea},
     {{&Ctx::s_tlat}, 8, 1, false, kSimTrails},       {{&Ctx::s_tlon}, 8, 1, false, kSimTrails},
     {{&Ctx::s_ttim}, 8, 1, false, kSimTrails},
+    {{&Ctx::s_adlast0}, 8, 1, false, kSimAdsb},      {{&Ctx::s_adlast1}, 8, 1, false, kSimAdsb},
+    {{&Ctx::s_adlat}, 8, 1, false, kSimAdsb},        {{&Ctx::s_adlon}, 8, 1, false, kSimAdsb},
+    {{&Ctx::s_adalt}, 8, 1, false, kSimAdsb},        {{&Ctx::s_adtrk}, 8, 1, false, kSimAdsb},
+    {{&Ctx::s_adtas}, 8, 1, false, kSimAdsb},        {{&Ctx::s_adgs}, 8, 1, false, kSimAdsb},
+    {{&Ctx::s_advs}, 8, 1, false, kSimAdsb},
 };
 // is the array part of the sim now (to be carried through a delete / create)?
 inline bool sim_array_on(Ctx *c, const SimArray &a) {
@@ -665,6 +684,7 @@ inline bool sim_array_on(Ctx *c, const SimArray &a) {
     case kSimSectors: return c->sim_sect;
     case kSimExparea: return c->sim_exparea;
     case kSimTrails: return c->sim_trails;
+    case kSimAdsb: return c->sim_adsb;
     default: return true;
   }
 }
@@ -789,6 +809,14 @@ int trails_sim_launch(Ctx *c, double t, unsigned tag);
 int trails_reserve(Ctx *c, int64_t nsteps);
 int trails_created(Ctx *c, int64_t n, int64_t m, const double *lat, const double *lon);
 void trails_off(Ctx *c);
+
+// The ADS-B model of the step (bsa_adsb.hip): ADSB.update(simt) on the state the previous step left,
+// this rank's rows, after a geovector application and before the FMS stage (traffic.py:392); t: clk.adsb_simt before
+// the step's advance.  adsb_created: ADSB.create for the m aircraft bsa_sim_create appended after the first n (s:
+// their state, host).  adsb_off: off, the arrays released, the clocks back at 0
+int adsb_sim_launch(Ctx *c, double t);
+int adsb_created(Ctx *c, int64_t n, int64_t m, const bsa_sim_state *s);
+void adsb_off(Ctx *c);
 
 // Sector occupancy (bsa_area.hip): sect_sim_launch after the last stage of a step whose StepPlan::sect_pass is
 // set (clk.sect_ctr + 1 a multiple of the cadence); sect_note_deleted by bsa_sim_delete before anything moves;

@@ -155,6 +155,7 @@ enum class Change {
   SetSymSweep,        // bsa_set_symmetric_sweep
   WindField,          // bsa_set_windfield3d
   Turbulence,         // bsa_sim_set_turbulence: on / off, sd, seed
+  Adsb,               // bsa_sim_set_adsb: on / off and every setting
   Count
 };
 struct Drops {
@@ -178,6 +179,8 @@ constexpr bool drop = true, stays = false;
 //      prepared records), on several the own-tile K0b checks every record against the list's snapshot.  Switching
 //      it on, off or to other sd / seed drops what was made under the other setting's drift: the prepared
 //      records' budget check and HK's predictions assumed it
+//  (a) the ADS-B stage reads the traffic state and writes only its own picture and lastupdate arrays, which no detect
+//      reads (the step's detect takes the true state as intruder): nothing kept depends on it or on its settings
 //  (n) the steps enqueued behind the stop became no-ops, but their detects ran -- on the state the stop left, with
 //      the host's later decisions: they re-armed the candidate list, the tile-pair list and its snapshot, the zeroed
 //      counters and the HK history for steps that never happened, and K4' prepared no records for them.  All of it
@@ -206,6 +209,7 @@ constexpr Drops kDrops[(int)Change::Count] = {
     /* SetSymSweep       */ {stays, stays, drop, stays, stays, stays},  // p i . i i b
     /* WindField         */ {stays, stays, stays, stays, stays, stays}, // w w w w w w
     /* Turbulence        */ {stays, drop, drop, drop, stays, drop},     // p t t t z t
+    /* Adsb              */ {stays, stays, stays, stays, stays, stays}, // a a a a a a
 };
 
 }  // namespace bsa

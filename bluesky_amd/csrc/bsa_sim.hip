@@ -211,7 +211,7 @@ void sim_release(Ctx *c) {
   // not per aircraft: staging, control words, tables, the FMS undo set, K2 + K4' double buffers
   DevBuf *rest[] = {&c->red, &c->g_send, &c->g_recv, &c->pg_send, &c->pg_recv, &c->sim_ctl, &c->s_ptab, &c->s_ftab,
                     &c->f_const, &c->s_fmsrows, &c->s_fmsur, &c->s_fmsuf, &c->s_fmsui, &c->gv_tab, &c->gv_shapes, &c->gv_undo,
-                    &c->gv_cnt, &c->xfer_stage, &c->lbyidx, &c->xa_ws, &c->xa_rec, &c->tr_stage, &c->tr_seg, &c->tr_ws,
+                    &c->gv_cnt, &c->xfer_stage, &c->lbyidx, &c->xa_ws, &c->xa_rec, &c->tr_stage, &c->tr_seg, &c->tr_ws, &c->adsb_stage,
                     &c->fetch_stage, &c->tpr_snap, &c->tpr_ctl, &c->nx_alt, &c->nx_vs, &c->nx_gse, &c->nx_gsn};
   for (auto *b : rest) release(*b);
   bk_release(c);
@@ -337,6 +337,10 @@ struct StepPlan {
   // cond_tag; trail_t: clk.trail_simt at the step's start, the simt traf.update was called with
   bool trails;
   double trail_t;
+  // the ADS-B model (3.32): ADSB.update(adsb_t) on the state the previous step left, before the FMS stage;
+  // adsb_t: clk.adsb_simt at the step's start
+  bool adsb;
+  double adsb_t;
 };
 static StepPlan step_decide(const Ctx *c, bool rerun_first) {
   const DetectEnv &env = detect_env();
@@ -359,6 +363,8 @@ static StepPlan step_decide(const Ctx *c, bool rerun_first) {
   sp.area_pass = exparea_passes_at(c);
   sp.trails = c->sim_trails;
   sp.trail_t = k.trail_simt;
+  sp.adsb = c->sim_adsb;
+  sp.adsb_t = k.adsb_simt;
   return sp;
 }
 
@@ -375,6 +381,10 @@ static void step_advance(Ctx *c, const StepPlan &sp) {
   if (c->sim_sect) k.sect_ctr++;
   if (c->sim_exparea) k.area_ctr++;
   if (c->sim_trails) k.trail_last = k.trail_simt, k.trail_simt += c->simp.simdt;  // simt += simdt (simulation.py), accumulated as there
+  if (c->sim_adsb) {  // simt as the trails' clock; the lastupdate buffers change roles; a call number per noisy update
+    k.adsb_simt += c->simp.simdt, k.adsb_cur ^= 1;
+    if (c->ad_noise) k.adsb_call++;
+  }
   k.steps++;
 }
 
@@ -416,6 +426,7 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const BatchCtl &ctl) {
   // every per-detect buffer (an aborted K2 wrote no inconf / tcpamax); an aborted K4' prepared nothing, and the HK
   // decisions of the aborted steps never took effect
   invalidate(c, Change::BatchAborted);
+  c->sim_aborts++;
   const int64_t done = (int64_t)ctl.steps_done;
   // the clocks of the completed steps, replayed from the batch base with each step's own plan (a CD call alone
   // completes no step: its count goes back to the base, the re-run counts it)
@@ -437,7 +448,12 @@ static int batch_rollback(Ctx *c, const BatchBase &base, const BatchCtl &ctl) {
     // clock makes the re-run count the pass once.
     // Trails: an aborted step's pass wrote nothing, since the abort is raised in the step's detect -- its count
     // and emit launches returned behind the sticky word and left the running total as it was: nothing to undo,
-    // and the replayed trail_simt hands the re-run the same t
+    // and the replayed trail_simt hands the re-run the same t.
+    // ADS-B: the stage runs BEFORE the step's detect, so the aborted step's launch did run.  Two lastupdate buffers:
+    // it read the one clk.adsb_cur names and wrote the other for all its rows, and the replayed clock names the one
+    // it read again, untouched; its picture writes are a pure function of that buffer, the state, adsb_simt and
+    // adsb_call, all as they were, so the re-run writes the same values again.  Later launches returned behind the
+    // sticky word.  Nothing to undo, no lastupdate += trunctime applied twice
     const StepPlan sp = step_decide(c, false);
     if (sp.fms_tick && fms_sim_restore(c)) return -1;
     if (sp.gv_apply && geovec_sim_restore(c)) return -1;
@@ -617,6 +633,8 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
   // geovectoring is the plugin's preupdate (tools/plugin.py:161-169): the first launch on the step's stream, so
   // that Autopilot.update already reads the limited selspd / selvs / selalt / ap.trk
   if (sp.gv_apply && geovec_sim_launch(c)) return -1;
+  // adsb.update(simt) (traffic.py:392): the broadcast picture of the state the previous step left
+  if (sp.adsb && adsb_sim_launch(c, sp.adsb_t)) return -1;
   // (forces and FMS read the pre-step state)
   if (c->sim_forces && forces_sim_launch(c, sp.commit_fuel)) return -1;
   if (c->sim_fms && fms_sim_launch(c, sp.fms_tick)) return -1;  // Autopilot.update (bsa_fms.hip)
@@ -656,7 +674,7 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
 }
 
 // every stage with a launch of its own, off (fms_off takes recovery and the geovectors with it): a new sim
-static void stages_off(Ctx *c) { forces_off(c), fms_off(c), turb_off(c), sect_off(c), cond_off(c), exparea_off(c), trails_off(c); }
+static void stages_off(Ctx *c) { forces_off(c), fms_off(c), turb_off(c), sect_off(c), cond_off(c), exparea_off(c), trails_off(c), adsb_off(c); }
 
 }  // namespace bsa
 
@@ -714,6 +732,7 @@ int bsa_sim_init(bsa_ctx *cc, int64_t n, const bsa_sim_state *s, const bsa_sim_p
   c->halo_mode = c->nranks > 1 ? 1 : 0;
   if (bsa::halo_init_caps(c)) return -1;
   c->clk = bsa::StepClocks{};
+  c->sim_aborts = 0;
   c->sim_last_conf = c->sim_last_los = 0;
   c->sim_gathered = true;
   bsa::invalidate(c, bsa::Change::NewSim);
@@ -774,6 +793,14 @@ int bsa_sim_step(bsa_ctx *cc, int nsteps) {
     if (bsa::batch_rollback(c, base, ctl)) return -1;
   }
   c->steps_last = c->clk.steps - start;
+  return 0;
+}
+
+int bsa_sim_aborts(bsa_ctx *cc, int64_t *aborts) {
+  Ctx *c = (Ctx *)cc;
+  if (!c) return -1;
+  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_aborts before bsa_sim_init");
+  if (aborts) *aborts = c->sim_aborts;
   return 0;
 }
 

@@ -476,6 +476,7 @@ int bsa_sim_create(bsa_ctx *cc, int64_t m, const bsa_sim_state *s) {
   BSA_HIP(c, hipStreamSynchronize(c->stream));
   if (bsa::exparea_created(c, n, m, (const double *)bsa::ptr_at(s, 2))) return -1;  // Area.create
   if (bsa::trails_created(c, n, m, (const double *)bsa::ptr_at(s, 0), (const double *)bsa::ptr_at(s, 1))) return -1;  // Trails.create (3.31)
+  if (bsa::adsb_created(c, n, m, s)) return -1;  // ADSB.create (3.32)
   // new aircraft have no resopairs and were in no previous pair set: empty CSR rows
   std::vector<int> ident((size_t)n);
   for (int64_t k = 0; k < n; ++k) ident[(size_t)k] = (int)k;

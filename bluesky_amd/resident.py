@@ -389,6 +389,34 @@ class ResidentSim:
         step's) and ``undrained`` (bsa_sim_read_trails)."""
         return self.ctx.sim_read_trails()
 
+    def set_adsb(self, on=True, noise=False, transerror=(1e-4, 100 * FT), trunctime=0.0, seed=0, draws='shared',
+                 simt=0.0, lastupdate=None):
+        """ADSB.update (traffic/adsbmodel.py:44-59) as a stage of every step, where Traffic.update runs it: on
+        the state the previous step left, before the autopilot (bsa_sim_set_adsb).  An aircraft with
+        ``lastupdate + trunctime < simt`` takes the current ``trk tas gs vs`` and ``lat lon alt`` -- with
+        ``noise`` plus a normal of ``transerror`` ([deg] for lat / lon, [m] for alt) -- into the picture, and
+        its ``lastupdate`` grows by ``trunctime``.  ``simt``: the sim time of the next step (the stage's clock
+        then accumulates ``simdt``).  ``draws='shared'`` restates the reference, which draws one normal per
+        quantity per call for all updated aircraft; ``'per_aircraft'`` gives each its own.  The draws are
+        build-defined (``bluesky_amd.adsb.draws``): a function of ``seed``, the call number (``adsb_call``) and,
+        per aircraft, the aircraft's current index, so a run repeats bitwise whatever the batching or the rank
+        count.  The first call starts the picture at the current state -- ``vs`` too, where the reference's
+        ``create`` leaves 0 -- and ``lastupdate`` at ``lastupdate`` (a scalar or one value per aircraft, default
+        0); later calls change the settings only.  ``create`` gives new aircraft ``lastupdate = -trunctime *
+        u``, the picture from their state and ``vs = 0``.  ``on=False`` switches the stage off and frees its
+        arrays.  The step's own detect still reads the true state.  Sharded: every rank calls it alike."""
+        self.ctx.sim_set_adsb(on, noise, transerror, trunctime, seed, draws, simt, lastupdate)
+
+    def read_adsb(self):
+        """dict of ``lastupdate lat lon alt trk tas gs vs`` of this rank's rows (by aircraft index; other rows
+        0), ``simt`` (the time of the next step's update) and ``call`` (bsa_sim_read_adsb)."""
+        return self.ctx.sim_read_adsb()
+
+    def adsb_call(self, set_to=None):
+        """The call number of the next noisy update's draws (0 when switched on, + 1 per step while noise is
+        on); ``set_to`` continues another sim's stream."""
+        return self.ctx.sim_adsb_call(set_to)
+
     def set_geovectors(self, geovecs, every=1):
         """Geovectoring inside the step (plugins/geovector.py:76-128; bsa_sim_set_geovectors):
         ``geovecs`` is the plugin's list of ``[area, gsmin, gsmax, trkmin, trkmax, vsmin, vsmax]``
@@ -412,6 +440,11 @@ class ResidentSim:
 
     def stats(self):
         return self.ctx.sim_stats()
+
+    def aborts(self):
+        """Batches that aborted (a buffer overflowed, a kept list went stale) and were re-run from the aborted
+        step, since the sim was made (bsa_sim_aborts)."""
+        return self.ctx.sim_aborts()
 
     def asas_stats(self):
         return self.ctx.sim_asas_stats()

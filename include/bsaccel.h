@@ -882,6 +882,58 @@ int bsa_sim_trails_drain(bsa_ctx *ctx, int64_t cap, double *lat0, double *lon0, 
  * step's) and the undrained segment count as of the last batch or drain. */
 int bsa_sim_read_trails(bsa_ctx *ctx, double *lastlat, double *lastlon, double *lasttim, double *simt,
                         double *last_t, int64_t *undrained);
+/* ---------------------------------------------------------------- ADS-B model
+ * traffic/adsbmodel.py: ADSB.update(time).  An aircraft is due when
+ * lastupdate + trunctime < time -- strict, false for a NaN.  For a due aircraft
+ * the picture's trk, tas, gs, vs are copies of the traffic's; lat, lon, alt are
+ * copies too, or with noise x + (0 + sigma z): sigma = transerror[0] [deg] for
+ * lat and lon, transerror[1] [m] for alt, z a unit normal; two roundings, as
+ * numpy's.  Then lastupdate += trunctime (not = time).  Nothing of an aircraft
+ * that is not due is written.
+ * The normals are build-defined: Philox4x64-10, counter {index, call, stream,
+ * 0}, key {seed, 0}; stream 1 gives the update's three normals (lat, lon, alt;
+ * the Box-Muller pairs of bsa_turb_draws), stream 2 create's uniform (word 0);
+ * stream 0 is turbulence's.  per_aircraft == 0 (the reference: it draws ONE
+ * normal per quantity per call, shared by every due aircraft): index 0.
+ * per_aircraft == 1: the aircraft's index, first_index + its position here.
+ * bsa_adsb_draws: the words (4 n), normals (3 n) and uniforms (n) of indices
+ * first_index .. of `call` in stream 1 or 2; any output may be NULL.
+ * bsa_adsb_update: one update over host arrays; lastupdate and the seven
+ * picture arrays are updated in place.  draws: the unit normals to apply
+ * instead -- 3 values (shared) or lat | lon | alt, n each (per aircraft) -- or
+ * NULL.  transerror and trunctime must be finite and >= 0. */
+int bsa_adsb_draws(bsa_ctx *ctx, int64_t n, uint64_t seed, uint64_t call, uint64_t first_index, int stream,
+                   uint64_t *raw4n, double *z3n, double *un);
+int bsa_adsb_update(bsa_ctx *ctx, int64_t n, double time, double trunctime, int noise, const double *transerror,
+                    int per_aircraft, const double *draws, uint64_t seed, uint64_t call, uint64_t first_index,
+                    const double *lat, const double *lon, const double *alt, const double *trk, const double *tas,
+                    const double *gs, const double *vs, double *lastupdate, double *alat, double *alon, double *aalt,
+                    double *atrk, double *atas, double *ags, double *avs);
+/* The same update as a stage of every resident step, where Traffic.update runs
+ * it (traffic.py:392): on the state the previous step left, after a geovector
+ * application and before the FMS stage, on this rank's rows.  time is the
+ * stage's clock: `simt` here, + simdt per step, accumulated in fp64.  The call
+ * number of the draws starts at 0 and grows by one per step with noise on.
+ * The first call with on != 0 starts the picture at the current state -- vs
+ * too, where ADSB.create leaves 0 -- and lastupdate at lastupdate[] (n values
+ * by aircraft index); later calls change noise, transerror, trunctime, seed and
+ * per_aircraft only (lastupdate may be NULL).  on == 0 switches the stage off
+ * and frees its arrays; off, a step launches nothing for it.  bsa_sim_delete
+ * and bsa_sim_create carry the arrays; a new aircraft starts with lastupdate =
+ * -trunctime u (u: stream 2 at its index and the current call number), the
+ * picture at its state and vs 0.  An aborted batch repeats nothing: the stage
+ * keeps two lastupdate buffers, reads one and writes the other.  Sharded: every
+ * rank calls it alike; per-aircraft draws depend on the aircraft index only. */
+int bsa_sim_set_adsb(bsa_ctx *ctx, int on, int noise, const double *transerror, double trunctime, uint64_t seed,
+                     int per_aircraft, double simt, const double *lastupdate);
+/* This rank's rows of the arrays, by aircraft index in n-long arrays (other
+ * entries untouched; any may be NULL), the stage's clock (*simt: the time of the
+ * next step's update) and the call number of its draws. */
+int bsa_sim_read_adsb(bsa_ctx *ctx, double *lastupdate, double *lat, double *lon, double *alt, double *trk, double *tas,
+                      double *gs, double *vs, double *simt, int64_t *call);
+/* The call number of the next noisy update (*call, after setting it from
+ * *set_to if given; either may be NULL). */
+int bsa_sim_adsb_call(bsa_ctx *ctx, int64_t *call, const int64_t *set_to);
 /* ---------------------------------------------------------------- geovectoring
  * plugins/geovector.py:76-128: per area an allowed interval for ground speed,
  * track and vertical speed.  The geovectors are an ordered list; each is
@@ -990,6 +1042,9 @@ int bsa_sim_read(bsa_ctx *ctx, bsa_sim_out *o);
  * CD call (this rank's rows), [4] this rank's row_begin, [5] row_end (its home
  * range: row_end - row_begin rows; (0, n) with one rank). */
 int bsa_sim_stats(bsa_ctx *ctx, int64_t *out6);
+/* Batches of bsa_sim_step / bsa_sim_cd that aborted (a buffer overflowed, a kept
+ * list went stale) and were re-run from the aborted step, since bsa_sim_init. */
+int bsa_sim_aborts(bsa_ctx *ctx, int64_t *aborts);
 /* The aircraft indices of this rank's rows, ascending (row_end - row_begin
  * entries): the rows of bsa_sim_acdata_poll's arrays, of bsa_fetch_pairs'
  * inconf / tcpamax after resident steps, and of bsa_sim_read_perf. */

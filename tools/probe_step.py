@@ -7,7 +7,7 @@ untimed ones (the device at steady clocks, as bench.py's --settle).  Collectives
 (box all-gather, halo send / recv, gate all-reduce) are excluded: they need
 the 8-GPU node.  Prints every rank's ms per step and the slowest.
 Usage: python tools/probe_step.py [WORKLOAD [R [STEPS [RANK [SETTLE]]]]] [--perf | --forces] [--fms]
-[--resume-nav] [--recover] [--turb] [--cond] [--exparea]  (RANK:
+[--resume-nav] [--recover] [--turb] [--cond] [--exparea] [--adsb | --adsb-shared | --adsb-nonoise]  (RANK:
 that rank of R only, -1 all; SETTLE default 200; --perf: OpenAP phase / envelope in the step,
 --forces: also its drag / thrust / fuel-flow launch; --fms: Autopilot.update in the
 step, every aircraft on a generated 4-waypoint route; --resume-nav: ASAS.update's
@@ -16,7 +16,10 @@ bookkeeping and ResumeNav in the CD step; --recover: waypoint recovery after Res
 as the step's last stage, DESIGN.md 3.25: k_sim_turb and the next detect's own K0b in place of K4''s records;
 --cond: 10 000 conditional commands of both types that never fire, DESIGN.md 3.29: k_sim_cond every step;
 --exparea: the experiment area on a box around all the traffic that nobody leaves, TAXI OFF far below, a pass
-every step, DESIGN.md 3.30: k_sim_exparea every step)"""
+every step, DESIGN.md 3.30: k_sim_exparea every step; --adsb: the ADS-B model with trunctime 0, so that every aircraft
+updates in every step, noise on with per-aircraft draws, DESIGN.md 3.32: k_adsb every step at its most expensive;
+--adsb-shared: the same with the default shared draw, one one-lane launch in front of k_adsb; --adsb-nonoise: the same
+without noise, the kernel as a pure copy)"""
 import json
 import os
 import sys
@@ -53,8 +56,10 @@ def main():
     turb = '--turb' in sys.argv              # Turbulence.Woosh in the step (bsa_sim_set_turbulence)
     with_cond = '--cond' in sys.argv         # conditional commands in the step (bsa_sim_set_conditions), none firing
     with_area = '--exparea' in sys.argv      # the experiment area in the step (bsa_sim_set_exparea), nobody leaving
+    adsb_mode = ('noise' if '--adsb' in sys.argv else 'shared' if '--adsb-shared' in sys.argv else
+                 'nonoise' if '--adsb-nonoise' in sys.argv else None)          # (bsa_sim_set_adsb)
     sys.argv = [a for a in sys.argv if a not in ('--forces', '--perf', '--fms', '--recover', '--resume-nav', '--turb',
-                                                 '--cond', '--exparea')]
+                                                 '--cond', '--exparea', '--adsb', '--adsb-shared', '--adsb-nonoise')]
     name = sys.argv[1] if len(sys.argv) > 1 else 'global1m'
     R = int(sys.argv[2]) if len(sys.argv) > 2 else 8
     steps = int(sys.argv[3]) if len(sys.argv) > 3 else 40
@@ -86,7 +91,10 @@ def main():
     if with_area:
         sim.set_areas({'ALL': ('BOX', [-89.9, -179.9, 89.9, 179.9], 1e9, -1e9)})
         sim.set_exparea('ALL', dt=0.5, every=1, taxi=False, taxialt=-1e9)
-    out = dict(perf=with_perf, forces=forces, fms=with_fms, resume_nav=resume_nav, recover=recover, turb=turb, cond=with_cond,
+    if adsb_mode:
+        sim.set_adsb(True, noise=adsb_mode != 'nonoise', trunctime=0.0, seed=5,
+                     draws='shared' if adsb_mode == 'shared' else 'per_aircraft', simt=1.0)
+    out = dict(adsb=adsb_mode, perf=with_perf, forces=forces, fms=with_fms, resume_nav=resume_nav, recover=recover, turb=turb, cond=with_cond,
                exparea=with_area)
     for ranks in sorted({1, R}) if only is None else [R]:
         per = []
