@@ -229,7 +229,16 @@ class FmsState(ctypes.Structure):
     _fields_ = [(k, _c_dp) for k in FMS_REALS] + [(k, _c_u8p) for k in FMS_FLAGS]
 
 
+class SimCreateExtra(ctypes.Structure):
+    """bsa_sim_create_extra (include/bsaccel.h)."""
+    _fields_ = ([(k, _c_dp) for k in ('hmax', 'vmin', 'vmax', 'vsmin', 'vsmax', 'axmax')] +
+                [('type_idx', _c_i32p), ('mass', _c_dp), ('nrows', ctypes.c_int64), ('route_rows', _c_dp),
+                 ('rt_off', _c_i32p), ('rt_n', _c_i32p), ('iactwp', _c_i32p), ('st', ctypes.POINTER(FmsState))])
+
+
 SIGNATURES.update({
+    'bsa_sim_create_with': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.POINTER(SimState),
+                                           ctypes.POINTER(SimCreateExtra)]),
     'bsa_fms_update': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _c_dp, _c_i32p, _c_i32p, _c_i32p] +
                        [_c_dp] * 8 + [ctypes.POINTER(FmsState)] + [_c_dp] * 5),
     'bsa_sim_set_fms': (ctypes.c_int, [_vp, ctypes.c_int64, _c_dp, _c_i32p, _c_i32p, _c_i32p, ctypes.POINTER(FmsState),
@@ -1152,17 +1161,72 @@ class Context:
         st = SimState(**{k: ptr(a) for k, a in keep.items()})
         self.check(self.lib.bsa_sim_update(self.h, ctypes.byref(st)), 'bsa_sim_update')
 
-    def sim_create(self, state):
+    @staticmethod
+    def _create_extra(extra, m):
+        """(SimCreateExtra, the arrays it points into) for ``sim_create``'s ``extra``; ValueError for an unknown
+        part, a wrong length or a dtype that would have to be truncated."""
+        def arr(name, v, dtype, kinds):
+            a = np.asarray(v)
+            if a.dtype.kind not in kinds:
+                raise ValueError('create: %s has dtype %s' % (name, a.dtype))
+            a = np.ascontiguousarray(a, dtype=dtype).ravel()
+            if len(a) != m:
+                raise ValueError('create: %s has length %d != %d' % (name, len(a), m))
+            return a
+        bad = set(extra) - {'limits', 'type_idx', 'mass', 'fms'}
+        if bad:
+            raise ValueError('create: unknown parts %s' % sorted(bad))
+        x, keep = SimCreateExtra(), {}
+        if extra.get('limits') is not None:
+            for k in Context.ENVELOPE_FIELDS:
+                keep[k] = arr(k, extra['limits'][k], np.float64, 'fiu')
+                setattr(x, k, ptr(keep[k]))
+        if extra.get('type_idx') is not None:
+            keep['type_idx'] = arr('type_idx', extra['type_idx'], np.int32, 'iu')
+            x.type_idx = ptr(keep['type_idx'], _c_i32p)
+        if extra.get('mass') is not None:
+            keep['mass'] = arr('mass', extra['mass'], np.float64, 'fiu')
+            x.mass = ptr(keep['mass'])
+        if extra.get('fms') is not None:
+            rows, off, cnt, state = extra['fms']
+            rows = np.ascontiguousarray(rows, dtype=np.float64)
+            if rows.ndim != 2 or rows.shape[1] != ROUTE_COLS:
+                raise ValueError('route table must be nrows x %d' % ROUTE_COLS)
+            keep['rows'] = rows if len(rows) else np.zeros((1, ROUTE_COLS))   # (no rows is still a part)
+            x.nrows, x.route_rows = rows.shape[0], ptr(keep['rows'])
+            for k, v in (('rt_off', off), ('rt_n', cnt), ('iactwp', state['iactwp'])):
+                keep[k] = arr(k, v, np.int32, 'iu')
+                setattr(x, k, ptr(keep[k], _c_i32p))
+            for k in FMS_REALS:
+                keep[k] = arr(k, state[k], np.float64, 'fiu')
+            for k in FMS_FLAGS:
+                keep[k] = arr(k, state[k], np.uint8, 'biu')
+            keep['st'] = FmsState(**{k: ptr(keep[k]) for k in FMS_REALS}, **{k: ptr(keep[k], _c_u8p) for k in FMS_FLAGS})
+            x.st = ctypes.pointer(keep['st'])
+        return x, keep
+
+    def sim_create(self, state, extra=None):
         """bsa_sim_create: append aircraft (every SIM_STATE_FIELDS array, m long);
-        they take indices n..n+m-1 (Traffic.create, traffic.py:192-312)."""
+        they take indices n..n+m-1 (Traffic.create, traffic.py:192-312).  ``extra``
+        (bsa_sim_create_with): dict of the parts of the stages that are on, m long each --
+        ``limits`` (dict of ENVELOPE_FIELDS), ``type_idx``, ``mass``, ``fms`` = ``(rows, rt_off,
+        rt_n, state)`` of the new aircraft alone, as ``sim_set_fms`` takes them for all."""
         m = len(state['lat'])
         keep = {k: f64(state[k]) for k in SIM_STATE_FIELDS}
         for k, a in keep.items():
             if len(a) != m:
                 raise ValueError('created state %s has length %d != %d' % (k, len(a), m))
         st = SimState(**{k: ptr(a) for k, a in keep.items()})
-        self.gen += 1
-        self.check(self.lib.bsa_sim_create(self.h, m, ctypes.byref(st)), 'bsa_sim_create')
+        if extra is None:
+            self.gen += 1
+            self.check(self.lib.bsa_sim_create(self.h, m, ctypes.byref(st)), 'bsa_sim_create')
+        else:
+            x, parts = self._create_extra(extra, m)
+            self.gen += 1
+            self.check(self.lib.bsa_sim_create_with(self.h, m, ctypes.byref(st), ctypes.byref(x)), 'bsa_sim_create_with')
+            if 'type_idx' in parts and getattr(self, '_perf_keep', None) is not None \
+                    and len(self._perf_keep[1]) == self.n:                            # the host's copy follows
+                self._perf_keep = (self._perf_keep[0], np.concatenate([self._perf_keep[1], parts['type_idx']]))
         self.n += m
         st = self.sim_stats()
         self._rows = (st['row_begin'], st['row_end'])
@@ -1173,6 +1237,8 @@ class Context:
         d = np.unique(np.asarray(idx, dtype=np.int64).ravel())
         self.gen += 1
         self.check(self.lib.bsa_sim_delete(self.h, len(d), ptr(d, _c_i64p)), 'bsa_sim_delete')
+        if getattr(self, '_perf_keep', None) is not None and len(self._perf_keep[1]) == self.n:
+            self._perf_keep = (self._perf_keep[0], np.delete(self._perf_keep[1], d))
         self.n -= len(d)
         st = self.sim_stats()
         self._rows = (st['row_begin'], st['row_end'])

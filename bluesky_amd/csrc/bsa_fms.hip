@@ -227,6 +227,34 @@ void fms_off(Ctx *c) {
   geovec_off(c);  // selspd / selvs live in the FMS arrays
 }
 
+// bsa_sim_create_with's hook (bsa_internal.h).  The route table only grows: the new aircraft's rows go behind the
+// ones it holds, deleted aircraft's among them
+int fms_created(Ctx *c, int64_t n, int64_t m, const bsa_sim_create_extra &x) {
+  if (!c->sim_fms) return 0;
+  const size_t N = (size_t)(n + m);
+  const int64_t base = c->fms_nrows;
+  if (!ensure_keep(c, c->s_fmsrows, (size_t)(base + x.nrows) * 64 + 64, "route table") ||
+      !ensure(c, c->s_fmsur, kFmsUndoReals * N * 8, "FMS undo set") || !ensure(c, c->s_fmsuf, 2 * N, "FMS undo flags") ||
+      !ensure(c, c->s_fmsui, N * 4, "FMS undo waypoints"))
+    return -1;
+  if (x.nrows)
+    BSA_HIP(c, hipMemcpyAsync((char *)c->s_fmsrows.p + (size_t)base * 64, x.route_rows, (size_t)x.nrows * 64,
+                              hipMemcpyHostToDevice, c->stream));
+  const FmsFields ff = fms_fields(*x.st);
+  for (int q = 0; q < kFmsReals; ++q)
+    BSA_HIP(c, hipMemcpyAsync((double *)c->s_fmsr.p + q * N + n, ff.reals[q], (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+  for (int q = 0; q < kFmsFlags; ++q)
+    BSA_HIP(c, hipMemcpyAsync((uint8_t *)c->s_fmsf.p + q * N + n, ff.flags[q], (size_t)m, hipMemcpyHostToDevice, c->stream));
+  std::vector<int32_t> off(x.rt_off, x.rt_off + m);
+  for (int32_t &o : off) o += (int32_t)base;
+  const int32_t *ints[kFmsInts] = {x.iactwp, off.data(), x.rt_n};
+  for (int q = 0; q < kFmsInts; ++q)
+    BSA_HIP(c, hipMemcpyAsync((int32_t *)c->s_fmsi.p + q * N + n, ints[q], (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+  BSA_HIP(c, hipStreamSynchronize(c->stream));  // (off goes out of scope)
+  c->fms_nrows = base + x.nrows;
+  return 0;
+}
+
 }  // namespace bsa
 
 using bsa::Ctx;
@@ -441,6 +469,7 @@ extern "C" int bsa_sim_set_fms(bsa_ctx *cc, int64_t nrows, const double *route_r
   c->clk.fms_simt = simt;
   c->clk.fms_t0 = t0;
   c->clk.fms_ticks = 0;
+  c->fms_nrows = nrows;
   c->sim_fms = true;
   c->sim_gv = gv_on;
   return 0;

@@ -585,6 +585,7 @@ struct Ctx {
   // ap_trk / ap_alt / ap_vs / selalt; 2 x n u8; n int32).  Its clock: clk.fms_*
   DevBuf s_fmsr, s_fmsf, s_fmsi, s_fmsrows, s_fmsur, s_fmsuf, s_fmsui;
   bool sim_fms = false;
+  int64_t fms_nrows = 0;  // rows of the route table (bsa_sim_set_fms's, plus what bsa_sim_create_with appended)
   // NORESO / RESOOFF membership (bsa_sim_set_reso_lists, u8 in home order) and
   // the rows whose ResumeNav dropped a pair in the last CD call (u8, home order)
   // and how many pairs it dropped per row (int32: waypoint recovery runs once per pair)
@@ -847,6 +848,16 @@ void geovec_off(Ctx *c);
 int forces_consts(Ctx *c);
 int forces_sim_launch(Ctx *c, bool commit);
 void forces_off(Ctx *c);
+// The <stage>_created hooks of bsa_sim_create_with, for the m aircraft appended after the first n:
+// the stage's arrays are already grown to n + m, moved to that stride and zero in the new rows (so the flight phase,
+// the force outputs, perf.bank and the fuel burnt start as after set_perf / set_forces); each copies its checked
+// part of x into the new rows, stream-ordered, and does nothing while its stage is off.  limits_created /
+// perf_created: bsa_sim.hip; forces_created: bsa_perf.hip; fms_created (bsa_fms.hip) also appends x.route_rows to the
+// route table, rebases rt_off by the rows it held and sizes the undo set for n + m; it synchronises
+int limits_created(Ctx *c, int64_t n, int64_t m, const bsa_sim_create_extra &x);
+int perf_created(Ctx *c, int64_t n, int64_t m, const bsa_sim_create_extra &x);
+int forces_created(Ctx *c, int64_t n, int64_t m, const bsa_sim_create_extra &x);
+int fms_created(Ctx *c, int64_t n, int64_t m, const bsa_sim_create_extra &x);
 
 // Autopilot guidance (bsa_fms.hip).  fms_check_routes: every index the kernels
 // use unguarded, on host arrays.  fms_sim_launch: k_sim_fms of the step about

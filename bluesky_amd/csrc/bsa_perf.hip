@@ -114,6 +114,13 @@ int forces_sim_launch(Ctx *c, bool commit) {
 
 void forces_off(Ctx *c) { c->sim_forces = false; }
 
+// bsa_sim_create_with's hook (bsa_internal.h): the mass; the outputs and the fuel accumulators stay at the zeros
+int forces_created(Ctx *c, int64_t n, int64_t m, const bsa_sim_create_extra &x) {
+  if (!c->sim_forces) return 0;
+  BSA_HIP(c, hipMemcpyAsync((double *)c->s_fmass.p + n, x.mass, (size_t)m * 8, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
 }  // namespace bsa
 
 using bsa::Ctx;

@@ -676,6 +676,22 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
 // every stage with a launch of its own, off (fms_off takes recovery and the geovectors with it): a new sim
 static void stages_off(Ctx *c) { forces_off(c), fms_off(c), turb_off(c), sect_off(c), cond_off(c), exparea_off(c), trails_off(c), adsb_off(c); }
 
+// bsa_sim_create_with's hooks of the envelope and of OpenAP's type index (bsa_internal.h)
+int limits_created(Ctx *c, int64_t n, int64_t m, const bsa_sim_create_extra &x) {
+  if (!c->sim_limits) return 0;
+  const double *src[6] = {x.hmax, x.vmin, x.vmax, x.vsmin, x.vsmax, x.axmax};
+  for (int k = 0; k < 6; ++k)
+    BSA_HIP(c, hipMemcpyAsync((double *)c->s_env.p + (size_t)k * (n + m) + n, src[k], (size_t)m * 8, hipMemcpyHostToDevice,
+                              c->stream));
+  return 0;
+}
+
+int perf_created(Ctx *c, int64_t n, int64_t m, const bsa_sim_create_extra &x) {
+  if (!c->sim_perf) return 0;
+  BSA_HIP(c, hipMemcpyAsync((int32_t *)c->s_ptype.p + n, x.type_idx, (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
 }  // namespace bsa
 
 using bsa::Ctx;

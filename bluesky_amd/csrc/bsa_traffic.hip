@@ -301,6 +301,124 @@ static int multi_end(Ctx *c, Multi &m, const std::vector<int> &nh, const std::ve
   return halo_init_caps(c);
 }
 
+// the new aircraft's state arrays and their number (host checks)
+static int create_args(Ctx *c, const char *who, int64_t m, const bsa_sim_state *s) {
+  for (int k = 0; k < kSimStateFields; ++k)
+    if (!ptr_at(s, k)) return fail(c, "%s: NULL array", who);
+  if (c->n + m > 0x7fffffff) return fail(c, "n would exceed 2^31-1");
+  return 0;
+}
+
+// bsa_sim_create_with's parts against the stages that are on, on the host (nothing is enqueued): a part for every
+// stage that is on, none for one that is off, and every index the kernels use unguarded.  The force table needs no
+// look here: bsa_sim_set_forces checked engnum x engthrust of every row a type index inside the table can name
+static int create_check(Ctx *c, int64_t m, const bsa_sim_create_extra *x) {
+  static const bsa_sim_create_extra none{};
+  const char *who = "bsa_sim_create_with";
+  const bsa_sim_create_extra &e = x ? *x : none;
+  const double *env[6] = {e.hmax, e.vmin, e.vmax, e.vsmin, e.vsmax, e.axmax};
+  int nenv = 0;
+  for (auto q : env) nenv += q != nullptr;
+  if (c->sim_limits && nenv != 6) return fail(c, "%s: the envelope is on: the new aircraft's six envelope arrays", who);
+  if (!c->sim_limits && nenv != 0) return fail(c, "%s: envelope arrays while bsa_sim_set_limits is off", who);
+  if (c->sim_perf && !e.type_idx) return fail(c, "%s: OpenAP is on: the new aircraft's type_idx", who);
+  if (!c->sim_perf && e.type_idx) return fail(c, "%s: type_idx while bsa_sim_set_perf is off", who);
+  if (c->sim_forces && !e.mass) return fail(c, "%s: the OpenAP forces are on: the new aircraft's mass", who);
+  if (!c->sim_forces && e.mass) return fail(c, "%s: mass while bsa_sim_set_forces is off", who);
+  const bool routes = e.nrows != 0 || e.route_rows || e.rt_off || e.rt_n || e.iactwp || e.st;
+  if (!c->sim_fms && routes) return fail(c, "%s: routes or FMS state while bsa_sim_set_fms is off", who);
+  for (int64_t k = 0; c->sim_perf && k < m; ++k)
+    if (e.type_idx[k] < 0 || e.type_idx[k] >= c->sim_ntypes)
+      return fail(c, "%s: aircraft %lld: type index %d outside [0, %lld)", who, (long long)k, e.type_idx[k],
+                  (long long)c->sim_ntypes);
+  if (!c->sim_fms) return 0;
+  if (c->nranks > 1)
+    return fail(c, "%s with autopilot guidance on several ranks: bsa_sim_set_fms(NULL), create, set it again", who);
+  if (!e.rt_off || !e.rt_n || !e.iactwp || !e.st || (e.nrows > 0 && !e.route_rows))
+    return fail(c, "%s: guidance is on: the new aircraft's routes and FMS state", who);
+  if (e.nrows < 0 || c->fms_nrows + e.nrows > 0x7fffffff / 8) return fail(c, "%s: bad route row count", who);
+  const FmsFields ff = fms_fields(*e.st);
+  for (auto q : ff.reals)
+    if (!q) return fail(c, "%s: NULL array in the FMS state", who);
+  for (auto q : ff.flags)
+    if (!q) return fail(c, "%s: NULL array in the FMS state", who);
+  for (int q = 0; q < kFmsFlags; ++q)
+    for (int64_t k = 0; k < m; ++k)
+      if (ff.flags[q][k] > 1) return fail(c, "%s: aircraft %lld: FMS flag %d is %d (0 or 1)", who, (long long)k, q, (int)ff.flags[q][k]);
+  return fms_check_routes(c, who, m, e.nrows, e.rt_off, e.rt_n, e.iactwp, e.st->swlnav);
+}
+
+// Traffic.create on checked arguments (bsa_sim_create, bsa_sim_create_with): append the m aircraft of s; x: the
+// parts of the stages that are on (create_check), or NULL with none of them on
+static int create_rows(Ctx *c, int64_t m, const bsa_sim_state *s, const bsa_sim_create_extra *x) {
+  const int64_t n = c->n, nn = n + m;
+  BSA_HIP(c, hipSetDevice(c->device));
+  BSA_HIP(c, hipStreamSynchronize(c->stream));
+  Multi mu;
+  if (multi_begin(c, mu)) return -1;
+  std::vector<PerAc> arrs = change_arrays(c, mu);
+  const size_t NA = rows_alloc(c, nn);
+  for (auto &pa : arrs) {
+    if (!ensure_keep(c, *pa.b, (pa.count == 1 ? NA : (size_t)nn) * pa.esz * pa.count, "traffic array"))
+      return -1;
+    if (pa.count == 1) continue;
+    // sub-arrays move to the new stride n + m (via a copy: the old and new places of a sub-array may overlap)
+    const size_t sub = (size_t)n * pa.esz, nsub = (size_t)nn * pa.esz;
+    DevBuf tmp;
+    if (!ensure(c, tmp, sub * pa.count, "restrided traffic array")) return -1;
+    BSA_HIP(c, hipMemcpyAsync(tmp.p, pa.b->p, sub * pa.count, hipMemcpyDeviceToDevice, c->stream));
+    for (int k = 0; k < pa.count; ++k)
+      BSA_HIP(c, hipMemcpyAsync((char *)pa.b->p + k * nsub, (char *)tmp.p + k * sub, sub, hipMemcpyDeviceToDevice,
+                                c->stream));
+    BSA_HIP(c, hipStreamSynchronize(c->stream));
+    release(tmp);
+  }
+  // the new aircraft's state, and what starts at it: asas.trk / tas at trk / tas (asas.py:402-407)
+  for (int k = 0; k < kSimStateFields; ++k) {
+    const SimField &f = kSimFields[k];
+    DevBuf *to[2] = {&buf_at(c, f.buf), f.also ? &(c->*f.also) : nullptr};
+    for (DevBuf *b : to)
+      if (b) BSA_HIP(c, hipMemcpyAsync((char *)b->p + (size_t)n * 8, ptr_at(s, k), (size_t)m * 8,
+                                       hipMemcpyHostToDevice, c->stream));
+  }
+  // every other array: the defaults of TrafficArrays.create (trafficarrays.py:73-95), 0 / False -- in
+  // neither reso list, nothing dropped
+  for (auto &pa : arrs) {
+    if (sim_field_names(c, pa.b)) continue;
+    for (int k = 0; k < pa.count; ++k)
+      BSA_HIP(c, hipMemsetAsync((char *)pa.b->p + ((size_t)k * nn + n) * pa.esz, 0, (size_t)m * pa.esz, c->stream));
+  }
+  // the envelope, OpenAP and the guidance, where on: their rows from x over the zeros
+  if (x && (limits_created(c, n, m, *x) || perf_created(c, n, m, *x) || forces_created(c, n, m, *x) ||
+            fms_created(c, n, m, *x)))
+    return -1;
+  BSA_HIP(c, hipStreamSynchronize(c->stream));
+  if (exparea_created(c, n, m, (const double *)ptr_at(s, 2))) return -1;  // Area.create
+  if (trails_created(c, n, m, (const double *)ptr_at(s, 0), (const double *)ptr_at(s, 1))) return -1;  // Trails.create (3.31)
+  if (adsb_created(c, n, m, s)) return -1;  // ADSB.create (3.32)
+  // new aircraft have no resopairs and were in no previous pair set: empty CSR rows
+  std::vector<int> ident((size_t)n);
+  for (int64_t k = 0; k < n; ++k) ident[(size_t)k] = (int)k;
+  if (c->bk_ready && !mu.on) {
+    std::vector<unsigned> p, q;
+    DevBuf *csr[3][2] = {{&c->bk_rptr, &c->bk_rcol}, {&c->bk_pcptr, &c->bk_pccol}, {&c->bk_plptr, &c->bk_plcol}};
+    const size_t caps[3] = {(size_t)c->bk_cap, (size_t)c->cand_cap, (size_t)std::max(c->cand_cap, c->los_cap)};
+    for (int k = 0; k < 3; ++k) {
+      if (get_csr(c, *csr[k][0], *csr[k][1], n, p, q)) return -1;
+      p.resize((size_t)nn + 1, p.back());
+      if (put_csr(c, *csr[k][0], *csr[k][1], p, q, caps[k], "bookkeeping rows")) return -1;
+    }
+  }
+  set_n(c, nn);
+  // the new aircraft's gseast / gsnorth are the host's (numpy's sin / cos), not
+  // K4's expressions of their gs / trk: the halo sends them until K4' has run
+  c->sim_gs_derivable = false;
+  // the new aircraft take the homes after the existing ones, in index order
+  for (int64_t k = n; k < nn; ++k) c->h2id_h.push_back((unsigned)k);
+  if (set_home_maps(c)) return -1;
+  return multi_end(c, mu, ident, ident, m);
+}
+
 }  // namespace bsa
 
 using bsa::Ctx;
@@ -433,71 +551,19 @@ int bsa_sim_create(bsa_ctx *cc, int64_t m, const bsa_sim_state *s) {
     return bsa::fail(c, "bsa_sim_create with OpenAP limits on: switch them off, create, set them again");
   if (c->sim_fms)
     return bsa::fail(c, "bsa_sim_create with autopilot guidance on: create, then bsa_sim_set_fms again with the new routes");
-  for (int k = 0; k < bsa::kSimStateFields; ++k)
-    if (!bsa::ptr_at(s, k)) return bsa::fail(c, "bsa_sim_create: NULL array");
-  const int64_t n = c->n, nn = n + m;
-  if (nn > 0x7fffffff) return bsa::fail(c, "n would exceed 2^31-1");
-  BSA_HIP(c, hipSetDevice(c->device));
-  BSA_HIP(c, hipStreamSynchronize(c->stream));
-  bsa::Multi mu;
-  if (bsa::multi_begin(c, mu)) return -1;
-  std::vector<bsa::PerAc> arrs = bsa::change_arrays(c, mu);
-  const size_t NA = bsa::rows_alloc(c, nn);
-  for (auto &pa : arrs) {
-    if (!bsa::ensure_keep(c, *pa.b, (pa.count == 1 ? NA : (size_t)nn) * pa.esz * pa.count, "traffic array"))
-      return -1;
-    if (pa.count == 1) continue;
-    // sub-arrays move to the new stride n + m (via a copy: the old and new places of a sub-array may overlap)
-    const size_t sub = (size_t)n * pa.esz, nsub = (size_t)nn * pa.esz;
-    bsa::DevBuf tmp;
-    if (!bsa::ensure(c, tmp, sub * pa.count, "restrided traffic array")) return -1;
-    BSA_HIP(c, hipMemcpyAsync(tmp.p, pa.b->p, sub * pa.count, hipMemcpyDeviceToDevice, c->stream));
-    for (int k = 0; k < pa.count; ++k)
-      BSA_HIP(c, hipMemcpyAsync((char *)pa.b->p + k * nsub, (char *)tmp.p + k * sub, sub, hipMemcpyDeviceToDevice,
-                                c->stream));
-    BSA_HIP(c, hipStreamSynchronize(c->stream));
-    bsa::release(tmp);
-  }
-  // the new aircraft's state, and what starts at it: asas.trk / tas at trk / tas (asas.py:402-407)
-  for (int k = 0; k < bsa::kSimStateFields; ++k) {
-    const bsa::SimField &f = bsa::kSimFields[k];
-    bsa::DevBuf *to[2] = {&bsa::buf_at(c, f.buf), f.also ? &(c->*f.also) : nullptr};
-    for (bsa::DevBuf *b : to)
-      if (b) BSA_HIP(c, hipMemcpyAsync((char *)b->p + (size_t)n * 8, bsa::ptr_at(s, k), (size_t)m * 8,
-                                       hipMemcpyHostToDevice, c->stream));
-  }
-  // every other array: the defaults of TrafficArrays.create (trafficarrays.py:73-95), 0 / False -- in
-  // neither reso list, nothing dropped
-  for (auto &pa : arrs) {
-    if (bsa::sim_field_names(c, pa.b)) continue;
-    for (int k = 0; k < pa.count; ++k)
-      BSA_HIP(c, hipMemsetAsync((char *)pa.b->p + ((size_t)k * nn + n) * pa.esz, 0, (size_t)m * pa.esz, c->stream));
-  }
-  BSA_HIP(c, hipStreamSynchronize(c->stream));
-  if (bsa::exparea_created(c, n, m, (const double *)bsa::ptr_at(s, 2))) return -1;  // Area.create
-  if (bsa::trails_created(c, n, m, (const double *)bsa::ptr_at(s, 0), (const double *)bsa::ptr_at(s, 1))) return -1;  // Trails.create (3.31)
-  if (bsa::adsb_created(c, n, m, s)) return -1;  // ADSB.create (3.32)
-  // new aircraft have no resopairs and were in no previous pair set: empty CSR rows
-  std::vector<int> ident((size_t)n);
-  for (int64_t k = 0; k < n; ++k) ident[(size_t)k] = (int)k;
-  if (c->bk_ready && !mu.on) {
-    std::vector<unsigned> p, q;
-    bsa::DevBuf *csr[3][2] = {{&c->bk_rptr, &c->bk_rcol}, {&c->bk_pcptr, &c->bk_pccol}, {&c->bk_plptr, &c->bk_plcol}};
-    const size_t caps[3] = {(size_t)c->bk_cap, (size_t)c->cand_cap, (size_t)std::max(c->cand_cap, c->los_cap)};
-    for (int k = 0; k < 3; ++k) {
-      if (bsa::get_csr(c, *csr[k][0], *csr[k][1], n, p, q)) return -1;
-      p.resize((size_t)nn + 1, p.back());
-      if (bsa::put_csr(c, *csr[k][0], *csr[k][1], p, q, caps[k], "bookkeeping rows")) return -1;
-    }
-  }
-  bsa::set_n(c, nn);
-  // the new aircraft's gseast / gsnorth are the host's (numpy's sin / cos), not
-  // K4's expressions of their gs / trk: the halo sends them until K4' has run
-  c->sim_gs_derivable = false;
-  // the new aircraft take the homes after the existing ones, in index order
-  for (int64_t k = n; k < nn; ++k) c->h2id_h.push_back((unsigned)k);
-  if (bsa::set_home_maps(c)) return -1;
-  return bsa::multi_end(c, mu, ident, ident, m);
+  if (bsa::create_args(c, "bsa_sim_create", m, s)) return -1;
+  return bsa::create_rows(c, m, s, nullptr);
+}
+
+int bsa_sim_create_with(bsa_ctx *cc, int64_t m, const bsa_sim_state *s, const bsa_sim_create_extra *x) {
+  Ctx *c = (Ctx *)cc;
+  if (!c) return -1;
+  // every check before check_sim: it drops a requested snapshot, and a refused call changes nothing
+  if (!c->sim_ready) return bsa::fail(c, "bsa_sim_create_with before bsa_sim_init");
+  if (m < 1 || !s) return bsa::fail(c, "bad create arguments");
+  if (bsa::create_args(c, "bsa_sim_create_with", m, s) || bsa::create_check(c, m, x)) return -1;
+  if (bsa::check_sim(c, "bsa_sim_create_with")) return -1;
+  return bsa::create_rows(c, m, s, x);
 }
 
 }  // extern "C"

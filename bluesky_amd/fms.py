@@ -198,6 +198,23 @@ def synthetic_routes(state, seed=0, nwp=4, leg=(3000., 9000.), first=(200., 1200
     return rows, off, cnt, st
 
 
+def append_routes(rows, off, n, new_rows, new_off, new_n):
+    """The route table after ``ResidentSim.create(..., fms=(new_rows, new_off, new_n, state))``,
+    as the device keeps it: ``new_rows`` behind ``rows``, ``new_off`` rebased by ``len(rows)``.
+    Returns ``(rows, off, n)`` for the old aircraft followed by the new ones; the inputs stay
+    as they are.  Pure numpy: the host's own copy of the table."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, len(COLS))
+    new_rows = np.asarray(new_rows, dtype=np.float64).reshape(-1, len(COLS))
+    off, n, new_off, new_n = (np.asarray(a, dtype=np.int32).ravel() for a in (off, n, new_off, new_n))
+    if len(off) != len(n) or len(new_off) != len(new_n):
+        raise ValueError('append_routes: one offset and one count per aircraft')
+    for o, c, r in ((off, n, rows), (new_off, new_n, new_rows)):
+        if len(o) and ((o < 0).any() or (c < 0).any() or (o.astype(np.int64) + c).max() > len(r)):
+            raise ValueError('append_routes: a route lies outside its table')
+    return (np.concatenate([rows, new_rows]), np.concatenate([off, new_off + np.int32(len(rows))]),
+            np.concatenate([n, new_n]))
+
+
 FMS_DT = 1.01    # Autopilot.dt (autopilot.py:18)
 
 

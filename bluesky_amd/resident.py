@@ -224,15 +224,27 @@ class ResidentSim:
         rows, and ``simt``, ``t0``, ``ticks`` (bsa_sim_read_fms)."""
         return self.ctx.sim_read_fms()
 
-    def create(self, state, ids=None):
+    def create(self, state, ids=None, *, limits=None, perf=None, mass=None, fms=None):
         """Append aircraft (Traffic.create; ``state`` as ``initial_state`` returns,
         m long each): indices n..n+m-1 (bsa_sim_create; collective with several ranks).
-        ``ids``: their callsigns, when ``set_sectors`` was given ids."""
+        ``ids``: their callsigns, when ``set_sectors`` was given ids.
+        While the envelope, OpenAP or the guidance run, plain ``create`` is refused; hand in
+        the new aircraft's part of every such stage (bsa_sim_create_with), m
+        long each: ``limits`` (the dict ``ResidentSim(limits=...)`` takes), ``perf`` (their
+        ``type_idx``, rows of ``set_perf``'s table), ``mass`` (``set_forces``), ``fms`` =
+        ``(rows, off, n, state)`` as ``fms.route_table`` / ``fms.from_bluesky`` /
+        ``fms.synthetic_routes`` return it for the new aircraft alone.  A part for a stage that
+        is off, a missing one, a type outside the table or a route outside ``rows`` is refused
+        and changes nothing.  The others keep everything -- fuel burnt, the FMS clock and tick
+        count; the new ones start as after ``set_perf`` / ``set_forces``.  With guidance on:
+        one rank only."""
+        extra = {k: v for k, v in (('limits', limits), ('type_idx', perf), ('mass', mass), ('fms', fms)) if v is not None}
         if getattr(self, 'ids', None) is not None:
             if ids is None or len(ids) != len(state['lat']):
                 raise ValueError('create: one id per new aircraft (set_sectors was given ids)')
+        self.ctx.sim_create(state, extra or None)
+        if getattr(self, 'ids', None) is not None:   # (after the call: a refused create changes nothing)
             self.ids = self.ids + list(ids)
-        self.ctx.sim_create(state)
 
     def delete(self, idx):
         """Remove aircraft ``idx`` (Traffic.delete: the rest shift down in order),

@@ -507,7 +507,8 @@ int bsa_sim_set_limits(bsa_ctx *ctx, const double *hmax, const double *vmin, con
  * (1 fixed wing, 2 rotor, 0 other), 0 (bluesky_amd/perf.py builds it from the
  * reference's Coefficient tables); type_idx: full-n row per aircraft
  * (validated).  Takes precedence over bsa_sim_set_limits; table == NULL
- * switches it off (the default after bsa_sim_init). */
+ * switches it off (the default after bsa_sim_init).  bsa_sim_create stays
+ * refused while it is on (bsa_sim_create_with takes the new aircraft's type_idx). */
 int bsa_sim_set_perf(bsa_ctx *ctx, int64_t ntypes, const double *table, const int32_t *type_idx);
 /* This rank's rows of the flight phase of the last step
  * (0..8, phase.py:4-12; needs bsa_sim_set_perf) and of traf.ax, written into
@@ -539,7 +540,8 @@ int bsa_openap_forces(bsa_ctx *ctx, int64_t n, int64_t ntypes, const double *tab
  * array [kg], constant as in the reference.  Switching on zeroes the outputs,
  * perf.bank and the fuel burnt.  ftable == NULL switches it off (the default),
  * and so does every bsa_sim_set_perf call.  bsa_sim_delete carries the arrays
- * along; bsa_sim_create stays refused while bsa_sim_set_perf is on.
+ * along; bsa_sim_create stays refused while bsa_sim_set_perf is on
+ * (bsa_sim_create_with takes the new aircraft's mass and keeps the others' fuel).
  * Fuel burnt (an extension, not in the reference): per aircraft, the sum over
  * the completed steps, in step order, of that step's fuelflow x simdt [kg] --
  * exact through aborted and re-run steps (each step counted once). */
@@ -601,7 +603,8 @@ int bsa_fms_recover(bsa_ctx *ctx, int64_t n, int64_t nrows, const double *route_
  * evaluates ap.tas.  Exact through aborted and re-run batches.  route_rows ==
  * NULL switches it off (the default); a second call replaces everything.
  * bsa_sim_delete carries the arrays along on one rank and is refused on
- * several; bsa_sim_create is refused while it is on. */
+ * several; bsa_sim_create is refused while it is on (bsa_sim_create_with
+ * takes the new aircraft's routes and state, on one rank). */
 int bsa_sim_set_fms(bsa_ctx *ctx, int64_t nrows, const double *route_rows, const int32_t *rt_off, const int32_t *rt_n,
                     const int32_t *iactwp, const bsa_fms_state *st, double simt, double t0);
 /* Waypoint recovery inside the resident step (off by default): every CD step
@@ -1025,6 +1028,38 @@ int bsa_sim_update(bsa_ctx *ctx, const bsa_sim_state *s);
  * first, the rows re-partitioned over the new n afterwards (each rank keeps
  * the bookkeeping of its new range). */
 int bsa_sim_create(bsa_ctx *ctx, int64_t m, const bsa_sim_state *s);
+/* bsa_sim_create while the envelope, OpenAP and the autopilot guidance run
+ * (DESIGN.md 3.15): the same append, plus the new aircraft's rows of every such
+ * stage that is on.  x holds one part per stage, m-long host arrays each: the
+ * six envelope arrays (bsa_sim_set_limits on), type_idx (bsa_sim_set_perf on:
+ * rows of its table), mass (bsa_sim_set_forces on), and for bsa_sim_set_fms
+ * the new aircraft's waypoints (nrows x 8, may be none), rt_off relative to
+ * them, rt_n, iactwp and st, as bsa_sim_set_fms takes them for all aircraft.
+ * A stage that is on needs its part; a part (any of its pointers, or nrows)
+ * given for a stage that is off is an error; x == NULL is no part at all, so
+ * with none of the four on this is bsa_sim_create.  Everything is validated on
+ * the host before anything is enqueued -- type_idx inside the table (whose
+ * every row bsa_sim_set_forces has checked), each route inside route_rows,
+ * iactwp inside its route (without a route: -1 or 0, and LNAV off), flags 0 or
+ * 1, no NULL -- and a refused call leaves the sim as it was.  New aircraft
+ * start with phase 0 as after bsa_sim_set_perf, and with the six force
+ * outputs, perf.bank and the fuel burnt at 0 as after bsa_sim_set_forces; the
+ * others keep everything, fuel burnt included.  route_rows is appended to the
+ * device's route table (which only grows: deleted aircraft leave holes) and
+ * rt_off rebased; simt, t0, the tick count and bsa_sim_set_recovery stay.
+ * Several ranks: collective as bsa_sim_create with the envelope, perf and
+ * forces parts (the re-partition carries their arrays); refused with guidance
+ * on, as bsa_sim_delete is. */
+typedef struct bsa_sim_create_extra {
+  const double *hmax, *vmin, *vmax, *vsmin, *vsmax, *axmax; /* limits on (set_limits form): m each */
+  const int32_t *type_idx;                                  /* perf on: m rows of the type table */
+  const double *mass;                                       /* forces on: m */
+  int64_t nrows;
+  const double *route_rows;                                 /* fms on: the new aircraft's waypoints, nrows x 8 */
+  const int32_t *rt_off, *rt_n, *iactwp;                    /* m each; rt_off relative to route_rows */
+  const bsa_fms_state *st;                                  /* m-long arrays */
+} bsa_sim_create_extra;
+int bsa_sim_create_with(bsa_ctx *ctx, int64_t m, const bsa_sim_state *s, const bsa_sim_create_extra *x);
 /* Traffic.delete for the resident sim (traffic.py:364-378 ->
  * trafficarrays.py:99-117): remove the k aircraft idx[0..k) (any order,
  * duplicates ignored); the rest keep their order and shift down, as np.delete
