@@ -236,7 +236,51 @@ class SimCreateExtra(ctypes.Structure):
                  ('rt_off', _c_i32p), ('rt_n', _c_i32p), ('iactwp', _c_i32p), ('st', ctypes.POINTER(FmsState))])
 
 
+class RouteEditRec(ctypes.Structure):
+    """bsa_route_edit_rec (include/bsaccel.h)."""
+    _fields_ = ([(k, ctypes.c_int32) for k in ('aircraft', 'op', 'pos', 'flyby', 'wptype', 'bump_active')] +
+                [(k, ctypes.c_double) for k in ('lat', 'lon', 'alt', 'spd')])
+
+
+ROUTE_REC_DTYPE = np.dtype([(k, np.int32) for k in ('aircraft', 'op', 'pos', 'flyby', 'wptype', 'bump_active')] +
+                           [(k, np.float64) for k in ('lat', 'lon', 'alt', 'spd')])
+ROUTE_INSERT, ROUTE_OVERWRITE, ROUTE_DELETE, ROUTE_DIRECT = range(4)
+ROUTE_ERRORS = {1: 'aircraft index out of range', 2: 'no such op', 3: 'pos outside the route',
+                4: 'runway / calculated waypoint', 5: 'lat / lon not finite', 6: 'guidance on several ranks'}
+_c_recp = ctypes.POINTER(RouteEditRec)
+
+
+class RouteEditRefused(ValueError):
+    """A route edit batch was refused (nothing changed); ``code``: BSA_ROUTE_ERR_*."""
+
+    def __init__(self, code, msg):
+        ValueError.__init__(self, msg)
+        self.code = code
+
+
+def route_records(records):
+    """A batch of edit records as a contiguous ROUTE_REC_DTYPE array (from such an
+    array, or a list of dicts / tuples in the field order)."""
+    if isinstance(records, np.ndarray) and records.dtype == ROUTE_REC_DTYPE:
+        return np.ascontiguousarray(records).ravel()
+    out = np.zeros(len(records), ROUTE_REC_DTYPE)
+    for q, r in enumerate(records):
+        if isinstance(r, dict):
+            for k in ROUTE_REC_DTYPE.names:
+                out[q][k] = r.get(k, 0)
+        else:
+            out[q] = tuple(r)
+    return out
+
+
 SIGNATURES.update({
+    'bsa_route_edit': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _c_dp, _c_u8p, _c_i32p, _c_i32p, _c_i32p] +
+                       [_c_dp] * 7 + [ctypes.POINTER(FmsState), _c_dp, ctypes.c_int64, _c_recp, ctypes.c_int64, _c_dp,
+                                      _c_u8p, _c_i32p, _c_i32p, _c_i64p]),
+    'bsa_sim_route_edit': (ctypes.c_int, [_vp, ctypes.c_int64, _c_recp]),
+    'bsa_sim_route_rows': (ctypes.c_int, [_vp, _c_i64p]),
+    'bsa_sim_read_routes': (ctypes.c_int, [_vp, ctypes.c_int64, _c_dp, _c_u8p, _c_i32p, _c_i32p, _c_i64p]),
+    'bsa_sim_route_stats': (ctypes.c_int, [_vp] + [_c_i64p] * 4),
     'bsa_sim_create_with': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.POINTER(SimState),
                                            ctypes.POINTER(SimCreateExtra)]),
     'bsa_fms_update': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _c_dp, _c_i32p, _c_i32p, _c_i32p] +
@@ -947,6 +991,71 @@ class Context:
         for k in FMS_FLAGS:
             out[k] = out[k].astype(bool)
         return out
+
+    def _route_check(self, rc, who):
+        if rc > 0:
+            raise RouteEditRefused(rc, '%s refused the batch (%s): %s' % (who, ROUTE_ERRORS.get(rc, rc),
+                                                                             self.lib.bsa_last_error(self.h).decode()))
+        self.check(rc, who)
+
+    def route_edit(self, rows, rt_off, rt_n, state, records, wptype=None):
+        """bsa_route_edit: a batch of route edit records (``route_records``) on host
+        arrays.  ``rows`` / ``rt_off`` / ``rt_n`` / ``state`` as ``fms_recover`` takes them;
+        ``wptype``: the waypoint type per row (None: all 0).  Returns ``(rows, rt_off,
+        rt_n, wptype, state)``: the new table compacted in aircraft order and a new dict of
+        FMS_REALS, FMS_FLAGS, ``ap_alt`` and ``iactwp``.  A refused batch raises
+        RouteEditRefused."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, ROUTE_COLS)
+        off = np.ascontiguousarray(rt_off, dtype=np.int32).ravel()
+        cnt = np.ascontiguousarray(rt_n, dtype=np.int32).ravel()
+        rec = route_records(records)
+        n = len(off)
+        wt = None if wptype is None else np.ascontiguousarray(wptype, dtype=np.uint8).ravel()
+        if wt is not None and len(wt) != len(rows):
+            raise ValueError('one waypoint type per table row')
+        names = [k for k in FMS_TRAFFIC if k != 'ax']
+        tr = [f64(state[k]).ravel() for k in names]
+        out = {k: np.array(state[k], dtype=np.float64).ravel() for k in FMS_REALS + ('ap_alt',)}
+        out.update({k: np.array(state[k]).astype(np.uint8).ravel() for k in FMS_FLAGS})
+        out['iactwp'] = np.array(state['iactwp'], dtype=np.int32).ravel()
+        for k, a in list(zip(names, tr)) + list(out.items()) + [('rt_n', cnt)]:
+            if len(a) != n:
+                raise ValueError('FMS array %s has length %d != %d' % (k, len(a), n))
+        cap = len(rows) + len(rec)
+        orows, otype = np.zeros((max(cap, 1), ROUTE_COLS)), np.zeros(max(cap, 1), np.uint8)
+        ooff, ocnt, onrows = np.zeros(n, np.int32), np.zeros(n, np.int32), ctypes.c_int64()
+        st = FmsState(**{k: ptr(out[k]) for k in FMS_REALS}, **{k: ptr(out[k], _c_u8p) for k in FMS_FLAGS})
+        rc = self.lib.bsa_route_edit(self.h, n, rows.shape[0], ptr(rows), ptr(wt, _c_u8p), ptr(off, _c_i32p),
+                                     ptr(cnt, _c_i32p), ptr(out['iactwp'], _c_i32p), *[ptr(a) for a in tr],
+                                     ctypes.byref(st), ptr(out['ap_alt']), len(rec),
+                                     rec.ctypes.data_as(_c_recp), cap, ptr(orows), ptr(otype, _c_u8p),
+                                     ptr(ooff, _c_i32p), ptr(ocnt, _c_i32p), ctypes.byref(onrows))
+        self._route_check(rc, 'bsa_route_edit')
+        for k in FMS_FLAGS:
+            out[k] = out[k].astype(bool)
+        return orows[:onrows.value].copy(), ooff, ocnt, otype[:onrows.value].copy(), out
+
+    def sim_route_edit(self, records):
+        """bsa_sim_route_edit: the batch on the resident sim's table."""
+        rec = route_records(records)
+        self._route_check(self.lib.bsa_sim_route_edit(self.h, len(rec), rec.ctypes.data_as(_c_recp)), 'bsa_sim_route_edit')
+
+    def sim_read_routes(self):
+        """bsa_sim_read_routes: ``(rows, rt_off, rt_n, wptype)`` in aircraft order, compacted."""
+        live = ctypes.c_int64()
+        self._route_check(self.lib.bsa_sim_route_rows(self.h, ctypes.byref(live)), 'bsa_sim_route_rows')
+        cap = max(int(live.value), 1)
+        rows, wt = np.zeros((cap, ROUTE_COLS)), np.zeros(cap, np.uint8)
+        off, cnt, got = np.zeros(self.n, np.int32), np.zeros(self.n, np.int32), ctypes.c_int64()
+        self._route_check(self.lib.bsa_sim_read_routes(self.h, cap, ptr(rows), ptr(wt, _c_u8p), ptr(off, _c_i32p),
+                                                       ptr(cnt, _c_i32p), ctypes.byref(got)), 'bsa_sim_read_routes')
+        return rows[:got.value].copy(), off, cnt, wt[:got.value].copy()
+
+    def sim_route_stats(self):
+        """bsa_sim_route_stats: dict of ``live``, ``dead``, ``written``, ``compactions``."""
+        v = [ctypes.c_int64() for _ in range(4)]
+        self._route_check(self.lib.bsa_sim_route_stats(self.h, *[ctypes.byref(x) for x in v]), 'bsa_sim_route_stats')
+        return dict(zip(('live', 'dead', 'written', 'compactions'), (int(x.value) for x in v)))
 
     def sim_set_recovery(self, on=True):
         """bsa_sim_set_recovery: waypoint recovery after ResumeNav in the resident step."""

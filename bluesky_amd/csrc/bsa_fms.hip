@@ -11,16 +11,6 @@
 
 namespace bsa {
 
-struct FmsArrays {
-  const double *tr[8];     // lat lon alt tas gs trk ax bank (read only)
-  double *st[kFmsReals];   // bsa_fms_state's doubles (selvs, apvsdef read only)
-  uint8_t *fl[4];          // swlnav swvnav abco belco (abco, belco read only)
-  double *tg[5];           // ap_trk ap_tas ap_alt ap_vs selalt
-  int *iactwp;
-  const int *rt_off, *rt_n;
-  const double *rows;
-};
-
 __device__ __forceinline__ fms::Lane fms_load(const FmsArrays &a, int k) {
   fms::Lane L;
   L.lat = a.tr[0][k], L.lon = a.tr[1][k], L.alt = a.tr[2][k], L.tas = a.tr[3][k];
@@ -93,7 +83,7 @@ __global__ __launch_bounds__(64) void k_sim_fms(int rb, int re, FmsArrays a, Fms
   }
 }
 
-static FmsArrays fms_sim_arrays(Ctx *c) {
+FmsArrays fms_sim_arrays(Ctx *c) {
   const size_t n = (size_t)c->n;
   FmsArrays a;
   const void *tr[8] = {c->own[0].p, c->own[1].p, c->own[4].p, c->s_tas.p, c->own[3].p, c->own[2].p, c->s_ax.p,
@@ -470,6 +460,7 @@ extern "C" int bsa_sim_set_fms(bsa_ctx *cc, int64_t nrows, const double *route_r
   c->clk.fms_t0 = t0;
   c->clk.fms_ticks = 0;
   c->fms_nrows = nrows;
+  c->fms_ntypes = 0, c->rt_written = 0, c->rt_compactions = 0;  // a new table: every row type 0, no edit yet
   c->sim_fms = true;
   c->sim_gv = gv_on;
   return 0;

@@ -586,6 +586,11 @@ struct Ctx {
   DevBuf s_fmsr, s_fmsf, s_fmsi, s_fmsrows, s_fmsur, s_fmsuf, s_fmsui;
   bool sim_fms = false;
   int64_t fms_nrows = 0;  // rows of the route table (bsa_sim_set_fms's, plus what bsa_sim_create_with appended)
+  // Route edits (bsa_route.hip): the waypoint type per table row (u8; the first fms_ntypes rows
+  // hold one, rows behind them are type 0 until an edit reaches them), the second table a compaction writes,
+  // staging, and the counts of bsa_sim_route_stats
+  DevBuf s_fmstype, s_fmsrows2, s_fmstype2, rt_stage, rt_ws;
+  int64_t fms_ntypes = 0, rt_written = 0, rt_compactions = 0;
   // NORESO / RESOOFF membership (bsa_sim_set_reso_lists, u8 in home order) and
   // the rows whose ResumeNav dropped a pair in the last CD call (u8, home order)
   // and how many pairs it dropped per row (int32: waypoint recovery runs once per pair)
@@ -869,6 +874,17 @@ int fms_check_routes(Ctx *c, const char *who, int64_t n, int64_t nrows, const in
                      const int32_t *iactwp, const uint8_t *swlnav);
 int fms_sim_launch(Ctx *c, bool tick);
 int fms_sim_restore(Ctx *c);
+// the device view of the FMS arrays (the resident sim's: fms_sim_arrays; the standalone calls stage their own)
+struct FmsArrays {
+  const double *tr[8];     // lat lon alt tas gs trk ax bank (read only)
+  double *st[kFmsReals];   // bsa_fms_state's doubles (selvs, apvsdef read only)
+  uint8_t *fl[4];          // swlnav swvnav abco belco (abco, belco read only)
+  double *tg[5];           // ap_trk ap_tas ap_alt ap_vs selalt
+  int *iactwp;
+  const int *rt_off, *rt_n;
+  const double *rows;
+};
+FmsArrays fms_sim_arrays(Ctx *c);
 void fms_off(Ctx *c);
 // waypoint recovery of the CD step just enqueued (after bk_apply, before K4'): k_sim_recover on this rank's rows
 int fms_sim_recover(Ctx *c);

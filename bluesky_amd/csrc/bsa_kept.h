@@ -156,6 +156,7 @@ enum class Change {
   WindField,          // bsa_set_windfield3d
   Turbulence,         // bsa_sim_set_turbulence: on / off, sd, seed
   Adsb,               // bsa_sim_set_adsb: on / off and every setting
+  RouteEdit,          // bsa_sim_route_edit
   Count
 };
 struct Drops {
@@ -181,6 +182,9 @@ constexpr bool drop = true, stays = false;
 //      records' budget check and HK's predictions assumed it
 //  (a) the ADS-B stage reads the traffic state and writes only its own picture and lastupdate arrays, which no detect
 //      reads (the step's detect takes the true state as intruder): nothing kept depends on it or on its settings
+//  (r) a route edit writes the route table and the FMS arrays (actwp.*, iactwp, swlnav, selspd, ap.alt): guidance
+//      targets only, no position or velocity, and no detect reads any of them; the aircraft move under the new
+//      targets only through K4', whose records (or the next detect's) every kept state checks against its snapshot
 //  (n) the steps enqueued behind the stop became no-ops, but their detects ran -- on the state the stop left, with
 //      the host's later decisions: they re-armed the candidate list, the tile-pair list and its snapshot, the zeroed
 //      counters and the HK history for steps that never happened, and K4' prepared no records for them.  All of it
@@ -210,6 +214,7 @@ constexpr Drops kDrops[(int)Change::Count] = {
     /* WindField         */ {stays, stays, stays, stays, stays, stays}, // w w w w w w
     /* Turbulence        */ {stays, drop, drop, drop, stays, drop},     // p t t t z t
     /* Adsb              */ {stays, stays, stays, stays, stays, stays}, // a a a a a a
+    /* RouteEdit         */ {stays, stays, stays, stays, stays, stays}, // r r r r r r
 };
 
 }  // namespace bsa

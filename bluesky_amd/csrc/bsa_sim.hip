@@ -210,7 +210,7 @@ void sim_release(Ctx *c) {
   for (const SimArray &a : kSimArrays) release(buf_at(c, a.buf));
   // not per aircraft: staging, control words, tables, the FMS undo set, K2 + K4' double buffers
   DevBuf *rest[] = {&c->red, &c->g_send, &c->g_recv, &c->pg_send, &c->pg_recv, &c->sim_ctl, &c->s_ptab, &c->s_ftab,
-                    &c->f_const, &c->s_fmsrows, &c->s_fmsur, &c->s_fmsuf, &c->s_fmsui, &c->gv_tab, &c->gv_shapes, &c->gv_undo,
+                    &c->f_const, &c->s_fmsrows, &c->s_fmstype, &c->s_fmsrows2, &c->s_fmstype2, &c->rt_stage, &c->rt_ws, &c->s_fmsur, &c->s_fmsuf, &c->s_fmsui, &c->gv_tab, &c->gv_shapes, &c->gv_undo,
                     &c->gv_cnt, &c->xfer_stage, &c->lbyidx, &c->xa_ws, &c->xa_rec, &c->tr_stage, &c->tr_seg, &c->tr_ws, &c->adsb_stage,
                     &c->fetch_stage, &c->tpr_snap, &c->tpr_ctl, &c->nx_alt, &c->nx_vs, &c->nx_gse, &c->nx_gsn};
   for (auto *b : rest) release(*b);

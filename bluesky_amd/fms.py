@@ -254,3 +254,107 @@ def recover(rows, off, n, state, count, ctx=None):
     by name for routes with unique names (``from_bluesky(unique_names=True)``)."""
     ctx = ctx or _lib.default_context()
     return ctx.fms_recover(rows, off, n, state, count)
+
+
+# ---- route edits (ADDWPT / DELWPT / DIRECT; bsa_route_edit, DESIGN.md 3.33)
+INSERT, OVERWRITE, DELETE, DIRECT = _lib.ROUTE_INSERT, _lib.ROUTE_OVERWRITE, _lib.ROUTE_DELETE, _lib.ROUTE_DIRECT
+WP_ORIG, WP_CALC = 2, 4
+RouteEditRefused = _lib.RouteEditRefused
+
+
+def record(aircraft, op, pos, lat=0., lon=0., alt=-999., spd=-999., flyby=True, wptype=0, bump_active=False):
+    """One edit record (a dict ``_lib.route_records`` takes)."""
+    return dict(aircraft=int(aircraft), op=int(op), pos=int(pos), flyby=int(bool(flyby)), wptype=int(wptype),
+                bump_active=int(bool(bump_active)), lat=float(lat), lon=float(lon), alt=float(alt), spd=float(spd))
+
+
+def edit(rows, off, n, state, records, wptype=None, ctx=None):
+    """A batch of edit records on the device, standalone (bsa_route_edit): returns
+    ``(rows, off, n, wptype, fms_state)``, the new table compacted in aircraft order
+    and the FMS state after the batch; the inputs stay as they are.  ``state`` as
+    ``recover`` takes it.  A refused batch raises ``RouteEditRefused`` (``.code``)."""
+    ctx = ctx or _lib.default_context()
+    return ctx.route_edit(rows, off, n, state, records, wptype)
+
+
+class RouteNames:
+    """The host's side of a route edit: the waypoint names (and types) of every
+    aircraft's route, and the reference's lookups on them.  ``addwpt`` / ``delwpt``
+    / ``direct`` take ``Route.addwpt`` / ``delwpt`` / ``direct``'s arguments with the
+    position already resolved (the nav database is the host's) and return edit
+    records for ``edit`` / ``ResidentSim.edit_routes``; each also applies the edit to
+    the names, so the next call sees the route this one leaves.  ``create`` /
+    ``delete`` mirror ``ResidentSim.create`` / ``delete``."""
+
+    def __init__(self, names, types=None):
+        self.names = [[str(x).upper().strip() for x in r] for r in names]
+        self.types = [[0] * len(r) for r in names] if types is None else [[int(t) for t in r] for r in types]
+        if [len(r) for r in self.names] != [len(r) for r in self.types]:
+            raise ValueError('one waypoint type per name')
+
+    def create(self, names, types=None):
+        new = RouteNames(names, types)
+        self.names += new.names
+        self.types += new.types
+
+    def delete(self, idx):
+        gone = set(int(i) for i in np.unique(np.asarray(idx, dtype=np.int64).ravel()))
+        self.names = [r for k, r in enumerate(self.names) if k not in gone]
+        self.types = [r for k, r in enumerate(self.types) if k not in gone]
+
+    @staticmethod
+    def available_name(data, name, len_=2):
+        """Route.get_available_name: ``name``, or ``name`` + the first free number."""
+        appi, out = 0, name
+        fmt = '{:0' + str(len_) + 'd}'
+        while data.count(out) > 0:
+            appi += 1
+            out = name + fmt.format(appi)
+        return out
+
+    def addwpt(self, iac, name, wptype, lat, lon, alt=-999., spd=-999., afterwp="", beforewp="", flyby=True):
+        """route.py:537-594 for a waypoint the nav database found (``lat, lon``: its
+        position).  ORIG / DEST (route.py:498-535 updates no ``next_qdr``), runway and
+        calculated waypoints are refused."""
+        if wptype in (WP_ORIG, WP_DEST, WP_CALC, WP_RUNWAY):
+            raise ValueError('addwpt: waypoint type %d is not supported on the device' % wptype)
+        names, types = self.names[iac], self.types[iac]
+        name = name.upper().strip()
+        newname = self.available_name(names, name, 3) if wptype == 0 else self.available_name(names, name)
+        aftwp, bfwp = afterwp.upper().strip(), beforewp.upper().strip()
+        bump = False
+        if (afterwp and names.count(aftwp) > 0) or (beforewp and names.count(bfwp) > 0):
+            pos = names.index(aftwp) + 1 if afterwp else names.index(bfwp)
+            bump = bool(afterwp)
+        elif len(names) > 0 and types[-1] == WP_DEST:
+            pos = len(names) - 1
+        else:
+            pos = len(names)
+        names.insert(pos, newname)
+        types.insert(pos, int(wptype))
+        return [record(iac, INSERT, pos, lat, lon, alt, spd, flyby, wptype, bump)]
+
+    def delwpt(self, iac, name):
+        """route.py:808-838: the LAST waypoint of that name; ``*``: every waypoint."""
+        names, types = self.names[iac], self.types[iac]
+        if name == '*':
+            out = [record(iac, DELETE, 0) for _ in names]
+            del names[:], types[:]
+            return out
+        idx = -1
+        i = len(names)
+        while idx == -1 and i > 0:
+            i -= 1
+            if names[i].upper() == name.upper():
+                idx = i
+        if idx == -1:
+            raise ValueError('delwpt: waypoint %s not found' % name)
+        del names[idx], types[idx]
+        return [record(iac, DELETE, idx)]
+
+    def direct(self, iac, name):
+        """route.py:635-640: the FIRST waypoint of that name."""
+        name = name.upper().strip()
+        if name == '' or self.names[iac].count(name) == 0:
+            raise ValueError('direct: waypoint %s not found' % name)
+        return [record(iac, DIRECT, self.names[iac].index(name))]

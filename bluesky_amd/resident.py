@@ -224,6 +224,24 @@ class ResidentSim:
         rows, and ``simt``, ``t0``, ``ticks`` (bsa_sim_read_fms)."""
         return self.ctx.sim_read_fms()
 
+    def edit_routes(self, records):
+        """A batch of route edit records (``fms.RouteNames.addwpt`` / ``delwpt`` /
+        ``direct``, ``fms.record``) on the sim's own route table, between batches of steps
+        (bsa_sim_route_edit): ADDWPT / DELWPT / DIRECT without reading the
+        table back.  The FMS clock, the tick count and every kept detect state stay.  A
+        refused batch raises ``fms.RouteEditRefused`` and changes nothing.  One rank only."""
+        self.ctx.sim_route_edit(records)
+
+    def read_routes(self):
+        """``(rows, off, n, wptype)``: the route table in aircraft order, compacted, as
+        ``set_fms`` takes it (bsa_sim_read_routes)."""
+        return self.ctx.sim_read_routes()
+
+    def route_stats(self):
+        """dict of the table's ``live`` and ``dead`` rows, the rows ``written`` by the last
+        ``edit_routes`` and the ``compactions`` since ``set_fms`` (bsa_sim_route_stats)."""
+        return self.ctx.sim_route_stats()
+
     def create(self, state, ids=None, *, limits=None, perf=None, mass=None, fms=None):
         """Append aircraft (Traffic.create; ``state`` as ``initial_state`` returns,
         m long each): indices n..n+m-1 (bsa_sim_create; collective with several ranks).

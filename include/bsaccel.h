@@ -1197,6 +1197,67 @@ typedef struct bsa_acdata {
 int bsa_sim_acdata_request(bsa_ctx *ctx);
 int bsa_sim_acdata_poll(bsa_ctx *ctx, int wait, bsa_acdata *out);
 
+/* ---------------------------------------------------------------- route edits
+ * ADDWPT / DELWPT / DIRECT on the route table.  A batch is m
+ * records; the records of one aircraft apply in batch order, each to the route
+ * the one before left, records of different aircraft are independent.  Names
+ * are the host's: pos is an index into the route.
+ *   INSERT     a new waypoint before row pos (pos == n appends); bump_active:
+ *              AFTER was given and found (iactwp >= pos moves up by one)
+ *   OVERWRITE  row pos gets the record's waypoint
+ *   DELETE     row pos goes, iactwp by Route.delwpt's rule; the active-waypoint
+ *              data stay (the reference's delwpt does not touch them); a route
+ *              emptied this way ends with iactwp -1 and LNAV off
+ *   DIRECT     Route.direct to row pos
+ * After an INSERT / OVERWRITE the route's flight plan (Route.calcfp) is
+ * recomputed, actwp.next_qdr = getnextqdr(), and with 0 <= iactwp < n
+ * Route.direct runs to iactwp; after a DELETE the flight plan is recomputed.
+ * A refused batch changes nothing; the call returns the refusal (> 0) and
+ * bsa_last_error names the record.  -1: any other failure. */
+enum { BSA_ROUTE_INSERT = 0, BSA_ROUTE_OVERWRITE = 1, BSA_ROUTE_DELETE = 2, BSA_ROUTE_DIRECT = 3 };
+enum {
+  BSA_ROUTE_OK = 0,
+  BSA_ROUTE_ERR_AIRCRAFT = 1,  /* aircraft index outside [0, n) */
+  BSA_ROUTE_ERR_OP = 2,        /* no such op */
+  BSA_ROUTE_ERR_POS = 3,       /* pos outside the route as the earlier records of the batch left it */
+  BSA_ROUTE_ERR_WPTYPE = 4,    /* runway (5) or calculated (4) waypoint, or no waypoint type */
+  BSA_ROUTE_ERR_NONFINITE = 5, /* lat / lon not finite */
+  BSA_ROUTE_ERR_RANKS = 6      /* guidance on several ranks */
+};
+typedef struct bsa_route_edit_rec {
+  int32_t aircraft, op, pos, flyby, wptype, bump_active;
+  double lat, lon, alt, spd;
+} bsa_route_edit_rec;
+/* bsa_route_edit: the batch on host arrays (the parity form).  The table and
+ * the state as bsa_fms_recover takes them; wptype: the waypoint type per table
+ * row, NULL = all 0 (only Route.dest, 3, matters: calcfp gives it toalt 0).
+ * iactwp, the mutable arrays of st and ap_alt are updated in place.  The new
+ * table comes back compacted in aircraft order: out_rows (room for cap_rows
+ * rows, cap_rows >= nrows + m), out_wptype (cap_rows, may be NULL), out_off /
+ * out_n (n each), *out_nrows. */
+int bsa_route_edit(bsa_ctx *ctx, int64_t n, int64_t nrows, const double *route_rows, const uint8_t *wptype,
+                   const int32_t *rt_off, const int32_t *rt_n, int32_t *iactwp, const double *lat, const double *lon,
+                   const double *alt, const double *tas, const double *gs, const double *trk, const double *bank,
+                   const bsa_fms_state *st, double *ap_alt, int64_t m, const bsa_route_edit_rec *rec, int64_t cap_rows,
+                   double *out_rows, uint8_t *out_wptype, int32_t *out_off, int32_t *out_n, int64_t *out_nrows);
+/* bsa_sim_route_edit: the batch on the resident sim's table, between batches of
+ * steps (guidance on, one rank).  Each edited route is rewritten behind the
+ * table's live tail and the aircraft repointed to it; the rows it held are dead.
+ * Once dead rows outnumber live ones the same call compacts the table in
+ * aircraft order.  The FMS clock and every kept detect state stay. */
+int bsa_sim_route_edit(bsa_ctx *ctx, int64_t m, const bsa_route_edit_rec *rec);
+/* bsa_sim_route_rows: live rows of the table (what bsa_sim_read_routes returns).
+ * bsa_sim_read_routes: the table compacted in aircraft order, as bsa_sim_set_fms
+ * takes it: rows (cap_rows >= live rows), wptype (may be NULL), off / n (n each).
+ * The sim's own table stays as it is. */
+int bsa_sim_route_rows(bsa_ctx *ctx, int64_t *live);
+int bsa_sim_read_routes(bsa_ctx *ctx, int64_t cap_rows, double *rows, uint8_t *wptype, int32_t *rt_off, int32_t *rt_n,
+                        int64_t *nrows);
+/* bsa_sim_route_stats: live rows, dead rows (the table's tail minus the live
+ * ones), the rows the last bsa_sim_route_edit wrote (the sum of the edited
+ * routes' new lengths) and the compactions since bsa_sim_set_fms. */
+int bsa_sim_route_stats(bsa_ctx *ctx, int64_t *live, int64_t *dead, int64_t *written, int64_t *compactions);
+
 /* ---------------------------------------------------------------- test seams
  * The two device primitives under the detect's row offsets, the bookkeeping's
  * CSR, the halo plan and the stopping stages' lists, over host arrays.  The

@@ -39,6 +39,11 @@ and outputs as small ``.npz`` files under ``tests/golden/``:
 * ``fms_<case>.npz``    -- ``Autopilot.update`` (autopilot.py:59-304): one forced FMS
                          tick (LNAV / VNAV guidance, waypoint switching) by the
                          reference's own Autopilot / ActiveWaypoint / Route objects
+* ``route_edit_<case>.npz`` -- ``Route.addwpt`` / ``delwpt`` / ``direct`` (route.py:472-613,
+                         808-838, 635-690) as sequences of commands on the reference's own Route
+                         objects; after a ``delwpt`` the capture removes ``wpflyby[idx]`` and calls
+                         ``calcfp()``, and a route left empty gets LNAV off
+                         (``--route-edit`` writes only this)
 * ``cd_nonfin_<case>.npz`` -- ``StateBasedCD.detect`` with a non-finite input
                          (``--nonfinite-only`` writes only these)
 * ``cdkwik_<case>.npz`` -- the opt-in KWIK variant: ``StateBasedCD.detect`` with
@@ -1591,6 +1596,170 @@ def run_recover(name, n, seed):
           % (name, n, seed + attempt, len(info), changed, os.path.getsize(path)))
 
 
+ROUTE_EDIT_SCENARIOS = (
+    'insert before the active waypoint (BEFORE)', 'insert at the active waypoint (BEFORE)',
+    'insert after the active waypoint (BEFORE)', 'AFTER the waypoint before the active one: iactwp moves up',
+    'AFTER the active waypoint', 'AFTER the first waypoint, active further on: iactwp moves up',
+    'append', 'first waypoint of an empty route', 'delete before the active waypoint', 'delete the active waypoint',
+    'delete after the active waypoint', 'delete the last waypoint', 'delete the only waypoint',
+    'direct to an earlier waypoint', 'direct to a later waypoint', 'two commands: AFTER, then delete',
+    'three commands: append, BEFORE it, direct to it', 'DELWPT *')
+
+
+def route_edit_commands(routes, st, seed):
+    """One scenario of ROUTE_EDIT_SCENARIOS per aircraft (k % 18; ``append`` where the route is too short for it):
+    list of (scenario, aircraft, kind, name, afterwp, beforewp, wptype, lat, lon, alt, spd, flyby) in the order they
+    are issued -- all first commands, then the second ones, then the third, so one aircraft's are never adjacent."""
+    rng = np.random.default_rng(seed + 2000)
+    seqs = []
+    for k, r in enumerate(routes):
+        n, a = len(r['wplat']), r['iactwp']
+        nm_ = ['WP%03d' % i for i in range(n)]
+
+        def add(name, after='', before='', wptype=1):
+            la = r['wplat'][0] if n else float(st['lat'][k])
+            lo = r['wplon'][0] if n else float(st['lon'][k])
+            spd = float(rng.choice([-999., float(np.float32(rng.uniform(90., 190.))), float(np.float32(rng.uniform(0.55, 0.86)))]))
+            alt = float(rng.choice([-999., float(np.float32(rng.uniform(500., 11000.))), float(np.float32(st['alt'][k] + 1.))]))
+            return ('add', name, after, before, wptype, float(np.float32(la + rng.uniform(-0.3, 0.3))),
+                    float(np.float32(lo + rng.uniform(-0.3, 0.3))), alt, spd, bool(rng.random() < 0.7))
+
+        def cmd(kind, name):
+            return (kind, name, '', '', 0, 0., 0., -999., -999., True)
+        sc = k % len(ROUTE_EDIT_SCENARIOS)
+        ok = [a >= 1, n >= 1, a + 1 < n, a >= 1, n >= 1, a >= 2, True, n == 0, a >= 1, n >= 2, a + 1 < n, n >= 2, n == 1,
+              a >= 1, a + 1 < n, n >= 2, n >= 1, n >= 2][sc]
+        if not ok:
+            sc = 7 if n == 0 else 6
+        seq = {0: lambda: [add('NWA', before=nm_[a - 1])], 1: lambda: [add('NWA', before=nm_[a])],
+               2: lambda: [add('NWA', before=nm_[a + 1])], 3: lambda: [add('NWA', after=nm_[a - 1])],
+               4: lambda: [add('NWA', after=nm_[a])], 5: lambda: [add('NWA', after=nm_[0])],
+               6: lambda: [add('AC%04d' % k, wptype=0) if k % 4 == 0 else add('NWA', after='NOSUCH' if k % 4 == 1 else '')],
+               7: lambda: [add('NWA')], 8: lambda: [cmd('del', nm_[a - 1])], 9: lambda: [cmd('del', nm_[a])],
+               10: lambda: [cmd('del', nm_[a + 1])], 11: lambda: [cmd('del', nm_[n - 1])], 12: lambda: [cmd('del', nm_[0])],
+               13: lambda: [cmd('direct', nm_[0])], 14: lambda: [cmd('direct', nm_[n - 1])],
+               15: lambda: [add('NWA', after=nm_[0]), cmd('del', nm_[n - 1])],
+               16: lambda: [add('NWA'), add('NWB', before='NWA'), cmd('direct', 'NWA')],
+               17: lambda: [cmd('del', '*')]}[sc]()
+        seqs.append([(sc, k) + c for c in seq])
+    out = []
+    while any(seqs):
+        for s in seqs:
+            if s:
+                out.append(s.pop(0))
+    return out
+
+
+def run_route_edit(name, n, seed):
+    """ADDWPT / DELWPT / DIRECT by the reference's own Route.addwpt / delwpt / direct (route.py:472-613, 808-838,
+    635-690) on real Route / Autopilot / ActiveWaypoint objects over a stand-in bs.traf and a stub bs.navdb whose
+    lookups return the command's position.  The commands are resolved to edit records by bluesky_amd.fms.RouteNames
+    and applied by tests/route_np.py; both are asserted bitwise equal to the reference on the table, iactwp, actwp.*,
+    swlnav, selspd and the ap.* targets.  Capture rules: after the reference's delwpt the capture
+    removes wpflyby[idx] and calls calcfp() (this fork's delwpt does neither); DELWPT * re-initialises the Route; a
+    route left empty gets swlnav False (the reference's autopilot cannot fly an empty route).  The seed moves on until
+    no comparison of a direct lies within 1e-9 relative of equality."""
+    import bluesky as bs
+    from bluesky_amd import fms as bfms
+    from tests import recover_np, route_np
+    for attempt in range(50):
+        routes, st, _ = recover_case(n, seed + attempt)
+        cmds = route_edit_commands(routes, st, seed + attempt)
+        ap, wp, traf = ref_autopilot(routes, st)
+        names0 = [list(R.wpname) for R in ap.route]
+        types0 = [list(R.wptype) for R in ap.route]
+        rn = bfms.RouteNames(names0, types0)
+        recs, per_cmd = [], []
+        for c in cmds:
+            sc, k, kind, nam, aft, bef, wt, la, lo, al, sp, fb = c
+            r = (rn.addwpt(k, nam, wt, la, lo, al, sp, afterwp=aft, beforewp=bef, flyby=fb) if kind == 'add' else
+                 rn.delwpt(k, nam) if kind == 'del' else rn.direct(k, nam))
+            per_cmd.append(len(r))
+            recs += r
+        # the table before: the reference's own calcfp; iactwp -1 on the empty routes
+        cnt = np.array([R.nwp for R in ap.route], np.int32)
+        off = (np.cumsum(cnt) - cnt).astype(np.int32)
+        rows = ref_route_rows(ap.route)
+        wptype = np.array([t for R in ap.route for t in R.wptype], np.uint8)
+        with np.errstate(all='ignore'):
+            if route_np.near_threshold(st, rows, off, cnt, recs, wptype).any():
+                continue
+            mine = route_np.edit(st, rows, off, cnt, recs, wptype)
+        break
+    else:
+        raise AssertionError('no seed clear of the thresholds')
+    seen = {c[0] for c in cmds}
+    assert seen == set(range(len(ROUTE_EDIT_SCENARIOS))), sorted(set(range(len(ROUTE_EDIT_SCENARIOS))) - seen)
+    stub = types.SimpleNamespace(wplat=[0.], wplon=[0.], aptlat=[], aptlon=[], getwpidx=lambda *a: 0, getaptidx=lambda *a: -1)
+    traf.id = ['AC%04d' % k for k in range(n)]
+    saved, saved_db = getattr(bs, 'traf', None), getattr(bs, 'navdb', None)
+    bs.traf, bs.navdb = traf, stub
+    try:
+        with np.errstate(all='ignore'):
+            for c in cmds:
+                sc, k, kind, nam, aft, bef, wt, la, lo, al, sp, fb = c
+                R = ap.route[k]
+                if kind == 'add':
+                    stub.wplat[0], stub.wplon[0] = la, lo
+                    R.swflyby = fb
+                    assert R.addwpt(k, nam, wt, la, lo, al, sp, aft, bef) >= 0
+                elif kind == 'del' and nam == '*':
+                    R.delwpt(nam)
+                    R.calcfp()
+                elif kind == 'del':
+                    idx = max(i for i, x in enumerate(R.wpname) if x.upper() == nam.upper())
+                    assert R.delwpt(nam) is True
+                    del R.wpflyby[idx]
+                    R.calcfp()
+                else:
+                    assert R.direct(k, nam) is True
+                if R.nwp == 0:
+                    traf.swlnav[k] = False
+    finally:
+        bs.traf, bs.navdb = saved, saved_db
+    ref = ref_fms_state(ap, wp, traf)
+    for k in route_np.OUTPUTS + route_np.UNTOUCHED:
+        if k in ref:
+            assert np.array_equal(np.asarray(mine[4][k], dtype=ref[k].dtype), ref[k], equal_nan=True), 'helper != reference %s' % k
+    rcnt = np.array([len(R.wplat) for R in ap.route], np.int32)
+    assert np.array_equal(mine[2], rcnt) and np.array_equal(mine[0], ref_route_rows(ap.route))
+    assert np.array_equal(mine[3], np.array([t for R in ap.route for t in R.wptype], np.uint8))
+    assert [list(R.wpname) for R in ap.route] == rn.names, 'RouteNames != the reference names'
+    out = {k: v for k, v in st.items() if k != 'ax'}
+    def U(xs):
+        xs = list(xs)
+        return np.array(xs or [''], dtype='U16')[:len(xs)]
+    out.update(route_rows=rows, rt_off=off, rt_n=cnt, wptype=wptype, names=U(x for r in names0 for x in r),
+               cmd_scenario=np.array([c[0] for c in cmds], np.int32), cmd_aircraft=np.array([c[1] for c in cmds], np.int32),
+               cmd_kind=U(c[2] for c in cmds), cmd_name=U(c[3] for c in cmds), cmd_after=U(c[4] for c in cmds),
+               cmd_before=U(c[5] for c in cmds), cmd_wptype=np.array([c[6] for c in cmds], np.int32),
+               cmd_lat=np.array([c[7] for c in cmds]), cmd_lon=np.array([c[8] for c in cmds]),
+               cmd_alt=np.array([c[9] for c in cmds]), cmd_spd=np.array([c[10] for c in cmds]),
+               cmd_flyby=np.array([c[11] for c in cmds], bool), cmd_records=np.array(per_cmd, np.int32),
+               scenarios=U(ROUTE_EDIT_SCENARIOS), seed=seed + attempt, numpy_version=np.array(np.__version__),
+               out_route_rows=mine[0], out_rt_off=mine[1], out_rt_n=mine[2], out_wptype=mine[3])
+    for f in bfms._lib.ROUTE_REC_DTYPE.names:
+        out['rec_' + f] = np.array([r[f] for r in recs])
+    out.update({'out_' + k: ref[k] for k in route_np.OUTPUTS + ('ap_trk', 'ap_tas', 'ap_vs', 'selalt')})
+    path = os.path.join(OUT, 'route_edit_%s.npz' % name)
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) < 1000000, os.path.getsize(path)
+    print('route_edit_%-12s N=%5d seed %d commands %d records %d, %d bytes' % (name, n, seed + attempt, len(cmds), len(recs),
+                                                                               os.path.getsize(path)))
+
+
+def ref_route_rows(routes):
+    """The route table of reference Route objects after calcfp(), from their own wpxtoalt / wptoalt / wpdirfrom."""
+    rows = []
+    for R in routes:
+        n = len(R.wplat)
+        assert len(R.wpflyby) == n and len(R.wpxtoalt) == n and len(R.wpdirfrom) == n
+        for i in range(n):
+            rows.append((R.wplat[i], R.wplon[i], R.wpalt[i], R.wpspd[i], R.wpxtoalt[i], R.wptoalt[i],
+                         1.0 if R.wpflyby[i] else 0.0, R.wpdirfrom[i] if i + 1 < n else -999.))
+    return np.array(rows, dtype=np.float64).reshape(-1, 8)
+
+
 def recover_flight_case(n, seed):
     """n aircraft at 100-150 m/s on routes of 2-4 waypoints.  The first 18 are six
     triples far from each other: an ownship and, crossing its track at 120 degrees
@@ -2028,6 +2197,9 @@ def main():
         run_recover('recover2000', 2000, 81)
         run_recover_flight('recover_flight', 48, 83)
         return
+    if '--route-edit' in sys.argv:
+        run_route_edit('cmds300', 300, 91)
+        return
     if '--recover-flight-only' in sys.argv:
         run_recover_flight('recover_flight', 48, 83)
         return
@@ -2083,6 +2255,7 @@ def main():
     run_fms_flight('flight64', 64, 79)
     run_recover('recover2000', 2000, 81)
     run_recover_flight('recover_flight', 48, 83)
+    run_route_edit('cmds300', 300, 91)
     run_turb('woosh300', 300, 97)
     for case in geo_cases():
         run_geo(*case)
