@@ -204,6 +204,9 @@ SIGNATURES.update({
     'bsa_exact_fusion_stats': (ctypes.c_int, [_vp, _c_i64p]),
     'bsa_set_symmetric_sweep': (ctypes.c_int, [_vp, ctypes.c_int]),
     'bsa_symmetric_sweep_stats': (ctypes.c_int, [_vp, _c_i64p]),
+    'bsa_set_lean_pairs': (ctypes.c_int, [_vp, ctypes.c_int]),
+    'bsa_lean_pairs_stats': (ctypes.c_int, [_vp, _c_i64p]),
+    'bsa_listed_items': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64, _c_i64p]),
     'bsa_sim_comm_stats': (ctypes.c_int, [_vp, _c_i64p]),
     'bsa_sim_set_atmos': (ctypes.c_int, [_vp, ctypes.c_int]),
     'bsa_sim_read_atmos': (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp]),
@@ -1762,6 +1765,26 @@ class Context:
         v = np.zeros(2, np.int64)
         self.check(self.lib.bsa_symmetric_sweep_stats(self.h, ptr(v, _c_i64p)), 'bsa_symmetric_sweep_stats')
         return dict(detects=int(v[0]), last=bool(v[1]), level=int(v[1]))
+
+    def set_lean_pairs(self, on=True):
+        """bsa_set_lean_pairs: the CD steps of a step() call before its last skip the pair lists
+        (default on; results never depend on it)."""
+        self.check(self.lib.bsa_set_lean_pairs(self.h, int(on)), 'bsa_set_lean_pairs')   # (2: bsaccel.h, a testing aid)
+
+    def lean_pairs_stats(self):
+        """bsa_lean_pairs_stats: CD steps since the sim's init that ran lean / placed their pair lists."""
+        v = np.zeros(2, np.int64)
+        self.check(self.lib.bsa_lean_pairs_stats(self.h, ptr(v, _c_i64p)), 'bsa_lean_pairs_stats')
+        return dict(lean=int(v[0]), full=int(v[1]))
+
+    def listed_items(self, tier):
+        """bsa_listed_items: the list slots of the items listed for the next detect, sorted."""
+        n = np.zeros(1, np.int64)
+        self.check(self.lib.bsa_listed_items(self.h, int(tier), None, 0, ptr(n, _c_i64p)), 'bsa_listed_items')
+        out = np.zeros(max(int(n[0]), 1), np.uint32)
+        self.check(self.lib.bsa_listed_items(self.h, int(tier), ptr(out, ctypes.POINTER(ctypes.c_uint32)), len(out),
+                                             ptr(n, _c_i64p)), 'bsa_listed_items')
+        return np.sort(out[:int(n[0])])
 
     def sim_probe_rank(self, rank, nranks):
         """bsa_sim_probe_rank (measurement aid): the one-rank sim's steps play rank `rank` of `nranks`."""

@@ -85,7 +85,8 @@ const DetectEnv &detect_env() {
                      std::min(std::max(num("BSA_PF_SYM", 2), 0), 2),
                      num("BSA_K24", 1) != 0,
                      (k4b == 64 || k4b == 128 || k4b == 256) ? k4b : 64,
-                     num("BSA_SIM_PREP", 1) != 0};
+                     num("BSA_SIM_PREP", 1) != 0,
+                     num("BSA_LEAN_K2", 1) != 0};
   }();
   return env;
 }
@@ -675,8 +676,10 @@ static int detect_rank(DetectRun &R) {
   const DetectRequest &q = R.q;
   MvpFuse mf{};
   if (q.mvp) {
-    if (!ensure(c, c->mvp_pdv, std::max<unsigned long long>(cap, 1) * sizeof(double4), "mvp pair dv") ||
-        !ensure(c, c->mvp_pfl, std::max<unsigned long long>(cap, 1), "mvp pair flags"))
+    // (the lean K2 folds a block beyond its LDS arrays through the block's own slice, kRankRows x B entries)
+    const unsigned long long npair = std::max<unsigned long long>(
+        {cap, 1ull, q.lean_k2 ? (unsigned long long)rank_blocks(nrows) * kRankRows * (unsigned long long)B : 0ull});
+    if (!ensure(c, c->mvp_pdv, npair * sizeof(double4), "mvp pair dv") || !ensure(c, c->mvp_pfl, npair, "mvp pair flags"))
       return -1;
     mf.p = *q.mvp;
     mf.in = MvpPairIn{q.gse, q.gsn, q.vs, q.alt, q.noreso, p.home ? (const unsigned *)c->id2h.p : nullptr};
@@ -691,13 +694,20 @@ static int detect_rank(DetectRun &R) {
   }
   if (B) {
     const bool hl = p.fuse && R.hn.cost;  // the heavy-item listing moves here from K1b
-    if (launch_rowblk(R, hl)) return -1;
-    const RankLaunch rl{(unsigned)rank_blocks(nrows), nrows, R.dcnt, cap, (unsigned *)c->rowoff.p,
+    // lean: no block sums -- the listing rides on extra workgroups of the K2 + K4' launch
+    const bool lean = q.lean_k2 && q.keep_k2;
+    if (!lean && launch_rowblk(R, hl)) return -1;
+    RankLaunch rl{(unsigned)rank_blocks(nrows), nrows, R.dcnt, cap, (unsigned *)c->rowoff.p,
                         (unsigned *)c->rowcnt.p, (const uint2 *)c->kbuck.p, B, (const double *)c->cpay.p, rb,
                         (int *)c->out_ci.p, (int *)c->out_cj.p, (double *)c->out_pay.p, (int *)c->out_li.p,
                         (int *)c->out_lj.p, (unsigned long long *)c->stats.p, q.gate, R.build, mf,
                         (unsigned char *)c->inconf.p, (unsigned long long *)c->tcpamax.p,
                         (Counters *)c->counters2.p, (unsigned long long *)c->workq2.p, R.nfa, R.hk_word};
+    if (lean) {
+      rl.lean = true;
+      rl.heavy = hl ? kHeavyBlocks : 0u;
+      if (hl) rl.hn = R.hn;
+    }
     if (q.keep_k2) {  // the step launches it fused with K4' (k24_launch)
       R.res.k2 = rl;
       R.res.k2_kept = true;

@@ -187,14 +187,7 @@ struct HeavyArgs {
   unsigned *cost;           // per slot: s_memrealtime ticks of its units (summed)
   unsigned epoch;
 };
-struct HeavyNext {
-  unsigned *cost;           // read and zeroed
-  unsigned *list[2], *count, *flag;
-  unsigned epoch;           // the next detect's
-  unsigned thresh[2];       // ticks (100 MHz)
-  const unsigned long long *work;  // [1] near, [2] far items of this detect's list
-  unsigned long long icap;
-};
+// (HeavyNext, the next detect's listing: bsa_internal.h, with RankLaunch)
 #ifndef BSA_PF_WAVES_PER_EU
 #define BSA_PF_WAVES_PER_EU 4
 #endif

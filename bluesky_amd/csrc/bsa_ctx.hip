@@ -709,6 +709,39 @@ int bsa_symmetric_sweep_stats(bsa_ctx *c, int64_t *out2) {
   return 0;
 }
 
+int bsa_set_lean_pairs(bsa_ctx *c, int on) {
+  if (!c) return -1;
+  if (on < 0 || on > 2) return bsa::fail(c, "lean pairs: 0 (off), 1 (on) or 2 (the call's last CD step too: testing)");
+  c->lean_on = on;  // (the next bsa_sim_step call's plan; nothing kept depends on it)
+  return 0;
+}
+
+int bsa_lean_pairs_stats(bsa_ctx *c, int64_t *out2) {
+  if (!c || !out2) return -1;
+  out2[0] = c->clk.lean_cd;
+  out2[1] = c->clk.full_cd;
+  return 0;
+}
+
+int bsa_listed_items(bsa_ctx *c, int tier, uint32_t *slots, int64_t cap, int64_t *count) {
+  if (!c || !count) return -1;
+  if (tier < 0 || tier > 1) return bsa::fail(c, "the listing has tiers 0 and 1");
+  *count = 0;
+  if (!c->hv_cnt.p || c->hv_epoch == 0) return 0;  // no detect has listed anything
+  BSA_HIP(c, hipSetDevice(c->device));
+  const unsigned b = (c->hv_epoch + 1) & 1;  // the next detect's lists (heavy_setup)
+  unsigned cn[4];
+  BSA_HIP(c, hipMemcpyAsync(cn, c->hv_cnt.p, sizeof(cn), hipMemcpyDeviceToHost, c->stream));
+  BSA_HIP(c, hipStreamSynchronize(c->stream));
+  const int64_t m = cn[2 * b + tier];
+  *count = m;
+  if (m == 0 || m > cap) return 0;
+  if (!slots) return bsa::fail(c, "NULL listed-items buffer");
+  BSA_HIP(c, hipMemcpyAsync(slots, c->hv_list[2 * b + tier].p, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+  BSA_HIP(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 int bsa_set_candidate_reuse(bsa_ctx *c, int on, double sigma_h, double sigma_v) {
   if (!c) return -1;
   if (on && !(sigma_h > 0.0 && sigma_h < 1e6 && sigma_v > 0.0 && sigma_v < 1e5))

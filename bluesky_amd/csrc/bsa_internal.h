@@ -197,6 +197,9 @@ struct Counters {
   unsigned long long stamp[8];
   unsigned long long cshard[kCandShards][16];  // candidates per shard (word 0 of each line)
   unsigned long long gpart[32][16];  // sub-groups swept, per prefilter workgroup shard (summed into groups by K2)
+  // the exact evaluation counted a conflict (plain stores of 1, one per wave): the lean K2 + K4' gates MVP with it
+  // (asas.py:486-487) where the full form has P, the sum.  Last, so that no other word moves
+  unsigned long long any_conf;
 };
 
 // ---------------------------------------------------------------- buffers
@@ -247,6 +250,7 @@ struct StepClocks {
   double adsb_simt = 0.0;                  // ADS-B (3.32): the simt the next step's adsb.update is called with,
   int64_t adsb_call = 0;                   // ... the call number of its draws (+ 1 per step with noise on),
   int adsb_cur = 0;                        // ... and which lastupdate buffer it reads (it writes the other)
+  int64_t lean_cd = 0, full_cd = 0;        // CD steps whose K2 ran lean (StepPlan::lean) / placed its pair lists
 };
 
 struct Ctx {
@@ -458,6 +462,9 @@ struct Ctx {
   int sym_on = 2;           // bsa_set_symmetric_sweep: the level allowed (DetectPlan::sym)
   int last_sym = 0;         // the last detect's level (> 0: it swept each unordered tile pair once)
   int64_t sym_count = 0;    // ... and how many did (bsa_symmetric_sweep_stats)
+  int lean_on = 1;          // bsa_set_lean_pairs: a batch's detects before its last skip the pair lists (StepPlan::lean;
+                            // 2: its last one too, a testing aid)
+  int64_t batch_target = 0; // clk.steps at the end of the bsa_sim_step call being enqueued (StepPlan::lean)
   // region layout agreement (comm_halo): every rank's send lengths / offsets
   // are compared with every receiver's expectation whenever the layout may have
   // changed -- a new capacity generation (init, regrowth: collective events) or
@@ -1015,6 +1022,16 @@ struct MvpFuse {
   uint8_t *pfl;
   double4 *rowdv;  // k_rank_rows: each row's folded dv (mvp_fold), or NULL
 };
+// the next detect's listed items (HeavyArgs, bsa_cd_args.h): what heavy_next (bsa_rank.hip) reads and appends to
+struct HeavyNext {
+  unsigned *cost;           // read and zeroed
+  unsigned *list[2], *count, *flag;
+  unsigned epoch;           // the next detect's
+  unsigned thresh[2];       // ticks (100 MHz)
+  const unsigned long long *work;  // [1] near, [2] far items of this detect's list
+  unsigned long long icap;
+};
+constexpr unsigned kHeavyBlocks = 64;  // extra workgroups for the listing (k_rowblk's; the lean k_rank_rows')
 // k_rank_rows' arguments (a value, so that the step can launch K2 fused with its K4': k24_launch)
 struct RankLaunch {
   unsigned grid;
@@ -1038,6 +1055,11 @@ struct RankLaunch {
   unsigned long long *wnext;
   NfArgs nf;
   unsigned long long *hkp;  // HK: the prediction word K2 moves into gate[2] (NULL: none / fused K4' publishes it)
+  // the lean form (DetectRequest::lean_k2, fused with K4' only): no block sums, no pair lists; grid = the row blocks
+  // + heavy extra workgroups that list the next detect's items (hn), k_rowblk's part on a full detect
+  bool lean = false;
+  unsigned heavy = 0;
+  HeavyNext hn{};
 };
 struct DetectRequest {
   double rpz = 0.0, hpz = 0.0, tla = 0.0;
@@ -1052,6 +1074,7 @@ struct DetectRequest {
   const double *gse = nullptr, *gsn = nullptr, *vs = nullptr, *alt = nullptr;
   const uint8_t *noreso = nullptr;     // NORESO list or NULL
   bool keep_k2 = false;                // K2 (k_rank_rows) is not launched but returned, for a launch fused with K4'
+  bool lean_k2 = false;                // ... in its lean form (StepPlan::lean): nothing reads this detect's pair lists
 };
 struct DetectResult {
   bool pairs_done = false;   // K2 produced MVP's per-pair vectors
@@ -1090,6 +1113,7 @@ struct DetectEnv {
   bool k24;            // BSA_K24=0: K2 and K4' as two launches
   int k4_block;        // BSA_K4_BLOCK=64/128/256: K4' workgroup size (anything else: 64)
   bool sim_prep;       // BSA_SIM_PREP=0: K4' does not prepare the next detect's records
+  bool lean_k2;        // BSA_LEAN_K2=0: every detect of a batch places its pair lists (StepPlan::lean off)
 };
 const DetectEnv &detect_env();
 #ifdef BSA_PF_TRACE

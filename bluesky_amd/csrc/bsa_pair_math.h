@@ -85,6 +85,8 @@ __device__ __forceinline__ void exact_bucket(const PairResult &o, int row, unsig
                                              unsigned *__restrict__ rowcnt, uint2 *__restrict__ kb,
                                              Counters *__restrict__ cnt) {
   if (o.conf) {
+    // the detect's "any conflict" word (the lean K2's MVP gate): the first of the wave's lanes here stores it
+    if (__lane_id() == (unsigned)__ffsll((long long)__ballot(1)) - 1u) cnt->any_conf = 1ull;
     double *rec = cpay + id * kPayStride;
     rec[0] = __longlong_as_double((long long)py);
     rec[1] = o.qdr;

@@ -42,18 +42,19 @@ __device__ __forceinline__ bool cand_overflow(const Counters *cnt, unsigned long
 // least a threshold is listed (two tiers), its cost word zeroed.  Runs on the
 // grid's last lanes (K1b: the lanes past the candidate count; k_rowblk's extra
 // blocks when K1b is fused into the prefilter -- in K2's launch, whose lanes
-// would have had the time, its code cost K2 +5 us even when skipped).
-// Called by every thread of a block (block-uniform trips: it synchronises the
-// block).  One returning atomic per tier per BLOCK and trip, the block's
+// would have had the time, its code cost K2 +5 us even when skipped; the lean
+// K2 + K4', which has no k_rowblk in front of it, appends workgroups that do
+// nothing else).  Called by every thread of workgroup blk of the nblk that
+// take part (block-uniform trips: it synchronises the block).  One returning atomic per tier per BLOCK and trip, the block's
 // waves placed by an LDS prefix (one per wave contended on two words: ~350
 // at the 100k box, serialised at ~88 per us, were most of k_rowblk's 5.7 us).
 constexpr int kHeavyMaxWaves = 16;
-__device__ __forceinline__ void heavy_next(const HeavyNext &hn) {
+__device__ __forceinline__ void heavy_next(const HeavyNext &hn, unsigned nblk, unsigned blk) {
   __shared__ unsigned hcnt[2][kHeavyMaxWaves];
   __shared__ unsigned hbase[2];
   const unsigned long long inear = hn.work[1], m = inear + hn.work[2];
-  const unsigned long long nt = (unsigned long long)gridDim.x * blockDim.x;
-  const unsigned long long g0 = (unsigned long long)blockIdx.x * blockDim.x;
+  const unsigned long long nt = (unsigned long long)nblk * blockDim.x;
+  const unsigned long long g0 = (unsigned long long)blk * blockDim.x;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, W = (int)(blockDim.x >> 6);
   // trip j: lane k = nt - 1 - (g0 + t) + j nt; the block's smallest is nt - g0 - blockDim.x + j nt
   for (unsigned long long kb = nt - g0 - blockDim.x; kb < m; kb += nt) {
@@ -118,7 +119,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == kEx
     int B,
     unsigned *__restrict__ rctl, const Snap *__restrict__ snap_cur, Snap *__restrict__ snap_build, int nsnap,
     HeavyNext hn) {
-  if (hn.cost) heavy_next(hn);  // the next detect's listed items, on the grid's last lanes (idle: past the candidates)
+  if (hn.cost) heavy_next(hn, gridDim.x, blockIdx.x);  // the next detect's listed items, on the grid's last lanes (idle: past the candidates)
   if (cand_overflow(cnt, cap)) return;  // the caller retries with more room
   if (rctl) {  // reuse: after a build this detect's state becomes the snapshot
     const bool built = rctl[0] != 0;
@@ -356,12 +357,11 @@ __global__ __launch_bounds__(256) void k_rank(int nrows, Counters *__restrict__ 
 // read: k_rank_rows checks the overflow itself)
 // k_rowblk: 16 waves per block, wave w of block b sums row block 16 b + w
 constexpr int kRowblkWaves = 16;
-constexpr unsigned kHeavyBlocks = 64;  // k_rowblk's extra blocks for the heavy-item listing (65 536 lanes)
 __global__ __launch_bounds__(64 * kRowblkWaves) void k_rowblk(int nrows, unsigned *__restrict__ rowcnt, HeavyNext hn) {
   // (K1b fused into the prefilter: the next detect's listed items here, on
   // every lane of the grid -- the host adds kHeavyBlocks blocks past the
   // row-block sums for them, ~1 slot per lane at the 100k box)
-  if (hn.cost) heavy_next(hn);
+  if (hn.cost) heavy_next(hn, gridDim.x, blockIdx.x);
   const int nb = rank_blocks(nrows), b = blockIdx.x * kRowblkWaves + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (b >= nb) return;
   unsigned c = 0, l = 0;
@@ -381,7 +381,15 @@ __global__ __launch_bounds__(64 * kRowblkWaves) void k_rowblk(int nrows, unsigne
   }
 }
 
-template <bool K24>
+// LEAN (with K24 only; DESIGN.md 3.4, StepPlan::lean): a detect whose pair lists nobody can read before the next
+// detect overwrites them.  No block sums (no k_rowblk in front), so no cb / lb / P / L: none of ci, cj, out, li,
+// lj, rowoff, cnt->conf / los is written and the LoS pairs are not visited.  Everything per row and per block is
+// as in the full form, bit for bit: the block-local offsets, each conflict pair's rank and MVP vector at
+// so[lo] + rank, the folds in the same order, K4'.  MVP's gate (P != 0 in the full form) is Counters::any_conf; a
+// block beyond its LDS arrays folds through its own slice of pdv / pfl (kRankRows x B entries from b kRankRows B:
+// every row's pairs fit its bucket) and takes tcpamax, a maximum, from its rows' buckets.  The workgroups past the
+// row blocks (hvn > 0 of them) list the next detect's items (heavy_next), k_rowblk's part on a full detect
+template <bool K24, bool LEAN>
 __global__ __launch_bounds__(kRankThreads) void k_rank_rows(int nrows, Counters *__restrict__ cnt, unsigned long long cap,
                                                          unsigned *__restrict__ rowoff,
                                                          unsigned *__restrict__ rowcnt,
@@ -396,7 +404,9 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_rows(int nrows, Counters 
                                                          unsigned long long *__restrict__ tcpamax_bits,
                                                          Counters *__restrict__ cnext,
                                                          unsigned long long *__restrict__ wnext, K24Args ka,
-                                                         NfArgs nf, unsigned long long *__restrict__ hkp) {
+                                                         NfArgs nf, unsigned long long *__restrict__ hkp, HeavyNext hn,
+                                                         unsigned hvn) {
+  static_assert(K24 || !LEAN, "the lean form is the fused K2 + K4' only");
   constexpr int W = kRankThreads / 64;
   __shared__ unsigned red[4][W];
   __shared__ unsigned soff[2][kRankRows + 1];  // the block's rows' exclusive offsets (conf, LoS), + total
@@ -405,6 +415,10 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_rows(int nrows, Counters 
   __shared__ uint8_t sfl[kRankLds];
   __shared__ double stc[kRankLds];  // ... and their tcpa (tcpamax)
   const int nb = rank_blocks(nrows), b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  if (LEAN && b >= nb) {  // (block-uniform, before any barrier: these workgroups hold no rows)
+    heavy_next(hn, hvn, (unsigned)(b - nb));
+    return;
+  }
   const unsigned *bcnt = rowcnt + 2 * (nrows + 1);
   const bool rowlane = t < kRankRows;  // lanes past the block's rows only place pairs
   const int r = rowlane ? b * kRankRows + t : nrows;
@@ -412,6 +426,7 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_rows(int nrows, Counters 
   // non-finite tcpa inputs (NfArgs; loaded with the counts)
   const bool nfcol = nf.word && *nf.word == nf.epoch;
   const unsigned nfrow = nf.rowbad && r < nrows ? nf.rowbad[r] : 0u;
+  const unsigned long long anyc = LEAN ? cnt->any_conf : 0ull;  // (the exact evaluation's launch is complete)
   // the next detect's per-row counts and counters start at zero (its K0z
   // launch is skipped, detect_enqueue): this block's counts are read, the
   // next detect's counter block (cnext / wnext, double-buffered) is idle
@@ -427,14 +442,14 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_rows(int nrows, Counters 
   const bool ovf = cand_overflow(cnt, cap);
   // P / L = all conflict / LoS pairs, cb / lb = those of the blocks before b
   unsigned P = 0, L = 0, cb = 0, lb = 0;
-  for (int q = t; q < nb; q += kRankThreads) {
-    const unsigned x = bcnt[q], y = bcnt[nb + q];
-    P += x;
-    L += y;
-    cb += q < b ? x : 0u;
-    lb += q < b ? y : 0u;
-  }
-  {
+  if (!LEAN) {
+    for (int q = t; q < nb; q += kRankThreads) {
+      const unsigned x = bcnt[q], y = bcnt[nb + q];
+      P += x;
+      L += y;
+      cb += q < b ? x : 0u;
+      lb += q < b ? y : 0u;
+    }
     unsigned v[4] = {P, L, cb, lb};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -453,10 +468,12 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_rows(int nrows, Counters 
   unsigned wc = 0, wl = 0, tc = 0, tl = 0;
 #pragma unroll
   for (int q = 0; q < W; ++q) {
-    P += red[0][q];
-    L += red[1][q];
-    cb += red[2][q];
-    lb += red[3][q];
+    if (!LEAN) {
+      P += red[0][q];
+      L += red[1][q];
+      cb += red[2][q];
+      lb += red[3][q];
+    }
     wc += q < w ? wsum[0][q] : 0u;
     wl += q < w ? wsum[1][q] : 0u;
     tc += wsum[0][q];
@@ -465,8 +482,10 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_rows(int nrows, Counters 
   if (b == 0 && t == 0) {
     unsigned long long ncand = 0;  // candidates written (the prefilter's per-workgroup counts; the list is dense)
     for (int q = 0; q < 32; ++q) ncand += cnt->gpart[q][1];
-    cnt->conf = ovf ? 0 : P;
-    cnt->los = ovf ? 0 : L;
+    if (!LEAN) {
+      cnt->conf = ovf ? 0 : P;
+      cnt->los = ovf ? 0 : L;
+    }
     cnt->cand = ncand;
     unsigned long long g = 0;
     for (int q = 0; q < 32; ++q) g += cnt->gpart[q][0];
@@ -485,7 +504,7 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_rows(int nrows, Counters 
     }
     if (gate) {
       gate[0] = ovf ? kGateOverflow : (nfcol ? kGateNonfinite : 0);
-      gate[1] = ovf ? 0 : P;
+      gate[1] = ovf ? 0 : (LEAN ? anyc : (unsigned long long)P);  // (read as "any conflict": mvp_row)
       gate[2] = hkp && *hkp ? 1ull : 0ull;  // HK: this detect's prediction, all-reduced with the gate
     }
     if (hkp) *hkp = 0ull;  // (the word's next writer is two detects on)
@@ -519,18 +538,20 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_rows(int nrows, Counters 
     soff[0][kRankRows] = tc;
     soff[1][kRankRows] = tl;
   }
-  if (r < nrows) {
+  if (!LEAN && r < nrows) {
     rowoff[r] = cb + ec;
     rowoff[nrows + 1 + r] = P + lb + el;
   }
-  if (b == nb - 1 && t == 0) {
+  if (!LEAN && b == nb - 1 && t == 0) {
     rowoff[nrows] = P;
     rowoff[2 * nrows + 1] = P + L;
   }
   __syncthreads();
   const bool lds = tc <= (unsigned)kRankLds;  // the block's conflict pairs fit the LDS arrays
   const bool lds_fold = mf.rowdv && lds;
-  for (unsigned x = t; x < tc + tl; x += kRankThreads) {
+  // where the block's pairs start in pdv / pfl: their global position, or (lean) the block's own slice
+  const size_t fb = LEAN ? (size_t)b * kRankRows * (size_t)B : (size_t)cb;
+  for (unsigned x = t; x < (LEAN ? tc : tc + tl); x += kRankThreads) {
     const bool conf = x < tc;
     const unsigned q = conf ? x : x - tc;
     const unsigned *so = soff[conf ? 0 : 1];
@@ -564,13 +585,15 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_rows(int nrows, Counters 
     }
     if (conf) {
       const unsigned pos = cb + so[lo] + rank;
-      ci[pos] = rb + row;
-      cj[pos] = (int)e.x;
+      if (!LEAN) {
+        ci[pos] = rb + row;
+        cj[pos] = (int)e.x;
+      }
       double pay[5];
 #pragma unroll
       for (int f = 0; f < 5; ++f) {
         pay[f] = cpay[(size_t)e.y * kPayStride + 1 + f];
-        out[(size_t)f * P + pos] = pay[f];
+        if (!LEAN) out[(size_t)f * P + pos] = pay[f];
       }
       const unsigned jh = (unsigned)__double_as_longlong(cpay[(size_t)e.y * kPayStride]);  // (K1b: home column)
       if (lds) stc[so[lo] + rank] = pay[2];
@@ -588,11 +611,11 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_rows(int nrows, Counters 
           sdv[so[lo] + rank] = dv;
           sfl[so[lo] + rank] = fl;
         } else {
-          mf.pdv[pos] = dv;
-          mf.pfl[pos] = fl;
+          mf.pdv[fb + so[lo] + rank] = dv;
+          mf.pfl[fb + so[lo] + rank] = fl;
         }
       }
-    } else {
+    } else if (!LEAN) {
       const unsigned pos = lb + so[lo] + rank;
       li[pos] = rb + row;
       lj[pos] = (int)e.x;
@@ -610,7 +633,10 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_rows(int nrows, Counters 
     inconf[r] = c ? 1 : 0;
     unsigned long long tm = 0ull;
     for (unsigned k = 0; k < c; ++k) {
-      const double tq = lds ? stc[ec + k] : out[(size_t)2 * P + cb + ec + k];
+      // (lean, beyond LDS: from the row's bucket, in the bucket's order -- a maximum)
+      const double tq = lds    ? stc[ec + k]
+                        : LEAN ? cpay[(size_t)kb[(size_t)r * B + k].y * kPayStride + 3]
+                               : out[(size_t)2 * P + cb + ec + k];
       const unsigned long long bits = (unsigned long long)__double_as_longlong(tq);
       if (tq > 0.0 && bits > tm) tm = bits;
     }
@@ -618,13 +644,13 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_rows(int nrows, Counters 
     // as np.max propagates it
     tcpamax_bits[r] = nfcol || nfrow ? kNanBits : tm;
     if (mf.rowdv)
-      mf.rowdv[r] = lds_fold ? mvp_fold(sdv, sfl, ec, ec + c) : mvp_fold(mf.pdv, mf.pfl, cb + ec, cb + ec + c);
+      mf.rowdv[r] = lds_fold ? mvp_fold(sdv, sfl, ec, ec + c) : mvp_fold(mf.pdv + fb, mf.pfl + fb, ec, ec + c);
   }
   if (K24) {  // K4' of this workgroup's rows (k_sim_pilot_kin<true, PREP>'s body), every lane
     __shared__ unsigned long long sgate[2];
     if (t == 0) {
       sgate[0] = 0ull;
-      sgate[1] = P;
+      sgate[1] = LEAN ? anyc : (unsigned long long)P;
     }
     __syncthreads();
     if (b == 0 && t == 0) *ka.d.steps_done += 1;
@@ -708,10 +734,11 @@ int launch_rowblk(const DetectRun &R, bool heavy) {
 }
 // ... and one K2 launch (k_rank_rows; RankLaunch: bsa_internal.h), alone or fused with the step's K4'
 int rank_launch(Ctx *c, const RankLaunch &a, bool k24, const K24Args &ka) {
-  const auto K = k24 ? k_rank_rows<true> : k_rank_rows<false>;
-  hipLaunchKernelGGL(K, dim3(a.grid), dim3(kRankThreads), 0, c->stream, a.nrows, a.cnt, a.cap, a.rowoff, a.rowcnt,
-                     a.kb, a.B, a.cpay, a.rb, a.ci, a.cj, a.out, a.li, a.lj, a.stats, a.gate, a.build, a.mf,
-                     a.inconf, a.tcpamax, a.cnext, a.wnext, ka, a.nf, k24 ? nullptr : a.hkp);
+  if (a.lean && !k24) return fail(c, "internal: the lean K2 is the fused K2 + K4' only");
+  const auto K = a.lean ? k_rank_rows<true, true> : (k24 ? k_rank_rows<true, false> : k_rank_rows<false, false>);
+  hipLaunchKernelGGL(K, dim3(a.grid + (a.lean ? a.heavy : 0u)), dim3(kRankThreads), 0, c->stream, a.nrows, a.cnt, a.cap,
+                     a.rowoff, a.rowcnt, a.kb, a.B, a.cpay, a.rb, a.ci, a.cj, a.out, a.li, a.lj, a.stats, a.gate, a.build,
+                     a.mf, a.inconf, a.tcpamax, a.cnext, a.wnext, ka, a.nf, k24 ? nullptr : a.hkp, a.hn, a.heavy);
   BSA_HIP(c, hipGetLastError());
   return 0;
 }

@@ -260,10 +260,10 @@ struct CdOut {
 // per-row part may run inside the step's K4' (k_sim_pilot_kin<true>), which
 // also publishes a host-decided detect's prediction, so the host may decide
 // the list; a CD call without kinematics (bsa_sim_cd) launches K3 itself.
-// keep_k2: the detect's K2 is left to the step too (StepPlan::k24).  The
+// keep_k2: the detect's K2 is left to the step too (StepPlan::k24), lean_k2: in its lean form (StepPlan::lean).  The
 // caller counts the call (clk.cd_calls).  Its stages: gather, detect,
 // bookkeeping count, gate all-reduce, K3, bookkeeping apply
-static int sim_cd(Ctx *c, bool in_step, bool keep_k2, CdOut *out) {
+static int sim_cd(Ctx *c, bool in_step, bool keep_k2, bool lean_k2, CdOut *out) {
   const bsa_sim_params &p = c->simp;
   // several ranks: the detect's halo exchange (bsa_halo.hip) refreshes the
   // other ranks' rows this rank reads; one rank holds everything
@@ -274,6 +274,7 @@ static int sim_cd(Ctx *c, bool in_step, bool keep_k2, CdOut *out) {
   q.home = true;
   q.host_decides = in_step;
   q.keep_k2 = keep_k2;
+  q.lean_k2 = keep_k2 && lean_k2;
   // MVP's per-pair vectors are evaluated by K2 as it places each pair;
   // k_mvp_row folds them after the gate
   if (p.reso) {
@@ -318,6 +319,12 @@ struct StepPlan {
   // off) -- K4' then starts on each workgroup's rows as soon as their fold is
   // done, instead of behind the whole of K2
   bool k24;
+  // the fused K2 + K4' in its lean form: no block sums (no k_rowblk launch), no pair lists, no
+  // rowoff, no conf / los counts -- a later CD step of the same bsa_sim_step call overwrites them all before the
+  // host can read any, and with k24's conditions (one rank, no ASAS bookkeeping) nothing on the device reads them.
+  // Not with a stage that can end the batch early (the stop protocol's: conditional commands, the experiment
+  // area), whose stopping step would then be the one the host reads.  bsa_set_lean_pairs / BSA_LEAN_K2=0 off
+  bool lean;
   // one rank, the next step a CD step: K4' also prepares that detect's
   // column records and boxes (its K0b launch is skipped; BSA_SIM_PREP=0 off)
   bool prep;
@@ -353,6 +360,8 @@ static StepPlan step_decide(const Ctx *c, bool rerun_first) {
   sp.cd = k.steps % c->simp.cd_every == 0;
   sp.k24 = sp.cd && env.k24 && c->nranks == 1 && c->halo_mode == 0 && !c->simp.resume_nav && re > rb &&
            c->k2_bucket > 0;
+  sp.lean = sp.k24 && c->lean_on && env.lean_k2 && (c->lean_on == 2 || k.steps + c->simp.cd_every < c->batch_target) && !c->sim_cond &&
+            !c->sim_exparea;
   sp.prep = env.sim_prep && c->nranks == 1 && c->home && !c->reuse_on && c->halo_mode == 0 && rb == 0 &&
             re == c->n && (k.steps + 1) % c->simp.cd_every == 0 &&
             !c->sim_turb;  // turbulence moves the aircraft after K4': the next detect makes its own records (K0b)
@@ -376,7 +385,7 @@ static void step_advance(Ctx *c, const StepPlan &sp) {
   if (c->sim_gv) k.gv_ctr++;
   if (sp.fms_tick) k.fms_t0 = k.fms_simt, k.fms_ticks++;  // Autopilot.update's tick: t0 = simt (autopilot.py:62)
   if (c->sim_fms) k.fms_simt += c->simp.simdt;
-  if (sp.cd) k.cd_calls++;
+  if (sp.cd) k.cd_calls++, (sp.lean ? k.lean_cd : k.full_cd)++;
   if (c->sim_turb) k.turb_call++;
   if (c->sim_sect) k.sect_ctr++;
   if (c->sim_exparea) k.area_ctr++;
@@ -598,6 +607,7 @@ static int step_launch(Ctx *c, const StepPlan &sp, const CdOut &cd, const PrepAr
     if (wind3d_launch(c, rb, re, n, d0.lat, d0.lon, d0.alt)) return -1;
     wf = wind_field_pa(c);
   }
+  if (sp.lean && !(cd.det.k2_kept && cd.det.k2.lean)) return fail(c, "internal: a lean step without its lean K2 + K4'");
   if (cd.det.k2_kept) {
     if (!cd.mvp_deferred) return fail(c, "internal: fused K2 + K4' without the deferred MVP rows");
     if (!ensure(c, c->nx_alt, n * 8, "next altitudes") || !ensure(c, c->nx_vs, n * 8, "next vs") ||
@@ -639,7 +649,7 @@ static int step_enqueue(Ctx *c, const StepPlan &sp) {
   if (c->sim_forces && forces_sim_launch(c, sp.commit_fuel)) return -1;
   if (c->sim_fms && fms_sim_launch(c, sp.fms_tick)) return -1;  // Autopilot.update (bsa_fms.hip)
   CdOut cd;
-  if (sp.cd && sim_cd(c, true, sp.k24, &cd)) {
+  if (sp.cd && sim_cd(c, true, sp.k24, sp.lean, &cd)) {
     invalidate(c, Change::StepNotEnqueued);  // (a detect may have been enqueued without its step's publication)
     return -1;
   }
@@ -787,6 +797,7 @@ int bsa_sim_step(bsa_ctx *cc, int nsteps) {
   BSA_HIP(c, hipSetDevice(c->device));
   if (bsa::trails_reserve(c, nsteps)) return -1;  // (before anything is enqueued: a refused batch runs no step)
   const int64_t start = c->clk.steps, target = start + nsteps;
+  c->batch_target = target;
   c->steps_last = 0;
   for (int attempt = 0; c->clk.steps < target; ++attempt) {
     if (attempt > 6) return bsa::fail(c, "candidate buffer overflow in the resident step (retries exhausted)");
@@ -1130,7 +1141,7 @@ int bsa_sim_cd(bsa_ctx *cc) {
     if (attempt > 6) return bsa::fail(c, "candidate buffer overflow in the CD call (retries exhausted)");
     bsa::BatchBase base;
     bsa::CdOut cd;
-    if (bsa::batch_begin(c, false, &base) || bsa::sim_cd(c, false, false, &cd)) return -1;
+    if (bsa::batch_begin(c, false, &base) || bsa::sim_cd(c, false, false, false, &cd)) return -1;
     c->clk.cd_calls++;  // (a CD call outside a step: step_advance counts a step's)
     bsa::BatchCtl ctl{};
     if (bsa::batch_end(c, &ctl)) return -1;

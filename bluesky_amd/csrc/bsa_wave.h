@@ -41,7 +41,8 @@ __device__ __forceinline__ bool list_word(int k) {
   constexpr int kCand = (int)(offsetof(Counters, cand) / 8), kTiles = (int)(offsetof(Counters, tiles) / 8);
   constexpr int kGroups = (int)(offsetof(Counters, groups) / 8), kStamp = (int)(offsetof(Counters, stamp) / 8);
   constexpr int kNear = (int)(offsetof(Counters, tiles_near) / 8);
-  return k == kCand || k == kTiles || k == kNear || k == kGroups || k >= kStamp;
+  constexpr int kAny = (int)(offsetof(Counters, any_conf) / 8);  // (each detect's evaluation sets it anew)
+  return k == kCand || k == kTiles || k == kNear || k == kGroups || (k >= kStamp && k != kAny);
 }
 
 __device__ __forceinline__ void zero_state(const ZeroArgs &z, int t, int nt) {

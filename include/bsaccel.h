@@ -173,6 +173,25 @@ int bsa_set_symmetric_sweep(bsa_ctx *ctx, int on);
 /* [0] detects enqueued with the symmetric sweep, [1] the last detect's level
  * (0: both orders, 1 / 2 as above). */
 int bsa_symmetric_sweep_stats(bsa_ctx *ctx, int64_t *out2);
+/* Lean pair placement in the resident step (on by default):
+ * in one bsa_sim_step call, every CD step that a later CD step of the same
+ * call follows skips the global placement of its conflict / LoS pair lists
+ * (and the launch that sums the blocks' pair counts for it) -- the later step
+ * overwrites them before the host could read any.  Only where nothing on the
+ * device reads them either: one rank, K2 fused with K4', no ASAS bookkeeping,
+ * no stage that can stop a batch early.  The call's last CD step always places
+ * them, so every result, count and statistic after the call is the same
+ * (A/B; the BSA_LEAN_K2=0 environment variable turns it off in every context).
+ * on = 2 is a testing aid: the call's last CD step runs lean too, after which
+ * the pair lists, their counts and bsa_sim_stats' n_conf / n_los are NOT valid
+ * (the state arrays are); any other value is refused. */
+int bsa_set_lean_pairs(bsa_ctx *ctx, int on);
+/* [0] CD steps since bsa_sim_init that ran lean, [1] that placed their lists. */
+int bsa_lean_pairs_stats(bsa_ctx *ctx, int64_t *out2);
+/* The prefilter items listed for the NEXT detect (longest items first,
+ * DESIGN.md 3.2), tier 0 or 1: *count receives their number, slots[] (if
+ * *count <= cap) their list slots in no particular order.  A testing aid. */
+int bsa_listed_items(bsa_ctx *ctx, int tier, uint32_t *slots, int64_t cap, int64_t *count);
 /* Candidate-list reuse across detects (own == intruder, whole row range, not
  * KWIK / NOPRUNE).  A detect that builds the list inflates
  * every aircraft's reach by a horizontal budget sigma_h [m] and a vertical
